@@ -3,7 +3,15 @@
 cfg2 -- one 640x480 view per step, 192 samples/ray (96 coarse + 96 fine),
 hash grid L=16, MLP width 64, 40 classes, fp32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up (the field's deterministic pre-training, the rays of every
+view), warms up, times K views and prints the line.  --dump-outputs DIR then
+writes the last timed view's render() outputs as DIR/<name>.npy (float32):
+with the same arguments the inputs are the same bits on every run, so two
+builds compare output for output.  --full adds every other measurement
+listed below (per-stage times, rooflines, quality, training legs, tuning-table
+check, CPU baseline; at N > 1 the data-parallel training leg).
 
 N > 1 is launched by the driver through torch.distributed.run, one rank per
 GPU.  Rendering shards by view (rays are independent): every rank renders its
@@ -12,7 +20,7 @@ collective ("scaling": "weak"); the only collectives are the timing barrier
 and the max-over-ranks of the elapsed time.
 
 stdout carries ONE compact JSON line (<= 4 KB, tools/bench_legs/headline.py):
-metric / value / ms_per_step / config{workload, ...} / roofline (dominant
+metric / value / ms_per_step / config{workload, ...} and, with --full, roofline (dominant
 kernel: the hash-grid gather, algorithmic bytes per launch / live event-timed
 launch duration against the 8 TB/s HBM line, PMC traffic, the unit that
 actually binds it) / cpu_baseline (the CPU oracle, "port", on the host cores,
@@ -71,10 +79,17 @@ def parse():
                     help="Adam steps on the synthetic scene before timing "
                          "(SURVEY 8d: 200)")
     ap.add_argument("--no-train-bench", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the rest: per-stage times and "
+                         "rooflines, quality of the last view, training legs, tuning-table "
+                         "check, CPU baseline (N = 1), data-parallel training leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's render() outputs (image, depth, "
+                         "semantics) as DIR/<name>.npy, float32")
     ap.add_argument("--detail", action="store_true",
                     help="also run the side legs (other MLP arithmetics, fp16 "
                          "table, marcher, every training precision, DeepLab) "
-                         "into bench_detail.json; the stdout line is the same")
+                         "into bench_detail.json; the stdout line is the same; implies --full")
     ap.add_argument("--scenes", type=int, default=10, help="cfg5: rooms in the loop")
     ap.add_argument("--nerf-epochs", type=int, default=2, help="cfg5: NeRF-only epochs per scene")
     ap.add_argument("--joint-epochs", type=int, default=1, help="cfg5: joint epochs per scene")
@@ -117,7 +132,26 @@ def parse():
     ap.add_argument("--views", type=int, default=512, help="cfg4: views in total")
     ap.add_argument("--gather", action="store_true",
                     help="cfg4: gather the images on rank 0 inside the timed region")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "render":
+        ap.error("--dump-outputs writes the render mode's outputs")
+    args.full = args.full or args.detail
+    return args
+
+
+def dump_outputs(out, path):
+    """What the timed path returned in its last step, as `path`/<name>.npy in
+    float32: image [1,H*W,3], depth [1,H*W], semantics [1,H*W,40] -- 54 MB for
+    one 640x480 view, under the 64 MB a dump may take."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    _tick(f"outputs written to {path}")
 
 
 def cpu_baseline(net, pose, intr, n_rays, threads):
@@ -426,11 +460,14 @@ def main():
         return main_cfg5(args, dev, dist, world, rank, backend)
     prelog = {}
     _tick("imports, device")
-    net, scene_ds = build_field(dev, train_steps=args.pretrain_steps, log=prelog)
+    # deterministic: the table gradient through the order-independent reduction,
+    # so that the same arguments give the same field, bit for bit, on every run
+    # (the inputs of --dump-outputs)
+    net, scene_ds = build_field(dev, train_steps=args.pretrain_steps, log=prelog,
+                                deterministic=True)
     _tick("field pre-trained")
     if dist:
-        # the pre-training is not bit-reproducible (float atomics in the grid
-        # backward): all ranks render / train rank 0's field
+        # all ranks render / train rank 0's field
         from ucsa_neural_rendering_amd import dist as udist_
         udist_.broadcast_parameters_(net)
     net.hip_ray_chunk = 65536
@@ -481,29 +518,12 @@ def main():
     result = None
     if rank == 0:
         assert torch.isfinite(out["image"]).all()
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         # the chunk render() really launches (whole 8-row bands of the image,
         # balanced over the pipelined call's chunks)
         chunk = net.infer_chunk(H * W, W)[0]
-        o, d, nrm = rays[0]
-        chunk_in = (o[0, :chunk].contiguous(), d[0, :chunk].contiguous(),
-                    nrm[0, :chunk, 0].contiguous(), u[:chunk])
-        st, rho = stage_times(net, *chunk_in, image_width=W, mode=args.nerf_precision)
-        samples = chunk * T_COARSE
-        masked = rho * chunk * (T_COARSE + T_FINE)
-        mlp_flop = masked * (12544 + 7040)
-        mlp_tf = mlp_flop / (st["composite"] * 1e-3) / 1e12
-        sig_tf = samples * 6144 / (0.5 * (st["sigma_c"] + st["sigma_f"]) * 1e-3) / 1e12
         ms_step = elapsed / args.steps * 1e3
-        S = T_COARSE + T_FINE
-        # whole view, SURVEY 8d / BASELINE.md 2.4 definitions
-        step_bytes_fp32 = H * W * (204 + S * 1024)        # this build: fp32 table
-        step_bytes_fp16 = H * W * (204 + S * 512)         # the definition's fp16 table
-        step_flop = H * W * S * (6144 + rho * 19584)
-        roof_enc = encoder_roofline(st, chunk, args.pretrain_steps)
-        roof_cmp = composite_pmc(composite_roofline(args.nerf_precision, mlp_tf, sig_tf,
-                                                    st["composite"]),
-                                 args.nerf_precision, args.pretrain_steps)
-        enc_share = st["encode_c"] + st["encode_f"]
         result = {
             "metric": "rays/sec",
             "value": value,
@@ -527,13 +547,36 @@ def main():
                                    "synthetic box-room scene (SURVEY 8d)"
                                    % prelog.get("pretrain_steps", 0),
                 "pretrain": prelog,
-                "masked_fraction_rho": rho,
                 "sharding": "views round-robin over ranks, no data-path collective",
                 "timed_region": "net.render() of one view per step (rows a2-a10), rays and "
                                 "uniforms resident in HBM; get_rays (a1, ~10 us/view) runs "
                                 "before it (--mode cfg4 times it per view)",
                 "mlp_arithmetic": MLP_ARITHMETIC[args.nerf_precision],
             },
+        }
+        _tick("headline measured")
+    if rank == 0 and args.full:
+        o, d, nrm = rays[0]
+        chunk_in = (o[0, :chunk].contiguous(), d[0, :chunk].contiguous(),
+                    nrm[0, :chunk, 0].contiguous(), u[:chunk])
+        st, rho = stage_times(net, *chunk_in, image_width=W, mode=args.nerf_precision)
+        samples = chunk * T_COARSE
+        masked = rho * chunk * (T_COARSE + T_FINE)
+        mlp_flop = masked * (12544 + 7040)
+        mlp_tf = mlp_flop / (st["composite"] * 1e-3) / 1e12
+        sig_tf = samples * 6144 / (0.5 * (st["sigma_c"] + st["sigma_f"]) * 1e-3) / 1e12
+        S = T_COARSE + T_FINE
+        # whole view, SURVEY 8d / BASELINE.md 2.4 definitions
+        step_bytes_fp32 = H * W * (204 + S * 1024)        # this build: fp32 table
+        step_bytes_fp16 = H * W * (204 + S * 512)         # the definition's fp16 table
+        step_flop = H * W * S * (6144 + rho * 19584)
+        roof_enc = encoder_roofline(st, chunk, args.pretrain_steps)
+        roof_cmp = composite_pmc(composite_roofline(args.nerf_precision, mlp_tf, sig_tf,
+                                                    st["composite"]),
+                                 args.nerf_precision, args.pretrain_steps)
+        enc_share = st["encode_c"] + st["encode_f"]
+        result["config"]["masked_fraction_rho"] = rho
+        result.update({
             # "roofline" = the kernel with the largest share of the step
             "roofline": roof_enc if enc_share >= st["composite"] else roof_cmp,
             "roofline_encode": roof_enc,
@@ -556,7 +599,7 @@ def main():
                          "peak_fp16_dense_tflops": F16_MFMA_PEAK_TF},
             },
             "stage_ms_per_chunk": st,
-        }
+        })
         # quality of the timed renders: last view vs the analytic ground truth
         t_hit, gt_rgb, gt_lab = scene_ds.room.cast(rays[n_views - 1][0][0], rays[n_views - 1][1][0])
         mse = torch.mean((out["image"][0] - gt_rgb) ** 2)
@@ -566,7 +609,7 @@ def main():
         meter.update(pred_lab, gt_lab)
         result["quality"] = {"psnr_db": float(-10 * torch.log10(mse)),
                              "miou": meter.measure()[0]}
-        _tick("headline measured")
+        _tick("stage times, rooflines and quality measured")
         # The side measurements below are single-GPU figures: at N > 1 the
         # other ranks would only wait for rank 0, so they run at N = 1 only.
         extras = world == 1
@@ -617,9 +660,10 @@ def main():
                 "gpu_over_cpu": value / v,
             }
             _tick("CPU baseline done")
-    if dist:
+    if dist and args.full:
         # the data-parallel training step with its gradient collectives: all
-        # ranks take part; rank 0 reports it in the detail file
+        # ranks take part (every rank has the same argv, so the same --full);
+        # rank 0 reports it in the detail file
         from tools.bench_legs.train import dp_train_leg
         tr = dp_train_leg(net, scene_ds, dev, dist, world, rank, backend,
                           steps=min(args.steps, 20), replicated=args.replicated_adam,

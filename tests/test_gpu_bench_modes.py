@@ -1,6 +1,6 @@
 """bench.py's multi-rank code paths, exercised with two ranks on ONE GPU
 (`UCSA_BENCH_BACKEND=gloo`, the test hook; the driver's real runs use RCCL,
-one rank per GPU): the default render line at N = 2 with its `train_dp`
+one rank per GPU): the `--full` render line at N = 2 with its `train_dp`
 object, `--mode train` and `--mode cfg4 --gather`.  ``-m gpu``."""
 import json
 import os
@@ -89,7 +89,7 @@ def _parse(rc, out, err):
 
 
 def test_default_render_line_at_two_ranks_carries_train_dp(tmp_path):
-    res = _run2(["--steps", "2", "--warmup", "1", "--pretrain-steps", "30"], tmp_path)
+    res = _run2(["--steps", "2", "--warmup", "1", "--pretrain-steps", "30", "--full"], tmp_path)
     assert res["n_gpus"] == 2 and res["scaling"] == "weak" and res["metric"] == "rays/sec"
     assert res["value"] > 0 and res["roofline"]["bound"] == "hbm"
     assert "cpu_baseline" not in res            # single-GPU legs run at N = 1 only
@@ -126,7 +126,7 @@ def test_cfg4_mode_two_ranks_with_gather(tmp_path):
 # that width (round-robin shards, max-over-ranks timing, aggregate `value`, the
 # 8-way ShardedHipAdam slices), not a measurement.
 def test_default_render_line_at_eight_ranks(tmp_path):
-    res = _run2(["--steps", "2", "--warmup", "1", "--pretrain-steps", "20"], tmp_path,
+    res = _run2(["--steps", "2", "--warmup", "1", "--pretrain-steps", "20", "--full"], tmp_path,
                 timeout=1500, ranks=8)
     assert res["n_gpus"] == 8 and res["scaling"] == "weak" and res["distributed"]["world_size"] == 8
     assert len(res["distributed"]["devices"]) == 8
@@ -223,14 +223,14 @@ def test_cfg3_mode_two_joint_steps_one_process(tmp_path):
 
 
 def test_the_default_command_prints_the_compact_record(tmp_path):
-    """`python bench.py` (short: 3 steps, 30 pre-training steps): ONE stdout
+    """`python bench.py --full` (short: 3 steps, 30 pre-training steps): ONE stdout
     line, <= 4 KB, with the roofline and cpu_baseline objects the driver
     records; the side legs are in the detail file."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     out, err = tmp_path / "out.txt", tmp_path / "err.txt"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-           "--pretrain-steps", "30", "--cpu-rays", "2048"]
+           "--pretrain-steps", "30", "--cpu-rays", "2048", "--full"]
     with open(out, "w") as fo, open(err, "w") as fe:
         rc = subprocess.Popen(cmd, stdout=fo, stderr=fe, stdin=subprocess.DEVNULL,
                               env=env, cwd=ROOT).wait(timeout=900)
@@ -292,3 +292,40 @@ def test_cfg5_mode_three_stages_at_true_sizes(tmp_path):
     q = full["quality"]["final_stage"]
     assert 0.0 <= q["test_nerf_mIoU"] <= 1.0 and q["test_nerf_PSNR"] == q["test_nerf_PSNR"]
     assert full["throughput"]["joint_steps_per_s"] > 0
+
+
+def test_plain_command_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the headline only (no
+    roofline, CPU baseline, quality, training or per-stage legs), and the last
+    timed view's render() outputs in DIR, float32, at most 64 MB.  A second run
+    with the same arguments writes the same bits: the pre-training is
+    deterministic and the rays and uniforms are seeded."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    names = ("depth", "image", "semantics")
+    dumps = []
+    for run in (1, 2):
+        out, err, dump = tmp_path / f"out{run}.txt", tmp_path / f"err{run}.txt", tmp_path / f"dump{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+               "--pretrain-steps", "30", "--dump-outputs", str(dump)]
+        with open(out, "w") as fo, open(err, "w") as fe:
+            rc = subprocess.Popen(cmd, stdout=fo, stderr=fe, stdin=subprocess.DEVNULL,
+                                  env=env, cwd=ROOT).wait(timeout=600)
+        res = _parse(rc, out, err)
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["dtype"] == "f32"
+        assert res["value"] == pytest.approx(640 * 480 / (res["ms_per_step"] * 1e-3), rel=1e-4)
+        for k in ("roofline", "cpu_baseline", "quality", "train", "tuning_tables_matched"):
+            assert k not in res, k
+        for k in ("stage_ms_per_chunk", "roofline_step", "cpu_vs_gpu", "train_dp"):
+            assert k not in res["_full"], k
+        assert sorted(os.listdir(dump)) == [n + ".npy" for n in names]
+        dumps.append({n: np.load(dump / (n + ".npy")) for n in names})
+    a, b = dumps
+    assert a["image"].shape == (1, 640 * 480, 3) and a["depth"].shape == (1, 640 * 480)
+    assert a["semantics"].shape == (1, 640 * 480, 40)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.isfinite(a["image"]).all() and 0.0 < float(a["image"].mean()) < 1.0
+    for n in names:
+        assert np.array_equal(a[n], b[n]), n

@@ -65,7 +65,8 @@ def test_bench_default_line_under_a_forced_rccl_group(tmp_path):
     world-1 RCCL group recorded, and the data-parallel training leg (sharded
     Adam over RCCL) in the detail file."""
     res, err = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup",
-                     "1", "--pretrain-steps", "30", "--no-cpu-baseline", "--no-train-bench"],
+                     "1", "--pretrain-steps", "30", "--no-cpu-baseline", "--no-train-bench",
+                     "--full"],
                     tmp_path, _env())
     d = res["distributed"]
     assert d["world_size"] == 1 and d["backend"].startswith("nccl") and d["forced_world_1"] is True
