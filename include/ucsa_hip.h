@@ -1202,6 +1202,38 @@ int32_t ucsa_augment(const float* img, const int64_t* label, uint32_t B,
                      uint32_t oh, uint32_t ow, float* out_img,
                      int64_t* out_label, void* workspace, void* stream);
 
+/* ---- marching cubes (labelled-mesh export of the field) --------------------
+ * Not on the reference's path (its parent code base, torch-ngp, ran marching
+ * cubes on the CPU in extract_geometry / save_mesh).  Two passes over a dense
+ * lattice field [nx,ny,nz] fp32, point (i,j,k) at field[(i*ny + j)*nz + k] and
+ * at origin + (i,j,k)*spacing; a point is inside iff field > iso.
+ *   ucsa_mc_count: cell cases, edge crossings and their prefix sums into the
+ *     workspace; totals_dev[0] = V vertices, [1] = F triangles (uint32, device).
+ *     A total above 2^31-1 is written as 0xFFFFFFFF in both: do not emit then.
+ *   ucsa_mc_emit: verts [V,3], normals [V,3] fp32, tris [F,3] int32 into
+ *     caller buffers sized from the totals (max_verts / max_faces: their
+ *     capacities; nothing is written beyond them).  origin3 / spacing3 are HOST
+ *     float[3].  Pass the same field, dims, iso and workspace as to the count.
+ * Point p owns its +x,+y,+z edges (edge id 3*p + axis); one vertex per
+ * crossing edge, in ascending edge id, shared by all its triangles.  Triangles
+ * by ascending cell (= lower-corner point) index, then in table order, wound so
+ * that face normals point toward lower field values.  Vertex on an edge:
+ * t = (iso - f0) / (f1 - f0) (f0 at the lower index), coordinate along the
+ * axis x0 + t*spacing.  Normal: -grad f by central differences (one-sided on
+ * the lattice boundary) at both ends, lerped by t, normalised; (0,0,0) when
+ * zero.  All fp32, no contraction, correctly rounded division / sqrt: the same
+ * bits as the obvious numpy float32 code.  No atomics: two runs give the same
+ * bytes.  Dims >= 2 each, nx*ny*nz <= 2^31-1 (else argument 1). */
+uint64_t ucsa_mc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int32_t ucsa_mc_count(const float* field, uint32_t nx, uint32_t ny, uint32_t nz,
+                      float iso, void* workspace, uint32_t* totals_dev,
+                      void* stream);
+int32_t ucsa_mc_emit(const float* field, uint32_t nx, uint32_t ny, uint32_t nz,
+                     float iso, const float* origin3, const float* spacing3,
+                     const void* workspace, float* verts, float* normals,
+                     int32_t* tris, uint32_t max_verts, uint32_t max_faces,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

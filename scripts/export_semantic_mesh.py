@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Export a trained semantic field as a labelled mesh (binary PLY in the layout
+of ScanNet's ``*_vh_clean_2.labels.ply``: per-vertex NYU40 ``label``, colour,
+normal) and, with ``--gt``, print its 3D semantic score against a labelled
+ground-truth mesh.
+
+    python scripts/train_joint.py ... --save_nerf nerf.pt
+    python scripts/export_semantic_mesh.py --nerf_state nerf.pt --out mesh.ply \\
+        [--resolution 256] [--threshold 10] [--aabb -4 -4 -4 4 4 4] \\
+        [--gt scene.labels.ply] [--one_m_to_scene_uom U]
+
+Without ``--one_m_to_scene_uom`` the mesh is written in the field's (NGP) frame
+and ``--gt`` vertices are read in that frame.  With it (the value of the scene's
+transforms_train.json), the mesh is written in the frame of that file's poses,
+in metres, and ``--gt`` vertices are read in that frame
+(utils/semantic_mesh.py says how that frame relates to ScanNet's own)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ucsa_neural_rendering_amd.nerf.network_tcnn_semantics import \
+    SemanticNeRFNetwork  # noqa: E402
+from ucsa_neural_rendering_amd.utils.ply import read_ply, write_ply  # noqa: E402
+from ucsa_neural_rendering_amd.utils.semantic_mesh import (  # noqa: E402
+    evaluate_semantic_mesh, ngp_to_pose_frame, pose_frame_to_ngp)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--nerf_state", required=True,
+                   help="file written by scripts/train_joint.py --save_nerf")
+    p.add_argument("--resolution", type=int, default=256)
+    p.add_argument("--threshold", type=float, default=10.0,
+                   help="density iso level of the surface")
+    p.add_argument("--aabb", type=float, nargs=6, default=None,
+                   help="lattice box in the field's frame (default: the field's aabb)")
+    p.add_argument("--out", required=True, help="output .ply")
+    p.add_argument("--gt", default=None, help="labelled ground-truth mesh (.ply)")
+    p.add_argument("--one_m_to_scene_uom", type=float, default=None)
+    return p.parse_args(argv)
+
+
+def load_network(path, device="cuda"):
+    st = torch.load(path, map_location="cpu")
+    cfg = st["config"]
+    net = SemanticNeRFNetwork(encoding="hashgrid", bound=cfg["bound"],
+                              cuda_ray=cfg["cuda_ray"], density_scale=1,
+                              num_semantic_classes=cfg["num_semantic_classes"])
+    net.load_state_dict(st["state_dict"])
+    return net.to(device).eval()
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    net = load_network(a.nerf_state)
+    t0 = time.perf_counter()
+    m = net.extract_semantic_mesh(a.resolution, a.threshold, a.aabb)
+    t_extract = time.perf_counter() - t0
+    verts, normals = m["verts"], m["normals"]
+    if a.one_m_to_scene_uom is not None:
+        verts = ngp_to_pose_frame(verts, a.one_m_to_scene_uom).astype(np.float32)
+        normals = ngp_to_pose_frame(normals).astype(np.float32)
+    write_ply(a.out, verts, m["faces"], normals, m["rgb"], m["labels"] + 1)
+    rec = {"out": a.out, "verts": int(verts.shape[0]), "faces": int(m["faces"].shape[0]),
+           "extract_s": round(t_extract, 3)}
+    if a.gt:
+        gt = read_ply(a.gt)
+        gv = gt["verts"]
+        if a.one_m_to_scene_uom is not None:
+            gv = pose_frame_to_ngp(gv, a.one_m_to_scene_uom)
+        rec.update(evaluate_semantic_mesh(net, gv, gt["labels"]))
+    print(json.dumps(rec))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

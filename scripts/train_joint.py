@@ -38,6 +38,9 @@ def parse_args(argv=None):
     p.add_argument("--joint_train_epoch", default=10, type=int)
     p.add_argument("--limit_batches", default=None, type=int,
                    help="extra: cap batches per loop (smoke runs)")
+    p.add_argument("--save_nerf", default=None, metavar="PATH",
+                   help="extra: after training, save the NeRF's state to PATH "
+                        "(for scripts/export_semantic_mesh.py); off by default")
     return p.parse_args(argv)
 
 
@@ -126,6 +129,12 @@ def _train(exp, env, args, rank, local_rank, world, model_path):
     if rank == 0:
         torch.save({"state_dict": model.seg_model.state_dict()},
                    os.path.join(model_path, "deeplab.ckpt"))
+        if getattr(args, "save_nerf", None):  # callers may pass their own namespace
+            nerf = model.nerf_model
+            torch.save({"state_dict": nerf.state_dict(),
+                        "config": {"bound": nerf.bound, "cuda_ray": nerf.cuda_ray,
+                                   "num_semantic_classes": nerf.num_semantic_classes}},
+                       args.save_nerf)
     return results
 
 

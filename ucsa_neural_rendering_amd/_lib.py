@@ -296,6 +296,11 @@ SIGNATURES = {
     "ucsa_density_grid_workspace_bytes": (C.c_uint64, []),
     "ucsa_density_grid_update": (C.c_int32, [_p, _p, C.c_uint64, _f, _f, _p,
                                              _p, _p]),
+    # ---- marching cubes (mesh export) ----
+    "ucsa_mc_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32]),
+    "ucsa_mc_count": (C.c_int32, [_p, _u32, _u32, _u32, _f, _p, _p, _p]),
+    "ucsa_mc_emit": (C.c_int32, [_p, _u32, _u32, _u32, _f, C.POINTER(_f),
+                                 C.POINTER(_f), _p, _p, _p, _p, _u32, _u32, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

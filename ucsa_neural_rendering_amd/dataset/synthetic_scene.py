@@ -80,6 +80,100 @@ class SyntheticRoom:
             setattr(self, k, getattr(self, k).to(device))
         return self
 
+    def _faces(self):
+        """The room's visible rectangles: (axis, plane coordinate, lo [3], hi [3],
+        class).  Room faces (-x,+x,-y,+y,-z,+z), then per box the four sides
+        and the top (the bottom rests on the floor)."""
+        out = []
+        lo, hi = self.room[0].cpu(), self.room[1].cpu()
+        for f in range(6):
+            ax, side = f // 2, f % 2
+            out.append((ax, float((hi if side else lo)[ax]), lo, hi, int(self.room_cls[f])))
+        for b in range(self.boxes.shape[0]):
+            blo, bhi = self.boxes[b, 0].cpu(), self.boxes[b, 1].cpu()
+            for f in (0, 1, 2, 3, 5):
+                ax, side = f // 2, f % 2
+                out.append((ax, float((bhi if side else blo)[ax]), blo, bhi,
+                            int(self.box_cls[b])))
+        return out
+
+    @torch.no_grad()
+    def labelled_mesh(self, step=0.05):
+        """The analytic room as a labelled triangle mesh (ground truth for the
+        mesh export): every visible rectangle of ``_faces`` on a grid of about
+        ``step`` scene units, two triangles per grid square; vertices that lie
+        in or on another box, or outside the room, are dropped with their
+        triangles (the floor under a box, box parts inside a wall).  Vertices
+        are not shared between rectangles, so each carries one class.
+        -> dict of numpy arrays: verts [V,3] f32, faces [F,3] int32 (normals
+        toward the empty space), labels [V] NYU40 ids (class + 1, as in
+        ScanNet's labels.ply), face_classes [F] class ids."""
+        room_lo, room_hi = self.room[0].cpu(), self.room[1].cpu()
+        boxes = self.boxes.cpu()
+        verts, faces, labels, fcls = [], [], [], []
+        base = 0
+        for fi, (ax, c, lo, hi, cls) in enumerate(self._faces()):
+            u, v = [a for a in range(3) if a != ax]
+            nu = max(1, int(math.ceil(float(hi[u] - lo[u]) / step)))
+            nv = max(1, int(math.ceil(float(hi[v] - lo[v]) / step)))
+            gu = torch.linspace(float(lo[u]), float(hi[u]), nu + 1, dtype=torch.float64)
+            gv = torch.linspace(float(lo[v]), float(hi[v]), nv + 1, dtype=torch.float64)
+            P = torch.empty(nu + 1, nv + 1, 3, dtype=torch.float64)
+            P[..., ax] = c
+            P[..., u] = gu[:, None]
+            P[..., v] = gv[None, :]
+            P = P.reshape(-1, 3)
+            keep = ((P >= room_lo.double() - 1e-9) & (P <= room_hi.double() + 1e-9)).all(1)
+            own = fi - 6 if fi >= 6 else -1
+            own_box = own // 5 if own >= 0 else -1
+            for b in range(boxes.shape[0]):
+                if b == own_box:
+                    continue
+                inside = ((P >= boxes[b, 0].double() - 1e-9) &
+                          (P <= boxes[b, 1].double() + 1e-9)).all(1)
+                keep &= ~inside
+            idx = torch.arange((nu + 1) * (nv + 1)).view(nu + 1, nv + 1)
+            a, b_, c_, d = (idx[:-1, :-1], idx[1:, :-1], idx[1:, 1:], idx[:-1, 1:])
+            quads = torch.stack([a, b_, c_, d], -1).reshape(-1, 4)
+            tri = torch.cat([quads[:, [0, 1, 2]], quads[:, [0, 2, 3]]], 0)
+            # winding: normal (e_u x e_v) points along +ax; it must point to
+            # the empty side (into the room for room faces, out of a box)
+            room_face = fi < 6
+            side_hi = c >= float(hi[ax]) - 1e-9 and c > float(lo[ax])
+            positive = (room_face and not side_hi) or (not room_face and side_hi)
+            if (u, v) == (0, 2):  # e_x x e_z = -e_y
+                positive = not positive
+            if not positive:
+                tri = tri[:, [0, 2, 1]]
+            tri = tri[keep[tri].all(1)]
+            remap = torch.full((P.shape[0],), -1, dtype=torch.int64)
+            remap[keep] = torch.arange(int(keep.sum())) + base
+            verts.append(P[keep].float())
+            faces.append(remap[tri])
+            labels.append(torch.full((int(keep.sum()),), cls + 1, dtype=torch.int64))
+            fcls.append(torch.full((tri.shape[0],), cls, dtype=torch.int64))
+            base += int(keep.sum())
+        return {"verts": torch.cat(verts).numpy(),
+                "faces": torch.cat(faces).to(torch.int32).numpy(),
+                "labels": torch.cat(labels).numpy(),
+                "face_classes": torch.cat(fcls).numpy()}
+
+    @torch.no_grad()
+    def nearest_surface(self, points):
+        """points [N,3] (torch, any device) -> (distance [N] to the nearest
+        rectangle of ``_faces``, that rectangle's class [N])."""
+        p = points.double()
+        best_d = torch.full((p.shape[0],), float("inf"), dtype=torch.float64, device=p.device)
+        best_c = torch.zeros(p.shape[0], dtype=torch.int64, device=p.device)
+        for ax, c, lo, hi, cls in self._faces():
+            q = torch.minimum(torch.maximum(p, lo.double().to(p.device)), hi.double().to(p.device))
+            q[:, ax] = c
+            d = (p - q).norm(dim=1)
+            closer = d < best_d
+            best_d = torch.where(closer, d, best_d)
+            best_c = torch.where(closer, torch.full_like(best_c, cls), best_c)
+        return best_d, best_c
+
     @torch.no_grad()
     def cast(self, rays_o, rays_d):
         """rays [N,3] (unit d) -> t_hit [N], rgb [N,3], label [N]."""

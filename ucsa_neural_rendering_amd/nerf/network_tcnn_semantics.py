@@ -647,3 +647,84 @@ class SemanticNeRFNetwork(SemanticNeRFRenderer):
         geo = den["geo_feat"].contiguous()
         return (den["sigma"], self.color(x, d, geo_feat=geo),
                 self.semantics(x, d, geo_feat=geo))
+
+    # -- labelled-mesh export (not in the reference; its parent code base,
+    # torch-ngp, had extract_geometry / save_mesh on the CPU) -----------------
+    LATTICE_SLAB_POINTS = 1 << 22
+
+    def _lattice_frame(self, resolution, aabb):
+        res = ((int(resolution),) * 3 if np.isscalar(resolution)
+               else tuple(int(r) for r in resolution))
+        if len(res) != 3 or min(res) < 2:
+            raise ValueError(f"resolution must be >= 2 per axis, got {resolution}")
+        box = self.aabb_infer if aabb is None else aabb
+        box = torch.as_tensor(box, dtype=torch.float32).detach().cpu().reshape(6)
+        lo, hi = box[:3], box[3:]
+        spacing = (hi - lo) / torch.tensor([r - 1 for r in res], dtype=torch.float32)
+        return res, lo, spacing
+
+    @torch.no_grad()
+    def density_lattice(self, resolution, aabb=None):
+        """sigma on a dense lattice [nx,ny,nz] (``resolution``: an int or three),
+        as ``density()`` returns it.  Point (i,j,k) sits at lo + (i,j,k)*spacing
+        (fp32), lo / hi = ``aabb`` [6] (default ``aabb_infer``), spacing =
+        (hi - lo) / (resolution - 1), so the lattice spans the box corner to
+        corner.  Runs in slabs of whole (y,z) planes through
+        ``ops.hashgrid_encode_points`` + ``ops.sigma_mlp_fwd``, at most
+        ``LATTICE_SLAB_POINTS`` (4 Mi) points per slab: the point path keeps
+        ~52 floats per point (coordinates, 32 features, 16 outputs, sigma), so the
+        scratch peaks near 0.9 GB whatever the resolution; the result itself is
+        4 bytes per point (0.54 GB at 512^3)."""
+        (nx, ny, nz), lo, h = self._lattice_frame(resolution, aabb)
+        dev = self.encoder.params.device
+        axes = [(lo[a] + torch.arange(n, dtype=torch.float32) * h[a]).to(dev)
+                for a, n in enumerate((nx, ny, nz))]
+        out = torch.empty(nx, ny, nz, device=dev)
+        plane = ny * nz
+        step = max(1, self.LATTICE_SLAB_POINTS // plane)
+        yz = torch.stack(torch.meshgrid(axes[1], axes[2], indexing="ij"), -1).reshape(-1, 2)
+        for i0 in range(0, nx, step):
+            i1 = min(nx, i0 + step)
+            xs = axes[0][i0:i1]
+            pts = torch.cat([xs.repeat_interleave(plane)[:, None],
+                             yz.repeat(i1 - i0, 1)], 1)
+            out[i0:i1] = self.density(pts)["sigma"].view(i1 - i0, ny, nz)
+        return out
+
+    @torch.no_grad()
+    def extract_semantic_mesh(self, resolution=256, threshold=10.0, aabb=None,
+                              color=True, chunk=1 << 20):
+        """The iso-surface sigma = ``threshold`` of the field as an indexed,
+        labelled mesh: a dict of numpy arrays
+          verts [V,3] f32, faces [F,3] int32, normals [V,3] f32 (outward, i.e.
+          toward lower density; ops.marching_cubes over ``density_lattice``),
+          labels [V] int64 in 0..C-1: argmax of ``semantics()`` on the vertex's
+          ``geo_feat``,
+          rgb [V,3] f32 (``color=True``): ``color()`` seen along -normal, along
+          (0,0,1) where the normal is zero.
+        Vertices are in the field's (NGP) frame; ``utils.semantic_mesh.
+        ngp_to_pose_frame`` maps them into the frame of transforms_train.json.
+        Attributes in chunks of ``chunk`` vertices.  Changes nothing: not the
+        parameters, the occupancy grid, the counters or the RNG state."""
+        res, lo, h = self._lattice_frame(resolution, aabb)
+        sigma = self.density_lattice(res, aabb)
+        verts, faces, normals = ops.marching_cubes(sigma, float(threshold), lo.tolist(),
+                                                   h.tolist())
+        del sigma
+        V = verts.shape[0]
+        labels = torch.empty(V, dtype=torch.int64, device=verts.device)
+        rgb = torch.empty(V, 3, device=verts.device) if color else None
+        for a in range(0, V, chunk):
+            b = min(V, a + chunk)
+            geo = self.density(verts[a:b])["geo_feat"].contiguous()
+            labels[a:b] = self.semantics(None, None, geo_feat=geo).argmax(-1)
+            if color:
+                nrm = normals[a:b]
+                zero = (nrm == 0).all(-1, keepdim=True)
+                view = torch.where(zero, torch.tensor([0.0, 0.0, 1.0], device=nrm.device),
+                                   -nrm)
+                rgb[a:b] = self.color(None, view.contiguous(), geo_feat=geo)
+        out = {"verts": verts, "faces": faces, "normals": normals, "labels": labels}
+        if color:
+            out["rgb"] = rgb
+        return {k: v.cpu().numpy() for k, v in out.items()}

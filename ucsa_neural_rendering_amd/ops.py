@@ -1532,3 +1532,37 @@ def augment(img, label, params, out_size=None):
                              _ptr(out), _ptr(out_l), _ptr(ws), _stream()),
           "ucsa_augment")
     return out, out_l
+
+
+# ---------------------------------------------------------------------------
+# marching cubes (labelled-mesh export)
+# ---------------------------------------------------------------------------
+def marching_cubes(field, iso: float, origin=(0.0, 0.0, 0.0),
+                   spacing=(1.0, 1.0, 1.0)):
+    """Indexed iso-surface of a lattice field [nx,ny,nz] (point (i,j,k) at
+    origin + (i,j,k)*spacing; inside iff field > iso) ->
+    (verts [V,3] f32, faces [F,3] int32, normals [V,3] f32), conventions of
+    ucsa_mc_count / ucsa_mc_emit (include/ucsa_hip.h).  Reads the two totals
+    back once, between the passes.  Workspace: 10 bytes per lattice point."""
+    field = _f32(field, "field")
+    if field.dim() != 3:
+        raise _lib.UcsaError(f"field must be [nx,ny,nz], got {tuple(field.shape)}")
+    nx, ny, nz = (int(s) for s in field.shape)
+    dev = field.device
+    ws = torch.empty(int(lib().ucsa_mc_workspace_bytes(nx, ny, nz)), dtype=torch.uint8,
+                     device=dev)
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
+    check(lib().ucsa_mc_count(_ptr(field), nx, ny, nz, float(iso), _ptr(ws),
+                              _ptr(totals), _stream()), "ucsa_mc_count")
+    V, F = (int(v) & 0xFFFFFFFF for v in totals.tolist())
+    if V > 0x7FFFFFFF or F > 0x7FFFFFFF:
+        raise _lib.UcsaError("marching_cubes: more than 2^31-1 vertices or triangles; "
+                             "use a coarser lattice or split it")
+    verts = torch.empty(V, 3, device=dev)
+    normals = torch.empty(V, 3, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    if V or F:
+        check(lib().ucsa_mc_emit(_ptr(field), nx, ny, nz, float(iso), fvec(origin),
+                                 fvec(spacing), _ptr(ws), _ptr(verts), _ptr(normals),
+                                 _ptr(faces), V, F, _stream()), "ucsa_mc_emit")
+    return verts, faces, normals
