@@ -1234,6 +1234,84 @@ int32_t ucsa_mc_emit(const float* field, uint32_t nx, uint32_t ny, uint32_t nz,
                      int32_t* tris, uint32_t max_verts, uint32_t max_faces,
                      void* stream);
 
+/* ---- mesh rasterization (not in the reference) ----------------------------
+ * A triangle mesh seen from B posed pinhole cameras -> per pixel the visible
+ * face, its z-depth, NYU40 label and colour (mesh-rendered labels / depth at
+ * any pose; utils/mesh_render.py, scripts/render_mesh_labels.py).  Two passes:
+ *   ucsa_raster_setup: per (view, face) a clipped, snapped record and the
+ *     number of 16x16 screen tiles its box touches; per-tile counts and their
+ *     scan.  total_dev[0] (uint64, device) = the (tile, face) pair total.
+ *   ucsa_raster_draw: the tile lists into `pairs` (uint32, capacity
+ *     max_pairs; total_pairs = the value read back from total_dev, at most
+ *     2^31-1), then one work-group per tile writes tri_id / depth / label
+ *     [B,H,W] and rgb [B,H,W,3] (capacity max_pixels >= B*H*W elements each).
+ *     A capacity too small: argument error, nothing is written.  Pass the same
+ *     mesh, cameras and workspace as to the setup.
+ * Inputs: verts [V,3], faces [F,3] int32 (a face with an index outside
+ * [0,V), read as unsigned, is skipped), poses [B,4,4] camera-to-world in the
+ * field's (NGP) frame (the poses of ucsa_get_rays), fx, fy > 0, cx, cy HOST
+ * scalars, 1 <= H, W <= 16384, near > 0, B <= 65535, B*F <= 2^31-1;
+ * vertex_labels [V] int32 and vertex_rgb [V,3] may be NULL (label 0; rgb not
+ * written, rgb may then be NULL).
+ * Contract (fp32, no contraction, correctly rounded division; a numpy
+ * restatement gives the same bits: tests/raster_numpy.py).  R = P[0:3,0:3],
+ * t = P[0:3,3]:
+ *   camera point of vertex p: d = p - t, c_r = (d0*R0r + d1*R1r) + d2*R2r;
+ *   planes s(c) >= 0 keep: near z - near; guard band with G = 65536 px:
+ *     x*fx + z*kL, z*kR - x*fx, y*fy + z*kT, z*kB - y*fy, where kL = cx + G,
+ *     kR = (W + G) - cx, kT = cy + G, kB = (H + G) - cy (fp32);
+ *   a face with a non-finite camera coordinate, or with all three corners
+ *     outside one plane (s < 0 or NaN), draws nothing; a face inside all five
+ *     is not clipped; otherwise Sutherland-Hodgman in that plane order,
+ *     polygon from corners (0,1,2), edges (i, i+1 mod n), each kept vertex
+ *     then the crossing vertex.  Every vertex carries the mask of the
+ *     corners it lies on (corner k: 1<<k; new vertex: the union when that has
+ *     two bits, else 7).  Crossing point of edge (A,B): with a two-bit union
+ *     {i,j}, P and Q are the corners i and j, lower vertex index first (equal
+ *     indices: lower corner), else P = A, Q = B; t = s(P) / (s(P) - s(Q)),
+ *     NaN or < 0 -> 0, > 1 -> 1; X = P + t*(Q - P) per coordinate.  Faces
+ *     sharing an edge thus get the same bits on it.  More than 12 vertices
+ *     during, fewer than 3 or more than 8 after (rounding only): nothing;
+ *   projection u = fx*(x/z) + cx, v = fy*(y/z) + cy, NaN or < -2^21 -> -2^21,
+ *     > 2^21 -> 2^21; snapped X = rint(u*256), Y = rint(v*256) (round half to
+ *     even, int32);
+ *   coverage: fan triangles (0, k+1, k+2) of the polygon; area
+ *     E(A->B, C) with E(P->Q, X) = (Qx-Px)(Xy-Py) - (Qy-Py)(Xx-Px) in int64;
+ *     area 0 covers nothing, area < 0 swaps B and C; pixel (x, y) has centre
+ *     (256x + 128, 256y + 128) and is covered iff for each edge P->Q of
+ *     (A,B,C): E > 0, or E == 0 and the edge owns it (dy > 0, or dy == 0 and
+ *     dx < 0, with (dx, dy) = Q - P).  No culling: both windings are drawn;
+ *   depth of a covered pixel: ray d = ((x+0.5-cx)/fx, (y+0.5-cy)/fy, 1)
+ *     (k_get_rays' order), e1 = c1-c0, e2 = c2-c0 of the UNCLIPPED corners,
+ *     n = e1 x e2 (n0 = e1y*e2z - e1z*e2y, n1 = e1z*e2x - e1x*e2z,
+ *     n2 = e1x*e2y - e1y*e2x), z = dot(n, c0) / ((n0*dx + n1*dy) + n2)
+ *     (dot(a,b) = (a0*b0 + a1*b1) + a2*b2); non-finite -> zhi; clamped into
+ *     [zlo, zhi], zlo = max(min z of the polygon, near), zhi = max(max z, zlo);
+ *   visibility: the smallest key (float_bits(z) << 32) | face id wins;
+ *   attributes: q = (z*dx - c0x, z*dy - c0y, z - c0z), w1 = dot(n, q x e2) /
+ *     dot(n, n), w2 = dot(n, e1 x q) / dot(n, n), w0 = (1 - w1) - w2; any
+ *     non-finite -> (1, 0, 0); label = vertex_labels of the corner with the
+ *     largest w (ties: lowest corner); rgb = (w0*rgb0 + w1*rgb1) + w2*rgb2;
+ *     depth = z, tri_id = face id.  Empty pixel: -1, 0, 0, (0, 0, 0).
+ * Deterministic (integer atomics only, the winner is a minimum): two runs give
+ * the same bytes.  Workspace (ucsa_raster_workspace_bytes): 132 bytes per
+ * (view, face), 8 per 1024 (view, face), 12 per (view, 16x16 tile) plus
+ * (tilesX + tilesY + 1) * 4 per view. */
+uint64_t ucsa_raster_workspace_bytes(uint32_t B, uint32_t F, uint32_t H, uint32_t W);
+int32_t ucsa_raster_setup(const float* verts, uint32_t V, const int32_t* faces,
+                          uint32_t F, const float* poses, uint32_t B, float fx,
+                          float fy, float cx, float cy, uint32_t H, uint32_t W,
+                          float near, void* workspace, uint64_t* total_dev,
+                          void* stream);
+int32_t ucsa_raster_draw(const float* verts, uint32_t V, const int32_t* faces,
+                         uint32_t F, const float* poses, uint32_t B, float fx,
+                         float fy, float cx, float cy, uint32_t H, uint32_t W,
+                         float near, const int32_t* vertex_labels,
+                         const float* vertex_rgb, void* workspace, uint32_t* pairs,
+                         uint64_t total_pairs, uint64_t max_pairs, int32_t* tri_id,
+                         float* depth, int32_t* label, float* rgb,
+                         uint64_t max_pixels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -301,6 +301,13 @@ SIGNATURES = {
     "ucsa_mc_count": (C.c_int32, [_p, _u32, _u32, _u32, _f, _p, _p, _p]),
     "ucsa_mc_emit": (C.c_int32, [_p, _u32, _u32, _u32, _f, C.POINTER(_f),
                                  C.POINTER(_f), _p, _p, _p, _p, _u32, _u32, _p]),
+    # ---- mesh rasterization ----
+    "ucsa_raster_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32, _u32]),
+    "ucsa_raster_setup": (C.c_int32, [_p, _u32, _p, _u32, _p, _u32, _f, _f, _f, _f,
+                                      _u32, _u32, _f, _p, _p, _p]),
+    "ucsa_raster_draw": (C.c_int32, [_p, _u32, _p, _u32, _p, _u32, _f, _f, _f, _f,
+                                     _u32, _u32, _f, _p, _p, _p, _p, C.c_uint64,
+                                     C.c_uint64, _p, _p, _p, _p, C.c_uint64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -7,6 +7,7 @@ on torch's current stream.  No arithmetic happens here.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from typing import Optional, Tuple
@@ -1566,3 +1567,85 @@ def marching_cubes(field, iso: float, origin=(0.0, 0.0, 0.0),
                                  fvec(spacing), _ptr(ws), _ptr(verts), _ptr(normals),
                                  _ptr(faces), V, F, _stream()), "ucsa_mc_emit")
     return verts, faces, normals
+
+
+# ---------------------------------------------------------------------------
+# mesh rasterization (labelled meshes into camera views)
+# ---------------------------------------------------------------------------
+RASTER_MAX_DIM = 16384
+
+
+def rasterize_mesh(verts, faces, poses, intrinsics, H: int, W: int, near: float,
+                   vertex_labels=None, vertex_rgb=None):
+    """A triangle mesh seen from B pinhole cameras (poses [B,4,4]
+    camera-to-world in the field's frame, intrinsics (fx, fy, cx, cy): the
+    conventions of get_rays) -> dict of device tensors ``tri_id`` [B,H,W] int32
+    (-1 = empty), ``depth`` [B,H,W] f32 z-depth (0 = empty), ``label`` [B,H,W]
+    int32 (``vertex_labels`` of the nearest corner of the hit point, 0 = empty
+    or no labels) and, with ``vertex_rgb`` [V,3], ``rgb`` [B,H,W,3] f32
+    (barycentric blend).  verts [V,3] f32, faces [F,3] int32 with indices in
+    [0,V).  Contract of ucsa_raster_setup / ucsa_raster_draw
+    (include/ucsa_hip.h): watertight, nearest face wins, ties to the lower face
+    id, deterministic.  Reads back the face index range (validation) and,
+    between the passes, the (tile, face) pair total."""
+    verts = _f32(verts, "verts")
+    poses = _f32(poses, "poses")
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise _lib.UcsaError("faces must be a GPU tensor: the HIP path has no CPU fallback")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise _lib.UcsaError(f"faces must be an integer tensor, got {faces.dtype}")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise _lib.UcsaError(f"verts must be [V,3], got {tuple(verts.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.UcsaError(f"faces must be [F,3], got {tuple(faces.shape)}")
+    if poses.dim() != 3 or poses.shape[1:] != (4, 4) or poses.shape[0] < 1:
+        raise _lib.UcsaError(f"poses must be [B,4,4], got {tuple(poses.shape)}")
+    V, F, B = int(verts.shape[0]), int(faces.shape[0]), int(poses.shape[0])
+    H, W = int(H), int(W)
+    if not (1 <= H <= RASTER_MAX_DIM and 1 <= W <= RASTER_MAX_DIM):
+        raise _lib.UcsaError(f"H, W must be in [1, {RASTER_MAX_DIM}], got {H}x{W}")
+    if B > 65535 or B * F > 0x7FFFFFFF:
+        raise _lib.UcsaError("rasterize_mesh: too many views x faces in one call; "
+                             "render fewer views at a time")
+    near = float(near)
+    if not (near > 0.0 and math.isfinite(near)):
+        raise _lib.UcsaError(f"near must be > 0, got {near}")
+    fx, fy, cx, cy = [float(v) for v in intrinsics]
+    if not (fx > 0 and fy > 0 and all(math.isfinite(v) for v in (fx, fy, cx, cy))):
+        raise _lib.UcsaError(f"intrinsics must have fx, fy > 0 and be finite, got "
+                             f"{(fx, fy, cx, cy)}")
+    lo_hi = torch.stack(torch.aminmax(faces)).tolist() if F else [0, 0]
+    if F and (lo_hi[0] < 0 or lo_hi[1] >= V):
+        raise _lib.UcsaError(f"faces index outside [0, {V})")
+    faces = _i32(faces.to(torch.int32).contiguous(), "faces")
+    labels = rgb_in = None
+    if vertex_labels is not None:
+        labels = _i32(vertex_labels.to(torch.int32).contiguous(), "vertex_labels")
+        if labels.shape != (V,):
+            raise _lib.UcsaError(f"vertex_labels must be [V], got {tuple(labels.shape)}")
+    if vertex_rgb is not None:
+        rgb_in = _f32(vertex_rgb, "vertex_rgb")
+        if rgb_in.shape != (V, 3):
+            raise _lib.UcsaError(f"vertex_rgb must be [V,3], got {tuple(rgb_in.shape)}")
+    dev = verts.device
+    args = (_ptr(verts), V, _ptr(faces), F, _ptr(poses), B, fx, fy, cx, cy, H, W, near)
+    ws = torch.empty(int(lib().ucsa_raster_workspace_bytes(B, F, H, W)), dtype=torch.uint8,
+                     device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(lib().ucsa_raster_setup(*args, _ptr(ws), _ptr(total), _stream()),
+          "ucsa_raster_setup")
+    n_pairs = int(total.item())
+    if n_pairs > 0x7FFFFFFF:
+        raise _lib.UcsaError("rasterize_mesh: more than 2^31-1 (tile, face) pairs; "
+                             "render fewer views at a time")
+    pairs = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)
+    out = {"tri_id": torch.empty(B, H, W, dtype=torch.int32, device=dev),
+           "depth": torch.empty(B, H, W, device=dev),
+           "label": torch.empty(B, H, W, dtype=torch.int32, device=dev)}
+    if rgb_in is not None:
+        out["rgb"] = torch.empty(B, H, W, 3, device=dev)
+    check(lib().ucsa_raster_draw(*args, _ptr(labels), _ptr(rgb_in), _ptr(ws), _ptr(pairs),
+                                 n_pairs, pairs.numel(), _ptr(out["tri_id"]),
+                                 _ptr(out["depth"]), _ptr(out["label"]), _ptr(out.get("rgb")),
+                                 B * H * W, _stream()), "ucsa_raster_draw")
+    return out
