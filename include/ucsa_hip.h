@@ -1312,6 +1312,59 @@ int32_t ucsa_raster_draw(const float* verts, uint32_t V, const int32_t* faces,
                          float* depth, int32_t* label, float* rgb,
                          uint64_t max_pixels, void* stream);
 
+/* ---- label fusion: 2D label maps voted onto mesh vertices (not in the
+ * reference) ---------------------------------------------------------------
+ * Per-frame label maps -> per-vertex labels by multi-view voting
+ * (utils/mesh_fusion.py, scripts/fuse_mesh_labels.py).  The projection is the
+ * rasterizer's: render the mesh with vertex_labels = 1..V and every pixel's
+ * `label` is the 1-based id of the vertex it votes for.
+ *   ucsa_label_fuse_accumulate: N pixels vote into votes [V][C+1] uint64,
+ *     row-major, allocated AND zeroed by the caller, accumulated over calls.
+ *     Column 0 of a row is never written (kept so that column = class id).
+ *     Pixel i votes iff ALL of
+ *       1 <= vertex_id[i] <= V          (int32; <= 0 = no vote; > V is the
+ *                                        caller's error and is skipped),
+ *       1 <= pred[i] <= C               (uint8 class id, what the PNGs hold),
+ *       weight == NULL or 0 <= weight[i] <= 65535   (int32),
+ *       mesh_depth == NULL, or sensor_depth[i] > 0 and
+ *         fabsf(mesh_depth[i] - sensor_depth[i]) <= depth_tol
+ *         (fp32 z in scene units, ONE fp32 subtraction; a NaN anywhere fails);
+ *     and then votes[vertex_id[i]-1][pred[i]] += weight ? weight[i] : 1.
+ *     mesh_depth and sensor_depth come as a pair (both or neither); with them
+ *     depth_tol must be >= 0 and not NaN, without them it is ignored.
+ *     Sums are uint64 and wrap modulo 2^64; integer adds commute, so the table
+ *     does not depend on the order or grouping of pixels or calls: two runs
+ *     give the same bytes.  row_width is a scheduling hint only (the arrays
+ *     are images of that width, stacked: B*H rows of W; 0 = no structure): a
+ *     wave takes a 16x16 pixel tile as four 8x8 patches, adds up its lanes
+ *     with an equal (vertex, class) before touching memory and issues one
+ *     64-bit integer atomic add per distinct pair; the result is the same for
+ *     every row_width.  flags: 0, or UCSA_FUSE_ONE_ATOMIC_PER_PIXEL (the
+ *     uncombined form with the same result, kept as the baseline of
+ *     tools/label_fusion_time.py).
+ *     Limits: 1 <= C <= 255, V*(C+1) <= 2^31-1, N <= 2^31-1,
+ *     votes_capacity (uint64 elements) >= V*(C+1), else an argument error and
+ *     nothing is written.  V == 0 or N == 0: returns 0, launches nothing.
+ *   ucsa_label_fuse_resolve: per vertex v from its row, with s_c = votes[v][c]:
+ *     total[v] = sum of s_c over c = 1..C (uint64, wrapping);
+ *     winner[v] = max of s_c; label[v] (int32) = the lowest c with
+ *     s_c == winner[v] if total[v] >= min_votes, else 0 (winner[v] is the
+ *     maximum either way).  min_votes >= 1.  label / total / winner hold
+ *     max_vertices >= V elements each; nothing is written past V.  No atomics.
+ *     Confidence = winner / total is the caller's, in float64. */
+#define UCSA_FUSE_ONE_ATOMIC_PER_PIXEL 1u
+int32_t ucsa_label_fuse_accumulate(const int32_t* vertex_id, const uint8_t* pred,
+                                   const int32_t* weight, const float* mesh_depth,
+                                   const float* sensor_depth, float depth_tol,
+                                   uint64_t N, uint32_t row_width, uint32_t V,
+                                   uint32_t C, uint64_t* votes,
+                                   uint64_t votes_capacity, uint32_t flags,
+                                   void* stream);
+int32_t ucsa_label_fuse_resolve(const uint64_t* votes, uint32_t V, uint32_t C,
+                                uint64_t min_votes, int32_t* label, uint64_t* total,
+                                uint64_t* winner, uint64_t max_vertices,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Fuse a scene's per-frame 2D label maps onto a mesh by multi-view voting (GPU:
+``ops.rasterize_mesh`` + ``ops.fuse_label_votes``, ``utils/mesh_fusion.py``) and
+write the mesh with the fused labels in the ``*.labels.ply`` layout.  The
+sibling of ``scripts/render_mesh_labels.py``, which goes the other way.
+
+    python scripts/fuse_mesh_labels.py --scene_root <root>/<scene> --mesh M.ply \\
+        [--pose_frame] --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] \\
+        [--depth_tol METRES] [--min_votes K] [--every N] --out FUSED.ply \\
+        [--render] [--score]
+
+``--labels``: ``label_40`` is ``<scene>/label_40``; ``seg_label`` / ``nerf_label``
+are ``<scene>/<exp_name>/...`` (the predict pass's output); anything else is a
+directory.  Each holds ``<stem>.png`` uint8 NYU40 ids (0 = no vote) for the
+frames of transforms_train.json; every ``--every``-th frame is used.  The mesh is
+read in the field's (NGP) frame, or with ``--pose_frame`` in the frame of the
+JSON poses in metres, and written back in the frame it was read in, with its
+colours and normals as they were (none are invented) and ``label`` replaced by
+the fused NYU40 id (0 = unobserved, or fewer than ``--min_votes`` votes).
+``--depth_tol``: a pixel votes only where the mesh's z-depth agrees with
+``depth/<stem>.png`` within that many metres; the PNG's uint16 millimetres
+become scene units as ``(float32(mm) / float32(1000)) * float32(one_m_to_scene_uom)``
+and the tolerance as ``float32(METRES * one_m_to_scene_uom)``.
+``--render`` re-renders the fused mesh into the same frames as
+``map_label/<stem>.png`` (uint8) under ``--out_dir`` (default: ``<scene>/<exp_name>``
+or the scene root).  ``--score`` (implies ``--render``) scores ``map_label`` and
+the input label maps against ``label_40``: one JSON line with the input mIoU
+next to the fused one."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ucsa_neural_rendering_amd.utils.mesh_fusion import fuse_views  # noqa: E402
+from ucsa_neural_rendering_amd.utils.mesh_render import (  # noqa: E402
+    load_mesh, read_frames, render_views, score_label_maps)
+from ucsa_neural_rendering_amd.utils.ply import read_ply, write_ply  # noqa: E402
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--scene_root", required=True, help="<root>/<scene>")
+    p.add_argument("--mesh", required=True, help="mesh to label (.ply)")
+    p.add_argument("--pose_frame", action="store_true",
+                   help="the mesh is in the JSON pose frame, in metres")
+    p.add_argument("--labels", required=True,
+                   help="seg_label | nerf_label | label_40 | a directory of <stem>.png")
+    p.add_argument("--exp_name", default=None)
+    p.add_argument("--depth_tol", type=float, default=None, help="metres")
+    p.add_argument("--min_votes", type=int, default=1)
+    p.add_argument("--every", type=int, default=1, help="use every N-th frame")
+    p.add_argument("--out", required=True, help="the labelled mesh to write (.ply)")
+    p.add_argument("--render", action="store_true")
+    p.add_argument("--score", action="store_true")
+    p.add_argument("--out_dir", default=None, help="where map_label/ goes")
+    p.add_argument("--near", type=float, default=0.05, help="near plane, scene units")
+    p.add_argument("--num_classes", type=int, default=40)
+    p.add_argument("--batch", type=int, default=16, help="views per rasterizer call")
+    return p.parse_args(argv)
+
+
+def label_dir(a):
+    if a.labels == "label_40":
+        return os.path.join(a.scene_root, "label_40")
+    if a.labels in ("seg_label", "nerf_label"):
+        if a.exp_name is None:
+            raise SystemExit(f"--labels {a.labels} reads <scene>/<exp_name>/{a.labels}: "
+                             "give --exp_name")
+        return os.path.join(a.scene_root, a.exp_name, a.labels)
+    return a.labels
+
+
+def main(argv=None):
+    from PIL import Image
+    a = parse_args(argv)
+    if a.every < 1 or a.min_votes < 1:
+        raise SystemExit("--every and --min_votes must be >= 1")
+    fr = read_frames(a.scene_root)
+    uom = fr["one_m_to_scene_uom"]
+    keep = list(range(0, len(fr["stems"]), a.every))
+    stems = [fr["stems"][i] for i in keep]
+    poses = fr["poses"][keep]
+    H, W = fr["H"], fr["W"]
+    raw = read_ply(a.mesh)
+    mesh = load_mesh(a.mesh, pose_frame=a.pose_frame, one_m_to_scene_uom=uom)
+    src = label_dir(a)
+
+    def png(folder, i):
+        return np.asarray(Image.open(os.path.join(folder, stems[i] + ".png")))
+
+    def depth(i):
+        mm = png(os.path.join(a.scene_root, "depth"), i)
+        return (mm.astype(np.float32) / np.float32(1000.0)) * np.float32(uom)
+
+    gated = a.depth_tol is not None
+    fused = fuse_views(mesh, poses, fr["intrinsics"], H, W, a.near, lambda i: png(src, i),
+                       depth_maps=depth if gated else None,
+                       depth_tol=float(np.float32(a.depth_tol * uom)) if gated else None,
+                       num_classes=a.num_classes, batch=a.batch, min_votes=a.min_votes)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    write_ply(a.out, raw["verts"], raw["faces"], normals=raw.get("normals"),
+              rgb=raw.get("rgb"), labels=fused["labels"])
+    n = len(stems)
+    rec = {"out": a.out, "labels": src, "frames": n, "vertices": int(mesh["verts"].shape[0]),
+           "faces": int(mesh["faces"].shape[0]), "observed": fused["observed"],
+           "fuse_ms_per_view": {"rasterize": round(fused["rasterize_ms"] / max(n, 1), 3),
+                                "accumulate": round(fused["accumulate_ms"] / max(n, 1), 3)}}
+    if a.render or a.score:
+        out_dir = a.out_dir or os.path.join(a.scene_root, a.exp_name or "")
+        os.makedirs(os.path.join(out_dir, "map_label"), exist_ok=True)
+        mesh["labels"], mesh["rgb"] = fused["labels"].astype(np.int32), None
+        maps = []
+        for start, out in render_views(mesh, poses, fr["intrinsics"], H, W, a.near, a.batch):
+            lab = out["label"].clamp(0, 255).cpu().numpy().astype(np.uint8)
+            for i in range(lab.shape[0]):
+                Image.fromarray(lab[i]).save(
+                    os.path.join(out_dir, "map_label", stems[start + i] + ".png"))
+            maps.append(lab)
+        rec["map_label"] = os.path.join(out_dir, "map_label")
+        if a.score:
+            truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
+            given = np.stack([png(src, i) for i in range(n)])
+            rec["input"] = score_label_maps(given, truth, a.num_classes)
+            rec["fused"] = score_label_maps(np.concatenate(maps), truth, a.num_classes)
+    print(json.dumps(rec))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

@@ -308,6 +308,11 @@ SIGNATURES = {
     "ucsa_raster_draw": (C.c_int32, [_p, _u32, _p, _u32, _p, _u32, _f, _f, _f, _f,
                                      _u32, _u32, _f, _p, _p, _p, _p, C.c_uint64,
                                      C.c_uint64, _p, _p, _p, _p, C.c_uint64, _p]),
+    # ---- label fusion (2D label maps voted onto mesh vertices) ----
+    "ucsa_label_fuse_accumulate": (C.c_int32, [_p, _p, _p, _p, _p, _f, C.c_uint64, _u32,
+                                               _u32, _u32, _p, C.c_uint64, _u32, _p]),
+    "ucsa_label_fuse_resolve": (C.c_int32, [_p, _u32, _u32, C.c_uint64, _p, _p, _p,
+                                            C.c_uint64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

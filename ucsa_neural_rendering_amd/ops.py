@@ -1649,3 +1649,94 @@ def rasterize_mesh(verts, faces, poses, intrinsics, H: int, W: int, near: float,
                                  _ptr(out["depth"]), _ptr(out["label"]), _ptr(out.get("rgb")),
                                  B * H * W, _stream()), "ucsa_raster_draw")
     return out
+
+
+# ---------------------------------------------------------------------------
+# label fusion (2D label maps voted onto mesh vertices)
+# ---------------------------------------------------------------------------
+def _fuse_input(t, name, dtype, n):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise _lib.UcsaError(f"{name} must be a GPU tensor: the HIP path has no CPU fallback")
+    if t.device.index != torch.cuda.current_device():
+        raise _lib.UcsaError(f"{name} is on {t.device} but the current device is cuda:"
+                             f"{torch.cuda.current_device()}: call torch.cuda.set_device first")
+    if t.dtype != dtype:
+        raise _lib.UcsaError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.numel() != n:
+        raise _lib.UcsaError(f"{name} has {t.numel()} elements, vertex_id has {n}")
+    return t.contiguous()
+
+
+def _vote_table(votes):
+    if not (torch.is_tensor(votes) and votes.is_cuda and votes.dtype == torch.int64
+            and votes.is_contiguous()):
+        raise _lib.UcsaError("votes must be a contiguous int64 tensor on the GPU (the bits of "
+                             "the uint64 table)")
+    if votes.dim() != 2 or not (2 <= votes.shape[1] <= 256):
+        raise _lib.UcsaError(f"votes must be [V, C+1] with 1 <= C <= 255, got "
+                             f"{tuple(votes.shape)}")
+    if votes.numel() > 0x7FFFFFFF:
+        raise _lib.UcsaError("votes: V*(C+1) must be at most 2^31-1")
+    return int(votes.shape[0]), int(votes.shape[1]) - 1
+
+
+def fuse_label_votes(votes, vertex_id, pred, weight=None, mesh_depth=None, sensor_depth=None,
+                     depth_tol=None, _one_atomic_per_pixel=False):
+    """Pixels vote for (vertex, class) cells of ``votes`` [V, C+1] int64 (the
+    bits of a uint64 table, zeroed by the caller; column 0 unused), in place;
+    returns ``votes``.  ``vertex_id`` int32, any shape (the ``label`` of
+    ``rasterize_mesh(..., vertex_labels=arange(1, V+1))``: 1-based, <= 0 = no
+    vote), ``pred`` uint8 class ids (1..C vote), ``weight`` int32 in [0, 65535]
+    or None (1 per vote), ``mesh_depth`` / ``sensor_depth`` fp32 z in scene
+    units with ``depth_tol``: a pixel then votes only where sensor_depth > 0
+    and |mesh_depth - sensor_depth| <= depth_tol.  All of vertex_id's size.
+    Contract of ucsa_label_fuse_accumulate (include/ucsa_hip.h): integer sums,
+    the same bytes whatever the order of pixels and calls."""
+    V, Cn = _vote_table(votes)
+    if not torch.is_tensor(vertex_id):
+        raise _lib.UcsaError("vertex_id must be a GPU tensor")
+    n = vertex_id.numel()
+    vid = _fuse_input(vertex_id, "vertex_id", torch.int32, n)
+    pr = _fuse_input(pred, "pred", torch.uint8, n)
+    if n > 0x7FFFFFFF:
+        raise _lib.UcsaError("fuse_label_votes: at most 2^31-1 pixels per call")
+    w = None if weight is None else _fuse_input(weight, "weight", torch.int32, n)
+    if (mesh_depth is None) != (sensor_depth is None):
+        raise _lib.UcsaError("mesh_depth and sensor_depth come as a pair")
+    md = sd = None
+    tol = 0.0
+    if mesh_depth is not None:
+        if depth_tol is None:
+            raise _lib.UcsaError("the depth gate needs depth_tol")
+        tol = float(depth_tol)
+        if not tol >= 0.0:
+            raise _lib.UcsaError(f"depth_tol must be >= 0, got {depth_tol}")
+        md = _fuse_input(mesh_depth, "mesh_depth", torch.float32, n)
+        sd = _fuse_input(sensor_depth, "sensor_depth", torch.float32, n)
+    elif depth_tol is not None:
+        raise _lib.UcsaError("depth_tol given without mesh_depth / sensor_depth")
+    row_width = int(vertex_id.shape[-1]) if vertex_id.dim() >= 2 else 0
+    check(lib().ucsa_label_fuse_accumulate(
+        _ptr(vid), _ptr(pr), _ptr(w), _ptr(md), _ptr(sd), tol, n, row_width, V, Cn,
+        _ptr(votes), votes.numel(), 1 if _one_atomic_per_pixel else 0, _stream()),
+        "ucsa_label_fuse_accumulate")
+    return votes
+
+
+def resolve_label_votes(votes, min_votes: int = 1):
+    """``votes`` [V, C+1] -> dict of device tensors: ``label`` [V] int32 (the
+    class with the largest sum, ties to the lower id, 0 where the row's total
+    is below ``min_votes``), ``total`` and ``winner`` [V] int64 (the bits of
+    uint64 sums; confidence = winner / total).  ucsa_label_fuse_resolve."""
+    V, Cn = _vote_table(votes)
+    min_votes = int(min_votes)
+    if not 1 <= min_votes < 1 << 64:
+        raise _lib.UcsaError(f"min_votes must be >= 1, got {min_votes}")
+    dev = votes.device
+    out = {"label": torch.empty(V, dtype=torch.int32, device=dev),
+           "total": torch.empty(V, dtype=torch.int64, device=dev),
+           "winner": torch.empty(V, dtype=torch.int64, device=dev)}
+    check(lib().ucsa_label_fuse_resolve(_ptr(votes), V, Cn, min_votes, _ptr(out["label"]),
+                                        _ptr(out["total"]), _ptr(out["winner"]), V,
+                                        _stream()), "ucsa_label_fuse_resolve")
+    return out
