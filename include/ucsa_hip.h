@@ -1234,6 +1234,30 @@ int32_t ucsa_mc_emit(const float* field, uint32_t nx, uint32_t ny, uint32_t nz,
                      int32_t* tris, uint32_t max_verts, uint32_t max_faces,
                      void* stream);
 
+/* The same two passes over the observed part of a lattice: `valid` [nx,ny,nz]
+ * uint8 (0 = invalid, anything else = valid; a TSDF volume's weight > 0).  An
+ * edge carries a vertex iff it crosses the iso value AND both its end points
+ * are valid; a cell emits its triangles iff ALL EIGHT corners are valid (every
+ * edge of such a cell has two valid ends, so every index it emits exists).
+ * Order, winding, interpolation as above.  Normal: per axis, the difference at
+ * an end point runs from its lower to its upper neighbour as above, except that
+ * a neighbour that is invalid (or off the lattice) is replaced by the point
+ * itself -- the one-sided difference, divided by 1*spacing -- and with neither
+ * neighbour usable the component is +0; then lerp and normalise as above.
+ * Field values at invalid points are never used for positions or normals; they
+ * are still compared with iso, which changes nothing that is emitted.  With
+ * every point valid the output is byte for byte that of ucsa_mc_count /
+ * ucsa_mc_emit.  Same workspace, totals, capacities and limits; dims are
+ * arguments 2..4 here.  tests/tsdf_numpy.py restates it. */
+int32_t ucsa_mc_count_masked(const float* field, const uint8_t* valid, uint32_t nx,
+                             uint32_t ny, uint32_t nz, float iso, void* workspace,
+                             uint32_t* totals_dev, void* stream);
+int32_t ucsa_mc_emit_masked(const float* field, const uint8_t* valid, uint32_t nx,
+                            uint32_t ny, uint32_t nz, float iso, const float* origin3,
+                            const float* spacing3, const void* workspace, float* verts,
+                            float* normals, int32_t* tris, uint32_t max_verts,
+                            uint32_t max_faces, void* stream);
+
 /* ---- mesh rasterization (not in the reference) ----------------------------
  * A triangle mesh seen from B posed pinhole cameras -> per pixel the visible
  * face, its z-depth, NYU40 label and colour (mesh-rendered labels / depth at
@@ -1364,6 +1388,56 @@ int32_t ucsa_label_fuse_resolve(const uint64_t* votes, uint32_t V, uint32_t C,
                                 uint64_t min_votes, int32_t* label, uint64_t* total,
                                 uint64_t* winner, uint64_t max_vertices,
                                 void* stream);
+
+/* ---- TSDF fusion: posed depth frames into a dense volume (not in the
+ * reference) ---------------------------------------------------------------
+ * Projective integration of B depth views into a truncated signed distance
+ * volume in the poses' (NGP) frame, scene units (utils/tsdf_fusion.py,
+ * scripts/fuse_tsdf_mesh.py); -tsdf at iso 0 with valid = weight > 0 goes to
+ * ucsa_mc_count_masked / ucsa_mc_emit_masked.  Lattice as for marching cubes:
+ * point (i,j,k) at origin + (i,j,k)*spacing, stored at [(i*ny + j)*nz + k].
+ * State, allocated and initialised by the caller, updated in place over calls:
+ *   tsdf [nx,ny,nz] fp32 in [-1, 1], units of trunc, initial 1;
+ *   weight [nx,ny,nz] fp32, initial 0;
+ *   rgb [nx,ny,nz,3] fp32 running average of the colour frames, initial 0, or
+ *     NULL; rgb and color come as a pair (both or neither).
+ * Inputs: depth [B,H,W] fp32 z-depth in scene units, color [B,H,W,3] uint8,
+ * poses [B,4,4] camera-to-world (the poses of ucsa_get_rays), all on the
+ * device; origin3 / spacing3 HOST float[3]; fx, fy, cx, cy, trunc, max_weight,
+ * depth_min, depth_max HOST scalars.
+ * Contract per voxel, for b = 0..B-1 in ascending order (fp32, every operation
+ * as written, no contraction, correctly rounded division; a numpy restatement
+ * gives the same bits: tests/tsdf_numpy.py).  R = P_b[0:3,0:3], t = P_b[0:3,3]:
+ *   p_a = origin_a + (float)index_a * spacing_a;
+ *   d = p - t, c_r = (d0*R0r + d1*R1r) + d2*R2r  (the rasterizer's camera point);
+ *   skip the view unless c_z > 0 (NaN skips);
+ *   u = floor((fx*c_x)/c_z + cx), v = floor((fy*c_y)/c_z + cy): pixel centres at
+ *     +0.5 as in ucsa_get_rays / the rasterizer, nearest pixel; skip unless
+ *     0 <= u < W and 0 <= v < H (compared in fp32; NaN skips);
+ *   z = depth[b][v][u]; skip unless z is finite and depth_min <= z <= depth_max
+ *     (with depth_min > 0, 0 means "no measurement" as in the depth PNGs);
+ *   sdf = z - c_z; skip if sdf < -trunc; x = min(1, sdf / trunc);
+ *   w1 = weight + 1; tsdf = (tsdf*weight + x) / w1;
+ *   rgb_c = (rgb_c*weight + (float)color[b][v][u][c]) / w1  for c = 0, 1, 2;
+ *   weight = min(w1, max_weight).
+ * One thread owns a voxel: no atomics, two runs give the same bytes, and since
+ * a voxel's views are applied in order, one call with B views, B calls with one
+ * view and every split in between give the same bytes.  The state is read
+ * once, carried in registers through up to 32 views per launch and written
+ * once (a voxel no view touched is not written); a work-group may skip a view
+ * for its whole 1x4x64 brick when the brick's corners prove that every voxel
+ * of it would skip that view (an optimisation that changes no bit).
+ * Limits: dims >= 2 each, nx*ny*nz <= 2^31-1, nx <= 65535, ny <= 262140 (else
+ * the dim's argument), B >= 1, 1 <= H, W <= 16384, fx, fy > 0, trunc > 0,
+ * max_weight >= 1, depth_min not NaN, depth_max >= depth_min; an argument error
+ * comes before any launch and nothing outside the three volumes is written. */
+int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx,
+                            uint32_t ny, uint32_t nz, const float* origin3,
+                            const float* spacing3, const float* depth,
+                            const uint8_t* color, const float* poses, uint32_t B,
+                            float fx, float fy, float cx, float cy, uint32_t H,
+                            uint32_t W, float trunc, float max_weight, float depth_min,
+                            float depth_max, void* stream);
 
 #ifdef __cplusplus
 }

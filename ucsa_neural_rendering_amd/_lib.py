@@ -301,6 +301,9 @@ SIGNATURES = {
     "ucsa_mc_count": (C.c_int32, [_p, _u32, _u32, _u32, _f, _p, _p, _p]),
     "ucsa_mc_emit": (C.c_int32, [_p, _u32, _u32, _u32, _f, C.POINTER(_f),
                                  C.POINTER(_f), _p, _p, _p, _p, _u32, _u32, _p]),
+    "ucsa_mc_count_masked": (C.c_int32, [_p, _p, _u32, _u32, _u32, _f, _p, _p, _p]),
+    "ucsa_mc_emit_masked": (C.c_int32, [_p, _p, _u32, _u32, _u32, _f, C.POINTER(_f),
+                                        C.POINTER(_f), _p, _p, _p, _p, _u32, _u32, _p]),
     # ---- mesh rasterization ----
     "ucsa_raster_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32, _u32]),
     "ucsa_raster_setup": (C.c_int32, [_p, _u32, _p, _u32, _p, _u32, _f, _f, _f, _f,
@@ -313,6 +316,10 @@ SIGNATURES = {
                                                _u32, _u32, _p, C.c_uint64, _u32, _p]),
     "ucsa_label_fuse_resolve": (C.c_int32, [_p, _u32, _u32, C.c_uint64, _p, _p, _p,
                                             C.c_uint64, _p]),
+    # ---- TSDF fusion (posed depth frames into a dense volume) ----
+    "ucsa_tsdf_integrate": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                        C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f,
+                                        _u32, _u32, _f, _f, _f, _f, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

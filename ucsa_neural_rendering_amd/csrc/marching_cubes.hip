@@ -18,6 +18,12 @@
 //   k_mc_offsets   per point its first vertex / triangle slot;
 //   k_mc_emit      vertices (position, normal) and triangles.
 // Workspace: 10 bytes per point plus 12 per tile (1.34 GB at 512^3).
+//
+// ucsa_mc_count_masked / ucsa_mc_emit_masked run the same kernels with a
+// validity mask (uint8 per point; a TSDF volume's "observed"): an edge carries a
+// vertex only between two valid points, a cell emits only with eight valid
+// corners, and the normal's differences stop at an invalid neighbour.  The
+// unmasked entries pass no mask and take the same path as before.
 #include "ucsa_common.h"
 #include "wave_ops.h"
 
@@ -317,7 +323,8 @@ __device__ __forceinline__ bool mc_out(const float* f, uint32_t q, float iso) {
 
 // class of point p: cell case (0 where p is no cell's lower corner) | crossing
 // edges << 8
-__device__ uint32_t mc_class(const float* __restrict__ f, McDims d, float iso,
+__device__ uint32_t mc_class(const float* __restrict__ f,
+                             const uint8_t* __restrict__ valid, McDims d, float iso,
                              uint32_t p) {
   const uint32_t sy = d.nz, sx = d.ny * d.nz;
   const uint32_t k = p % d.nz, r = p / d.nz, j = r % d.ny, i = r / d.ny;
@@ -335,6 +342,15 @@ __device__ uint32_t mc_class(const float* __restrict__ f, McDims d, float iso,
         (uint32_t)mc_out(f, p + sx + 1, iso) << 5 |
         (uint32_t)mc_out(f, p + sx + sy + 1, iso) << 6 |
         (uint32_t)mc_out(f, p + sy + 1, iso) << 7;
+  }
+  if (valid) {
+    // an edge needs both end points, a cell all eight corners
+    const bool v0 = valid[p] != 0;
+    const bool vx = hx && valid[p + sx], vy = hy && valid[p + sy], vz = hz && valid[p + 1];
+    e &= v0 ? ((uint32_t)vx | (uint32_t)vy << 1 | (uint32_t)vz << 2) : 0u;
+    if (c && !(v0 && vx && vy && vz && valid[p + sx + sy] && valid[p + sx + 1] &&
+               valid[p + sx + sy + 1] && valid[p + sy + 1]))
+      c = 0;
   }
   return c | e << 8;
 }
@@ -363,8 +379,8 @@ __device__ __forceinline__ uint32_t mc_block_excl(uint32_t v, uint32_t* lds,
 }
 
 __global__ __launch_bounds__(MC_THREADS) void k_mc_classify(
-    const float* __restrict__ f, McDims d, float iso, uint16_t* __restrict__ cls,
-    uint32_t* __restrict__ tile_counts) {
+    const float* __restrict__ f, const uint8_t* __restrict__ valid, McDims d, float iso,
+    uint16_t* __restrict__ cls, uint32_t* __restrict__ tile_counts) {
   __shared__ uint32_t lds[MC_THREADS / 64];
   const uint32_t p0 = blockIdx.x * MC_TILE + threadIdx.x * MC_ITEMS;
   uint32_t sum = 0;
@@ -372,7 +388,7 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_classify(
   for (uint32_t q = 0; q < MC_ITEMS; ++q) {
     const uint32_t p = p0 + q;
     if (p < d.n) {
-      const uint32_t c = mc_class(f, d, iso, p);
+      const uint32_t c = mc_class(f, valid, d, iso, p);
       cls[p] = (uint16_t)c;
       sum += mc_counts(c);
     }
@@ -459,12 +475,19 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_offsets(
 }
 
 // -grad f at lattice point q (index idx along `axis`, stride s, n points):
-// central difference inside, one-sided on the boundary
-__device__ __forceinline__ float mc_neg_grad(const float* __restrict__ f, uint32_t q,
+// central difference inside, one-sided on the boundary and next to an invalid
+// neighbour; +0 when neither neighbour can be used
+__device__ __forceinline__ float mc_neg_grad(const float* __restrict__ f,
+                                             const uint8_t* __restrict__ valid, uint32_t q,
                                              uint32_t idx, uint32_t n, uint32_t s,
                                              float h) {
-  const uint32_t hi = idx + 1 < n ? idx + 1 : idx;
-  const uint32_t lo = idx > 0 ? idx - 1 : idx;
+  uint32_t hi = idx + 1 < n ? idx + 1 : idx;
+  uint32_t lo = idx > 0 ? idx - 1 : idx;
+  if (valid) {
+    if (!valid[q + (hi - idx) * s]) hi = idx;
+    if (!valid[q - (idx - lo) * s]) lo = idx;
+    if (hi == lo) return 0.0f;
+  }
   const float df = f[q + (hi - idx) * s] - f[q - (idx - lo) * s];
   const float den = (float)(hi - lo) * h;
   return -(df / den);
@@ -475,8 +498,8 @@ struct McFrame {
 };
 
 __global__ __launch_bounds__(MC_THREADS) void k_mc_emit(
-    const float* __restrict__ f, McDims d, float iso, McFrame fr,
-    const uint16_t* __restrict__ cls, const uint32_t* __restrict__ voff,
+    const float* __restrict__ f, const uint8_t* __restrict__ valid, McDims d, float iso,
+    McFrame fr, const uint16_t* __restrict__ cls, const uint32_t* __restrict__ voff,
     const uint32_t* __restrict__ foff, float* __restrict__ verts,
     float* __restrict__ normals, int32_t* __restrict__ tris, uint32_t max_verts,
     uint32_t max_faces) {
@@ -500,8 +523,8 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_emit(
       x[a] = x[a] + t * fr.h[a];
       for (uint32_t b = 0; b < 3; ++b) {
         const uint32_t i1 = ijk[b] + (b == a ? 1u : 0u);
-        g0[b] = mc_neg_grad(f, p, ijk[b], dim[b], st[b], fr.h[b]);
-        g1[b] = mc_neg_grad(f, p1, i1, dim[b], st[b], fr.h[b]);
+        g0[b] = mc_neg_grad(f, valid, p, ijk[b], dim[b], st[b], fr.h[b]);
+        g1[b] = mc_neg_grad(f, valid, p1, i1, dim[b], st[b], fr.h[b]);
       }
       float n[3];
       for (uint32_t b = 0; b < 3; ++b) n[b] = g0[b] + t * (g1[b] - g0[b]);
@@ -555,23 +578,24 @@ extern "C" uint64_t ucsa_mc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t n
   return mc_layout((uint64_t)nx * ny * nz).total;
 }
 
-extern "C" int32_t ucsa_mc_count(const float* field, uint32_t nx, uint32_t ny,
-                                 uint32_t nz, float iso, void* workspace,
-                                 uint32_t* totals_dev, void* stream) {
+// k0: the argument index of nx (0-based) in the calling entry
+static int32_t mc_count(const float* field, const uint8_t* valid, int k0, uint32_t nx,
+                        uint32_t ny, uint32_t nz, float iso, void* workspace,
+                        uint32_t* totals_dev, void* stream) {
   UCSA_CHECK_ARG(field, 0);
-  UCSA_CHECK_ARG(nx >= 2 && mc_dims_ok(nx, ny, nz), 1);
-  UCSA_CHECK_ARG(ny >= 2, 2);
-  UCSA_CHECK_ARG(nz >= 2, 3);
-  UCSA_CHECK_ARG(workspace, 5);
-  UCSA_CHECK_ARG(totals_dev, 6);
+  UCSA_CHECK_ARG(nx >= 2 && mc_dims_ok(nx, ny, nz), k0);
+  UCSA_CHECK_ARG(ny >= 2, k0 + 1);
+  UCSA_CHECK_ARG(nz >= 2, k0 + 2);
+  UCSA_CHECK_ARG(workspace, k0 + 4);
+  UCSA_CHECK_ARG(totals_dev, k0 + 5);
   const McDims d{nx, ny, nz, nx * ny * nz};
   const McLayout l = mc_layout(d.n);
   char* ws = (char*)workspace;
   const uint32_t n_tiles = ucsa_div_up(d.n, MC_TILE);
   hipStream_t s = (hipStream_t)stream;
   UCSA_CLEAR_ERR();
-  hipLaunchKernelGGL(k_mc_classify, dim3(n_tiles), dim3(MC_THREADS), 0, s, field, d,
-                     iso, (uint16_t*)(ws + l.cls), (uint32_t*)(ws + l.tiles));
+  hipLaunchKernelGGL(k_mc_classify, dim3(n_tiles), dim3(MC_THREADS), 0, s, field,
+                     valid, d, iso, (uint16_t*)(ws + l.cls), (uint32_t*)(ws + l.tiles));
   hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, s,
                      (const uint32_t*)(ws + l.tiles), n_tiles,
                      (uint32_t*)(ws + l.tile_v), (uint32_t*)(ws + l.tile_f), totals_dev);
@@ -582,21 +606,21 @@ extern "C" int32_t ucsa_mc_count(const float* field, uint32_t nx, uint32_t ny,
   return ucsa_launch_status();
 }
 
-extern "C" int32_t ucsa_mc_emit(const float* field, uint32_t nx, uint32_t ny,
-                                uint32_t nz, float iso, const float* origin3,
-                                const float* spacing3, const void* workspace,
-                                float* verts, float* normals, int32_t* tris,
-                                uint32_t max_verts, uint32_t max_faces, void* stream) {
+static int32_t mc_emit(const float* field, const uint8_t* valid, int k0, uint32_t nx,
+                       uint32_t ny, uint32_t nz, float iso, const float* origin3,
+                       const float* spacing3, const void* workspace, float* verts,
+                       float* normals, int32_t* tris, uint32_t max_verts,
+                       uint32_t max_faces, void* stream) {
   UCSA_CHECK_ARG(field, 0);
-  UCSA_CHECK_ARG(nx >= 2 && mc_dims_ok(nx, ny, nz), 1);
-  UCSA_CHECK_ARG(ny >= 2, 2);
-  UCSA_CHECK_ARG(nz >= 2, 3);
-  UCSA_CHECK_ARG(origin3, 5);
-  UCSA_CHECK_ARG(spacing3, 6);
-  UCSA_CHECK_ARG(workspace, 7);
-  UCSA_CHECK_ARG(verts || max_verts == 0, 8);
-  UCSA_CHECK_ARG(normals || max_verts == 0, 9);
-  UCSA_CHECK_ARG(tris || max_faces == 0, 10);
+  UCSA_CHECK_ARG(nx >= 2 && mc_dims_ok(nx, ny, nz), k0);
+  UCSA_CHECK_ARG(ny >= 2, k0 + 1);
+  UCSA_CHECK_ARG(nz >= 2, k0 + 2);
+  UCSA_CHECK_ARG(origin3, k0 + 4);
+  UCSA_CHECK_ARG(spacing3, k0 + 5);
+  UCSA_CHECK_ARG(workspace, k0 + 6);
+  UCSA_CHECK_ARG(verts || max_verts == 0, k0 + 7);
+  UCSA_CHECK_ARG(normals || max_verts == 0, k0 + 8);
+  UCSA_CHECK_ARG(tris || max_faces == 0, k0 + 9);
   if (max_verts == 0 && max_faces == 0) return 0;
   const McDims d{nx, ny, nz, nx * ny * nz};
   const McLayout l = mc_layout(d.n);
@@ -608,8 +632,42 @@ extern "C" int32_t ucsa_mc_emit(const float* field, uint32_t nx, uint32_t ny,
   }
   UCSA_CLEAR_ERR();
   hipLaunchKernelGGL(k_mc_emit, dim3(ucsa_div_up(d.n, MC_THREADS)), dim3(MC_THREADS), 0,
-                     (hipStream_t)stream, field, d, iso, fr, (const uint16_t*)(ws + l.cls),
+                     (hipStream_t)stream, field, valid, d, iso, fr, (const uint16_t*)(ws + l.cls),
                      (const uint32_t*)(ws + l.voff), (const uint32_t*)(ws + l.foff), verts,
                      normals, tris, max_verts, max_faces);
   return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_mc_count(const float* field, uint32_t nx, uint32_t ny,
+                                 uint32_t nz, float iso, void* workspace,
+                                 uint32_t* totals_dev, void* stream) {
+  return mc_count(field, nullptr, 1, nx, ny, nz, iso, workspace, totals_dev, stream);
+}
+
+extern "C" int32_t ucsa_mc_emit(const float* field, uint32_t nx, uint32_t ny,
+                                uint32_t nz, float iso, const float* origin3,
+                                const float* spacing3, const void* workspace,
+                                float* verts, float* normals, int32_t* tris,
+                                uint32_t max_verts, uint32_t max_faces, void* stream) {
+  return mc_emit(field, nullptr, 1, nx, ny, nz, iso, origin3, spacing3, workspace, verts,
+                 normals, tris, max_verts, max_faces, stream);
+}
+
+extern "C" int32_t ucsa_mc_count_masked(const float* field, const uint8_t* valid,
+                                        uint32_t nx, uint32_t ny, uint32_t nz, float iso,
+                                        void* workspace, uint32_t* totals_dev,
+                                        void* stream) {
+  UCSA_CHECK_ARG(valid, 1);
+  return mc_count(field, valid, 2, nx, ny, nz, iso, workspace, totals_dev, stream);
+}
+
+extern "C" int32_t ucsa_mc_emit_masked(const float* field, const uint8_t* valid,
+                                       uint32_t nx, uint32_t ny, uint32_t nz, float iso,
+                                       const float* origin3, const float* spacing3,
+                                       const void* workspace, float* verts, float* normals,
+                                       int32_t* tris, uint32_t max_verts,
+                                       uint32_t max_faces, void* stream) {
+  UCSA_CHECK_ARG(valid, 1);
+  return mc_emit(field, valid, 2, nx, ny, nz, iso, origin3, spacing3, workspace, verts,
+                 normals, tris, max_verts, max_faces, stream);
 }

@@ -1539,22 +1539,40 @@ def augment(img, label, params, out_size=None):
 # marching cubes (labelled-mesh export)
 # ---------------------------------------------------------------------------
 def marching_cubes(field, iso: float, origin=(0.0, 0.0, 0.0),
-                   spacing=(1.0, 1.0, 1.0)):
+                   spacing=(1.0, 1.0, 1.0), valid=None):
     """Indexed iso-surface of a lattice field [nx,ny,nz] (point (i,j,k) at
     origin + (i,j,k)*spacing; inside iff field > iso) ->
     (verts [V,3] f32, faces [F,3] int32, normals [V,3] f32), conventions of
-    ucsa_mc_count / ucsa_mc_emit (include/ucsa_hip.h).  Reads the two totals
-    back once, between the passes.  Workspace: 10 bytes per lattice point."""
+    ucsa_mc_count / ucsa_mc_emit (include/ucsa_hip.h).  ``valid`` [nx,ny,nz]
+    bool or uint8 (a TSDF volume's observed voxels): vertices only on edges
+    between two valid points, triangles only from cells with eight valid
+    corners (ucsa_mc_count_masked / ucsa_mc_emit_masked); None = every point.
+    Reads the two totals back once, between the passes.  Workspace: 10 bytes
+    per lattice point."""
     field = _f32(field, "field")
     if field.dim() != 3:
         raise _lib.UcsaError(f"field must be [nx,ny,nz], got {tuple(field.shape)}")
     nx, ny, nz = (int(s) for s in field.shape)
     dev = field.device
+    head = (_ptr(field),)
+    count, emit, what = lib().ucsa_mc_count, lib().ucsa_mc_emit, "ucsa_mc"
+    if valid is not None:
+        if not (torch.is_tensor(valid) and valid.is_cuda):
+            raise _lib.UcsaError("valid must be a GPU tensor: the HIP path has no CPU fallback")
+        if valid.dtype not in (torch.bool, torch.uint8):
+            raise _lib.UcsaError(f"valid must be bool or uint8, got {valid.dtype}")
+        if valid.shape != field.shape or valid.device != dev:
+            raise _lib.UcsaError(f"valid must be {tuple(field.shape)} on {dev}, got "
+                                 f"{tuple(valid.shape)} on {valid.device}")
+        valid = valid.contiguous().view(torch.uint8)
+        head = (_ptr(field), _ptr(valid))
+        count, emit, what = lib().ucsa_mc_count_masked, lib().ucsa_mc_emit_masked, \
+            "ucsa_mc_masked"
     ws = torch.empty(int(lib().ucsa_mc_workspace_bytes(nx, ny, nz)), dtype=torch.uint8,
                      device=dev)
     totals = torch.zeros(2, dtype=torch.int32, device=dev)
-    check(lib().ucsa_mc_count(_ptr(field), nx, ny, nz, float(iso), _ptr(ws),
-                              _ptr(totals), _stream()), "ucsa_mc_count")
+    check(count(*head, nx, ny, nz, float(iso), _ptr(ws), _ptr(totals), _stream()),
+          what + " count")
     V, F = (int(v) & 0xFFFFFFFF for v in totals.tolist())
     if V > 0x7FFFFFFF or F > 0x7FFFFFFF:
         raise _lib.UcsaError("marching_cubes: more than 2^31-1 vertices or triangles; "
@@ -1563,9 +1581,8 @@ def marching_cubes(field, iso: float, origin=(0.0, 0.0, 0.0),
     normals = torch.empty(V, 3, device=dev)
     faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
     if V or F:
-        check(lib().ucsa_mc_emit(_ptr(field), nx, ny, nz, float(iso), fvec(origin),
-                                 fvec(spacing), _ptr(ws), _ptr(verts), _ptr(normals),
-                                 _ptr(faces), V, F, _stream()), "ucsa_mc_emit")
+        check(emit(*head, nx, ny, nz, float(iso), fvec(origin), fvec(spacing), _ptr(ws),
+                   _ptr(verts), _ptr(normals), _ptr(faces), V, F, _stream()), what + " emit")
     return verts, faces, normals
 
 
@@ -1740,3 +1757,83 @@ def resolve_label_votes(votes, min_votes: int = 1):
                                         _ptr(out["total"]), _ptr(out["winner"]), V,
                                         _stream()), "ucsa_label_fuse_resolve")
     return out
+
+
+# ---------------------------------------------------------------------------
+# TSDF fusion (posed depth frames into a dense volume)
+# ---------------------------------------------------------------------------
+def tsdf_volume(dims, origin, spacing, with_color: bool = False, device="cuda"):
+    """An empty TSDF volume for ``integrate_tsdf``: dict with ``tsdf`` [nx,ny,nz]
+    f32 (ones: free), ``weight`` [nx,ny,nz] f32 (zeros: unobserved), ``rgb``
+    [nx,ny,nz,3] f32 (zeros) or None, and the lattice ``origin`` / ``spacing``
+    (3 floats each; point (i,j,k) at origin + (i,j,k)*spacing, poses' frame,
+    scene units)."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"tsdf_volume: dims must be >= 2 each with at most 2^31-1 "
+                             f"voxels, got {(nx, ny, nz)}")
+    spacing = [float(spacing)] * 3 if isinstance(spacing, (int, float)) else \
+        [float(v) for v in spacing]
+    origin = [float(v) for v in origin]
+    if len(origin) != 3 or len(spacing) != 3:
+        raise _lib.UcsaError("tsdf_volume: origin and spacing have 3 entries each")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.UcsaError("tsdf_volume: the volume lives on the GPU (no CPU fallback)")
+    return {"tsdf": torch.ones(nx, ny, nz, device=dev),
+            "weight": torch.zeros(nx, ny, nz, device=dev),
+            "rgb": torch.zeros(nx, ny, nz, 3, device=dev) if with_color else None,
+            "origin": tuple(origin), "spacing": tuple(spacing)}
+
+
+def integrate_tsdf(volume, depth, poses, intrinsics, trunc: float, color=None,
+                   max_weight: float = 65504.0, depth_min: float = 1e-6,
+                   depth_max: float = 3.0e38):
+    """Integrate B posed depth views into ``volume`` (``tsdf_volume``), in place;
+    returns ``volume``.  ``depth`` [B,H,W] f32 z-depth in scene units (0, NaN,
+    inf, anything outside [depth_min, depth_max] = no measurement), ``poses``
+    [B,4,4] camera-to-world in the volume's frame, ``intrinsics`` (fx, fy, cx,
+    cy) as for get_rays, ``trunc`` the truncation distance in scene units,
+    ``color`` [B,H,W,3] uint8 iff the volume has ``rgb``.  Contract of
+    ucsa_tsdf_integrate (include/ucsa_hip.h): a voxel's views are applied in
+    order, so any split of the views over calls gives the same bytes."""
+    for k in ("tsdf", "weight"):
+        _inplace_f32(volume[k], f"volume['{k}']")
+    tsdf, weight, rgb = volume["tsdf"], volume["weight"], volume.get("rgb")
+    if tsdf.dim() != 3 or weight.shape != tsdf.shape or weight.device != tsdf.device:
+        raise _lib.UcsaError("volume: tsdf and weight must be [nx,ny,nz] on one device")
+    dev = tsdf.device
+    if dev.index != torch.cuda.current_device():
+        raise _lib.UcsaError(f"the volume is on {dev} but the current device is cuda:"
+                             f"{torch.cuda.current_device()}: call torch.cuda.set_device first")
+    nx, ny, nz = (int(s) for s in tsdf.shape)
+    if rgb is not None:
+        _inplace_f32(rgb, "volume['rgb']")
+        if rgb.shape != (nx, ny, nz, 3) or rgb.device != dev:
+            raise _lib.UcsaError("volume: rgb must be [nx,ny,nz,3] on the volume's device")
+    depth = _f32(depth, "depth")
+    poses = _f32(poses, "poses")
+    if depth.dim() != 3:
+        raise _lib.UcsaError(f"depth must be [B,H,W], got {tuple(depth.shape)}")
+    B, H, W = (int(s) for s in depth.shape)
+    if poses.dim() != 3 or tuple(poses.shape) != (B, 4, 4):
+        raise _lib.UcsaError(f"poses must be [{B},4,4], got {tuple(poses.shape)}")
+    if depth.device != dev or poses.device != dev:
+        raise _lib.UcsaError("depth and poses must be on the volume's device")
+    if (color is None) != (rgb is None):
+        raise _lib.UcsaError("color frames and a colour volume come as a pair")
+    if color is not None:
+        if not (torch.is_tensor(color) and color.is_cuda and color.device == dev):
+            raise _lib.UcsaError("color must be a GPU tensor on the volume's device: the HIP "
+                                 "path has no CPU fallback")
+        if color.dtype != torch.uint8 or tuple(color.shape) != (B, H, W, 3):
+            raise _lib.UcsaError(f"color must be uint8 [{B},{H},{W},3], got {color.dtype} "
+                                 f"{tuple(color.shape)}")
+        color = color.contiguous()
+    fx, fy, cx, cy = [float(v) for v in intrinsics]
+    check(lib().ucsa_tsdf_integrate(
+        _ptr(tsdf), _ptr(weight), _ptr(rgb), nx, ny, nz, fvec(volume["origin"]),
+        fvec(volume["spacing"]), _ptr(depth), _ptr(color), _ptr(poses), B, fx, fy, cx, cy,
+        H, W, float(trunc), float(max_weight), float(depth_min), float(depth_max),
+        _stream()), "ucsa_tsdf_integrate")
+    return volume

@@ -1,0 +1,133 @@
+"""A scene's mesh from its posed depth frames, on the GPU: projective TSDF
+fusion into a dense volume, then marching cubes over the observed cells.  The
+first stage of the mapping-based pseudo-label baseline, so that the chain runs
+from a scene directory alone:
+
+    depth/ + poses --fuse_depth_views--> mesh --mesh_fusion.fuse_views--> labels
+        --ops.rasterize_mesh--> map_label
+
+``ops.integrate_tsdf`` updates the volume with a batch of views per call (the
+voxel state is read and written once per batch); ``ops.marching_cubes`` with
+``valid = weight >= min_weight`` meshes ``-tsdf`` at 0 and leaves out every cell
+with an unobserved corner (no second sheet one truncation distance behind the
+walls).  Out of scope: sparse / hashed voxel blocks, per-voxel class votes,
+ray-cast updates, bilinear depth lookup, distance- or angle-dependent weights,
+pose refinement, anything in the training loop."""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+import torch
+
+from .. import ops
+from .mesh_fusion import _batch
+
+
+def depth_points_aabb(poses, intrinsics, depth_maps, H, W, batch=16, depth_min=1e-6,
+                      depth_max=3.0e38, device="cuda"):
+    """Bounding box [2,3] (numpy f32, poses' frame) of the back-projected valid
+    depth points of all views, computed on the device batch by batch."""
+    dev = torch.device(device)
+    fx, fy, cx, cy = [float(v) for v in intrinsics]
+    poses = torch.as_tensor(np.asarray(poses, np.float32)).reshape(-1, 4, 4)
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32),
+                            torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    ray = torch.stack([(xs + 0.5 - cx) / fx, (ys + 0.5 - cy) / fy, torch.ones_like(xs)], -1)
+    lo = torch.full((3,), float("inf"), device=dev)
+    hi = torch.full((3,), float("-inf"), device=dev)
+    for a in range(0, poses.shape[0], batch):
+        b = min(a + batch, poses.shape[0])
+        z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
+        P = poses[a:b].to(dev)
+        ok = torch.isfinite(z) & (z >= depth_min) & (z <= depth_max)
+        pc = ray[None] * torch.where(ok, z, torch.zeros_like(z))[..., None]
+        pw = torch.einsum("bhwc,brc->bhwr", pc, P[:, :3, :3]) + P[:, None, None, :3, 3]
+        inf = torch.full_like(pw, float("inf"))
+        lo = torch.minimum(lo, torch.where(ok[..., None], pw, inf).amin((0, 1, 2)))
+        hi = torch.maximum(hi, torch.where(ok[..., None], pw, -inf).amax((0, 1, 2)))
+    if not bool(torch.isfinite(lo).all() and torch.isfinite(hi).all()):
+        raise ValueError("no valid depth measurement in any view")
+    return torch.stack([lo, hi]).cpu().numpy()
+
+
+def extract_mesh(volume, min_weight=1):
+    """A volume of ``ops.tsdf_volume`` -> (verts, faces, normals, rgb or None)
+    on the device: ``-tsdf`` at iso 0 over the cells whose corners all have
+    weight >= min_weight; a vertex takes the colour of the nearer end point of
+    its edge (both are observed)."""
+    valid = volume["weight"] >= float(min_weight)
+    verts, faces, normals = ops.marching_cubes(-volume["tsdf"], 0.0, volume["origin"],
+                                               volume["spacing"], valid=valid)
+    rgb = None
+    if volume.get("rgb") is not None:
+        dev = verts.device
+        o = torch.tensor(volume["origin"], device=dev)
+        h = torch.tensor(volume["spacing"], device=dev)
+        top = torch.tensor(volume["tsdf"].shape, device=dev) - 1
+        q = torch.minimum(torch.round((verts - o) / h).long().clamp_(min=0), top)
+        rgb = (volume["rgb"][q[:, 0], q[:, 1], q[:, 2]] / 255.0).clamp_(0.0, 1.0)
+    return verts, faces, normals, rgb
+
+
+def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=None,
+                     voxel=0.05, trunc=None, min_weight=1, batch=16, max_weight=65504.0,
+                     depth_min=1e-6, depth_max=3.0e38, device="cuda"):
+    """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps``: a sequence
+    or a callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), read
+    batch by batch; ``color_maps`` likewise ``i -> [H,W,3]`` uint8 or None;
+    ``aabb`` [2,3] or 6 numbers (lo, hi) of the volume, None = the bounding box
+    of the back-projected valid depth points padded by ``trunc``; ``voxel`` the
+    lattice spacing and ``trunc`` the truncation distance in scene units
+    (default: 4 voxels).  -> a mesh dict as ``load_mesh`` gives it (numpy, NGP
+    frame): verts [V,3] f32, faces [F,3] int32, normals [V,3] f32, rgb [V,3]
+    f32 in [0,1] or None, labels None; plus ``dims``, ``origin``, ``spacing``,
+    ``observed`` (share of voxels with weight >= min_weight) and the wall-time
+    split ``integrate_ms`` / ``extract_ms`` (device-synchronised host clock)."""
+    dev = torch.device(device)
+    voxel = float(voxel)
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    if not (voxel > 0 and trunc > 0):
+        raise ValueError("voxel and trunc must be > 0")
+    poses = torch.as_tensor(np.asarray(poses, np.float32)).reshape(-1, 4, 4)
+    N = int(poses.shape[0])
+    if N == 0:
+        raise ValueError("no views")
+    if aabb is None:
+        box = depth_points_aabb(poses, intrinsics, depth_maps, H, W, batch, depth_min,
+                                depth_max, dev)
+        box = box + np.array([[-trunc], [trunc]], np.float32)
+    else:
+        box = np.asarray(aabb, np.float32).reshape(2, 3)
+    dims = [max(2, int(np.ceil(float(box[1, a] - box[0, a]) / voxel - 1e-6)) + 1)
+            for a in range(3)]
+    vol = ops.tsdf_volume(dims, box[0].tolist(), voxel, with_color=color_maps is not None,
+                          device=dev)
+    t_i = 0.0
+    for a in range(0, N, batch):
+        b = min(a + batch, N)
+        z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
+        col = None
+        if color_maps is not None:
+            col = np.stack([np.asarray(color_maps(i) if callable(color_maps) else color_maps[i])
+                            for i in range(a, b)])
+            if col.shape[1:] != (H, W, 3):
+                raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape[1:]}")
+            col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))).to(dev)
+        P = poses[a:b].to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
+                           depth_min=depth_min, depth_max=depth_max)
+        torch.cuda.synchronize()
+        t_i += time.perf_counter() - t0
+    t0 = time.perf_counter()
+    verts, faces, normals, rgb = extract_mesh(vol, min_weight)
+    torch.cuda.synchronize()
+    t_e = time.perf_counter() - t0
+    observed = float((vol["weight"] >= float(min_weight)).float().mean())
+    return {"verts": verts.cpu().numpy(), "faces": faces.cpu().numpy(),
+            "normals": normals.cpu().numpy(),
+            "rgb": None if rgb is None else rgb.cpu().numpy(), "labels": None,
+            "dims": tuple(dims), "origin": vol["origin"], "spacing": vol["spacing"],
+            "observed": observed, "integrate_ms": 1e3 * t_i, "extract_ms": 1e3 * t_e}
