@@ -1439,6 +1439,128 @@ int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx,
                             uint32_t W, float trunc, float max_weight, float depth_min,
                             float depth_max, void* stream);
 
+/* ---- voxel map: per-voxel class votes and a ray-caster over the TSDF volume
+ * (not in the reference) ----------------------------------------------------
+ * The voxel route of the mapping baseline (utils/voxel_map.py,
+ * scripts/voxel_map_labels.py): label maps vote into the voxels of the band
+ * around the measured surface while depth is integrated, the votes resolve to
+ * one label per voxel, and the volume is ray-cast into any camera view.  No
+ * mesh, no vertex-id render, no 64-bit table.  tests/voxel_map_numpy.py
+ * restates the three contracts; the outputs match it bit for bit.
+ *
+ * ucsa_tsdf_vote: B views vote into votes [C+1][nx][ny][nz] uint16, allocated
+ *   AND zeroed by the caller, accumulated over calls; plane 0 is never written
+ *   (plane = class id).  Class-major: the 64 voxels of a wave are consecutive
+ *   in k and mostly vote for one class, so their read-modify-write is one
+ *   coalesced line per plane.  Lattice, depth, poses, intrinsics as for
+ *   ucsa_tsdf_integrate; pred [B,H,W] uint8 class ids.
+ *   Per voxel, for b = 0..B-1: the projection and the skip tests of
+ *   ucsa_tsdf_integrate verbatim (camera point, c_z > 0, floor to the nearest
+ *   pixel, bounds, z finite and depth_min <= z <= depth_max, sdf = z - c_z);
+ *   the voxel votes iff -trunc <= sdf <= trunc (the band only, not the free
+ *   space in front) and 1 <= pred[b][v][u] <= C, and then
+ *   votes[pred][voxel] = min(votes[pred][voxel] + 1, 65535).
+ *   The votes do not depend on the TSDF state.  One thread owns a voxel: no
+ *   atomics; a saturating add of ones commutes, so every split and every order
+ *   of the views over calls gives the same bytes, and so do two runs.  Within a
+ *   launch (up to 32 views) a thread keeps a pending (class, count) in
+ *   registers and flushes it when the class changes; a work-group skips a view
+ *   for its whole 1x4x64 brick by ucsa_tsdf_integrate's corner test.  Neither
+ *   changes a bit.
+ *   Limits as for ucsa_tsdf_integrate (dims: argument 3..5 here), 1 <= C <= 255
+ *   (argument 2), (C+1)*nx*ny*nz <= 2^40 and votes_capacity (uint16 elements)
+ *   >= that (argument 1); an argument error comes before any launch and
+ *   nothing is written.
+ * ucsa_voxel_label_resolve: per voxel x of n_voxels, s_c = votes[c][x]:
+ *   total[x] = sum of s_c over c = 1..C (uint32), winner[x] = max of s_c,
+ *   label[x] (uint8) = the lowest c with s_c == winner[x] if total[x] >=
+ *   min_votes, else 0 (ucsa_label_fuse_resolve's rule).  min_votes >= 1.  The
+ *   planes are read one after the other, coalesced; no atomics.  label / total
+ *   / winner hold max_voxels >= n_voxels elements each.
+ * ucsa_tsdf_raycast: the volume (tsdf, weight, rgb or NULL: the state of
+ *   ucsa_tsdf_integrate) seen from B posed pinhole cameras.  Outputs, one
+ *   element per pixel, capacity max_pixels >= B*H*W each:
+ *     depth [B,H,W] fp32: z-depth of the hit in scene units (the rasterizer's
+ *       depth, the depth PNGs), 0 on a miss;
+ *     voxel_id [B,H,W] int32: (i*ny + j)*nz + k of the lattice point nearest to
+ *       the hit, -1 on a miss;
+ *     normal [B,H,W,3] fp32 or NULL: world frame, toward free space;
+ *     rgb_out [B,H,W,3] fp32, iff rgb is given (both or neither);
+ *     label [B,H,W] int32 = voxel_labels[voxel_id] (voxel_labels [nx,ny,nz]
+ *       uint8), iff voxel_labels is given (both or neither); 0 on a miss.
+ *   Contract (fp32, every operation as written, no contraction, correctly
+ *   rounded division and sqrt).  R = P[0:3,0:3], t = P[0:3,3], top_a = n_a - 1:
+ *   ray of pixel (x, y): d = ((x+0.5-cx)/fx, (y+0.5-cy)/fy, 1) (k_get_rays'
+ *     order); world direction w_a = (R_a0*d0 + R_a1*d1) + R_a2, NOT normalised:
+ *     the ray parameter is camera z and the hit parameter is the depth itself;
+ *   lattice coordinates: q0_a = (t_a - origin_a)/spacing_a, qd_a = w_a/spacing_a,
+ *     g_a(z) = q0_a + z*qd_a;
+ *   interval: z_in = near, z_out = far, then per axis a = 0, 1, 2: with
+ *     qd_a == 0 the ray misses unless 0 <= q0_a <= top_a; otherwise
+ *     z1 = (0 - q0_a)/qd_a, z2 = (top_a - q0_a)/qd_a, lo = min, hi = max,
+ *     z_in = lo > z_in ? lo : z_in, z_out = hi < z_out ? hi : z_out.  A miss
+ *     unless z_in <= z_out and q0, qd, z_in, z_out are all finite;
+ *   samples: dz = step / sqrt((d0*d0 + d1*d1) + 1), z_k = z_in + (float)k*dz
+ *     for k = 0, 1, ... while z_k <= z_out and k < 2^20 (indexed, not
+ *     accumulated: an implementation may skip indices);
+ *   cell of a sample at z: per axis c_a = min(max(floor(g_a), 0), n_a - 2),
+ *     fraction f_a = min(max(g_a - (float)c_a, 0), 1); corners v_{ijk} at
+ *     (c_0+i, c_1+j, c_2+k); the sample is valid iff all eight corners have
+ *     weight >= min_weight (the cell rule of ucsa_mc_*_masked);
+ *   value, seven lerps l(a, b, f) = a + f*(b - a): along k first,
+ *     c_ij = l(v_ij0, v_ij1, f_2); then along j, c_i = l(c_i0, c_i1, f_1); then
+ *     f = l(c_0, c_1, f_0);
+ *   hit: the first k with z_{k+1} <= z_out, both samples valid, f_k > 0,
+ *     f_{k+1} <= 0 and, with z = z_k + dz*(f_k / (f_k - f_{k+1})) clamped into
+ *     [z_k, z_{k+1}], the cell of z valid too (the crossing can lie in a third
+ *     cell; with an unobserved corner there the masked mesh has no face, the
+ *     march goes on, and no output is interpolated from an unobserved voxel).
+ *     No other stop rule: a surface within one step of the box's far side can
+ *     be stepped over (pad the volume by trunc, or shorten the step);
+ *   at g(z) of the hit, in its cell with its fractions: gradient
+ *     G_0 = c_1 - c_0, G_1 = l(c_01 - c_00, c_11 - c_10, f_0),
+ *     G_2 = l(l(e_00, e_01, f_1), l(e_10, e_11, f_1), f_0) with
+ *     e_ij = v_ij1 - v_ij0; n_a = G_a/spacing_a, normal = n / sqrt((n_0*n_0 +
+ *     n_1*n_1) + n_2*n_2), (0,0,0) when that length is zero or non-finite;
+ *     rgb_out: the seven lerps of rgb per channel; voxel_id from
+ *     min(max(rint(g_a), 0), top_a) per axis (round half to even).
+ *   One thread per pixel, a wave per 8x8 pixel patch (its rays stay in
+ *   neighbouring cells); no atomics: two runs give the same bytes.
+ *   Empty-space skipping (the default): a crossing needs f_{k+1} <= 0, a
+ *   clamped-fraction lerp of eight valid corners, so one of them is <= 2^-16
+ *   (the margin covers the rounding of the seven lerps of values in [-1, 1]).
+ *   A pre-pass marks the 8x8x8-cell bricks that hold such a cell into
+ *   `workspace` (ucsa_tsdf_raycast_workspace_bytes, checked against
+ *   workspace_bytes), and index k is evaluated only if the cell of sample k or
+ *   of sample k+1 lies in a marked brick.  The bytes are those of the plain
+ *   march, flags = UCSA_RAYCAST_PLAIN_MARCH, which needs no workspace and is
+ *   kept as the baseline of tools/voxel_map_time.py.
+ *   Limits: dims >= 2 each, nx*ny*nz <= 2^31-1, spacing finite and non-zero,
+ *   1 <= B <= 65535, 1 <= H, W <= 16384, fx, fy > 0, near > 0, far >= near,
+ *   trunc > 0, 0 < step < trunc (the truncation distance the volume was
+ *   integrated with: a longer step can jump the band), min_weight > 0; an
+ *   argument error comes before any launch and nothing is written. */
+#define UCSA_RAYCAST_PLAIN_MARCH 1u
+int32_t ucsa_tsdf_vote(uint16_t* votes, uint64_t votes_capacity, uint32_t C,
+                       uint32_t nx, uint32_t ny, uint32_t nz, const float* origin3,
+                       const float* spacing3, const float* depth, const uint8_t* pred,
+                       const float* poses, uint32_t B, float fx, float fy, float cx,
+                       float cy, uint32_t H, uint32_t W, float trunc, float depth_min,
+                       float depth_max, void* stream);
+int32_t ucsa_voxel_label_resolve(const uint16_t* votes, uint32_t C, uint64_t n_voxels,
+                                 uint32_t min_votes, uint8_t* label, uint32_t* total,
+                                 uint32_t* winner, uint64_t max_voxels, void* stream);
+uint64_t ucsa_tsdf_raycast_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int32_t ucsa_tsdf_raycast(const float* tsdf, const float* weight, const float* rgb,
+                          const uint8_t* voxel_labels, uint32_t nx, uint32_t ny,
+                          uint32_t nz, const float* origin3, const float* spacing3,
+                          const float* poses, uint32_t B, float fx, float fy, float cx,
+                          float cy, uint32_t H, uint32_t W, float near, float far,
+                          float trunc, float step, float min_weight, float* depth,
+                          int32_t* voxel_id, float* normal, float* rgb_out,
+                          int32_t* label, uint64_t max_pixels, void* workspace,
+                          uint64_t workspace_bytes, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Pseudo-labels from a semantic voxel map (GPU: ``ops.integrate_tsdf`` +
+``ops.vote_voxel_labels`` + ``ops.raycast_tsdf``, ``utils/voxel_map.py``): a
+scene's posed depth frames are fused into a TSDF volume while its per-frame 2D
+label maps vote per voxel, and the map is ray-cast back into the frames.  The
+voxel-route sibling of ``fuse_tsdf_mesh.py`` + ``fuse_mesh_labels.py --render``.
+
+    python scripts/voxel_map_labels.py --scene_root <root>/<scene> \\
+        --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] --out_dir D \\
+        [--voxel METRES] [--trunc METRES] [--step METRES] [--every N] \\
+        [--min_votes K] [--aabb x0 y0 z0 x1 y1 z1] [--score]
+
+Writes ``D/map_label/<stem>.png`` (uint8 NYU40 id, 0 = nothing) and
+``D/map_depth/<stem>.png`` (uint16 millimetres, 0 = nothing; the layout of
+``depth/`` and of ``render_mesh_labels.py``) for the frames of
+transforms_train.json that were used (every ``--every``-th).  ``--labels`` as
+for ``fuse_mesh_labels.py``.  The volume is ``--aabb`` (NGP frame, scene units)
+or the box of the back-projected depth points padded by the truncation
+distance.  ``--score`` scores ``map_label`` and the input label maps against
+``label_40``: one JSON line with the input mIoU next to the voxel map's."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ucsa_neural_rendering_amd.utils.mesh_render import (  # noqa: E402
+    read_frames, score_label_maps)
+from ucsa_neural_rendering_amd.utils.voxel_map import (  # noqa: E402
+    fuse_semantic_views, render_voxel_map)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--scene_root", required=True, help="<root>/<scene>")
+    p.add_argument("--labels", required=True,
+                   help="seg_label | nerf_label | label_40 | a directory of <stem>.png")
+    p.add_argument("--exp_name", default=None)
+    p.add_argument("--out_dir", required=True, help="where map_label/ and map_depth/ go")
+    p.add_argument("--voxel", type=float, default=0.04, help="metres")
+    p.add_argument("--trunc", type=float, default=None, help="metres (default: 4 voxels)")
+    p.add_argument("--step", type=float, default=None,
+                   help="ray-cast step in metres (default: trunc / 2)")
+    p.add_argument("--every", type=int, default=1, help="use every N-th frame")
+    p.add_argument("--min_votes", type=int, default=1)
+    p.add_argument("--aabb", type=float, nargs=6, default=None,
+                   help="x0 y0 z0 x1 y1 z1, NGP frame, scene units")
+    p.add_argument("--near", type=float, default=0.05, help="near plane, scene units")
+    p.add_argument("--far", type=float, default=None,
+                   help="far plane, scene units (default: the volume's diagonal)")
+    p.add_argument("--num_classes", type=int, default=40)
+    p.add_argument("--batch", type=int, default=16, help="views per call")
+    p.add_argument("--score", action="store_true")
+    return p.parse_args(argv)
+
+
+def label_dir(a):
+    if a.labels == "label_40":
+        return os.path.join(a.scene_root, "label_40")
+    if a.labels in ("seg_label", "nerf_label"):
+        if a.exp_name is None:
+            raise SystemExit(f"--labels {a.labels} reads <scene>/<exp_name>/{a.labels}: "
+                             "give --exp_name")
+        return os.path.join(a.scene_root, a.exp_name, a.labels)
+    return a.labels
+
+
+def main(argv=None):
+    from PIL import Image
+    a = parse_args(argv)
+    if a.every < 1 or a.min_votes < 1 or a.batch < 1:
+        raise SystemExit("--every, --min_votes and --batch must be >= 1")
+    fr = read_frames(a.scene_root)
+    uom = fr["one_m_to_scene_uom"]
+    keep = list(range(0, len(fr["stems"]), a.every))
+    stems = [fr["stems"][i] for i in keep]
+    poses = fr["poses"][keep]
+    H, W = fr["H"], fr["W"]
+    src = label_dir(a)
+
+    def png(folder, i):
+        return np.asarray(Image.open(os.path.join(folder, stems[i] + ".png")))
+
+    def depth(i):
+        mm = png(os.path.join(a.scene_root, "depth"), i)
+        return (mm.astype(np.float32) / np.float32(1000.0)) * np.float32(uom)
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fused = fuse_semantic_views(poses, fr["intrinsics"], H, W, depth, lambda i: png(src, i),
+                                aabb=a.aabb, voxel=a.voxel * uom,
+                                trunc=None if a.trunc is None else a.trunc * uom,
+                                batch=a.batch, num_classes=a.num_classes,
+                                min_votes=a.min_votes)
+    torch.cuda.synchronize()
+    t_fuse = time.perf_counter() - t0
+    vol = fused["volume"]
+    far = a.far
+    if far is None:
+        far = a.near + float(np.linalg.norm((np.asarray(fused["dims"]) - 1) *
+                                            np.asarray(vol["spacing"])))
+    for k in ("map_label", "map_depth"):
+        os.makedirs(os.path.join(a.out_dir, k), exist_ok=True)
+    maps, t_cast = [], 0.0
+    it = render_voxel_map(vol, fused["labels"], poses, fr["intrinsics"], H, W, a.near, far,
+                          step=None if a.step is None else a.step * uom, batch=a.batch)
+    while True:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        try:
+            start, out = next(it)
+        except StopIteration:
+            break
+        torch.cuda.synchronize()
+        t_cast += time.perf_counter() - t0
+        lab = out["label"].clamp(0, 255).to(torch.uint8).cpu().numpy()
+        mm = torch.round(out["depth"].double() / uom * 1000.0).clamp(0, 65535)
+        mm = mm.to(torch.int32).cpu().numpy().astype(np.uint16)
+        for i in range(lab.shape[0]):
+            stem = stems[start + i]
+            Image.fromarray(lab[i]).save(os.path.join(a.out_dir, "map_label", stem + ".png"))
+            Image.fromarray(mm[i]).save(os.path.join(a.out_dir, "map_depth", stem + ".png"))
+        maps.append(lab)
+    n = len(stems)
+    rec = {"out_dir": a.out_dir, "labels": src, "frames": n, "dims": list(fused["dims"]),
+           "observed": round(fused["observed"], 4), "labelled": round(fused["labelled"], 4),
+           "fuse_ms_per_view": round(1e3 * t_fuse / max(n, 1), 3),
+           "raycast_ms_per_view": round(1e3 * t_cast / max(n, 1), 3)}
+    if a.score:
+        truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
+        given = np.stack([png(src, i) for i in range(n)])
+        rec["input"] = score_label_maps(given, truth, a.num_classes)
+        rec["voxel_map"] = score_label_maps(np.concatenate(maps), truth, a.num_classes)
+    print(json.dumps(rec))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

@@ -320,6 +320,17 @@ SIGNATURES = {
     "ucsa_tsdf_integrate": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, C.POINTER(_f),
                                         C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f,
                                         _u32, _u32, _f, _f, _f, _f, _p]),
+    # ---- voxel map (per-voxel class votes, ray-caster over the TSDF volume) ----
+    "ucsa_tsdf_vote": (C.c_int32, [_p, C.c_uint64, _u32, _u32, _u32, _u32, C.POINTER(_f),
+                                   C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f, _u32,
+                                   _u32, _f, _f, _f, _p]),
+    "ucsa_voxel_label_resolve": (C.c_int32, [_p, _u32, C.c_uint64, _u32, _p, _p, _p,
+                                             C.c_uint64, _p]),
+    "ucsa_tsdf_raycast_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32]),
+    "ucsa_tsdf_raycast": (C.c_int32, [_p, _p, _p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                      C.POINTER(_f), _p, _u32, _f, _f, _f, _f, _u32, _u32,
+                                      _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, C.c_uint64,
+                                      _p, C.c_uint64, _u32, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

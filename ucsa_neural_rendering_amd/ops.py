@@ -1837,3 +1837,166 @@ def integrate_tsdf(volume, depth, poses, intrinsics, trunc: float, color=None,
         H, W, float(trunc), float(max_weight), float(depth_min), float(depth_max),
         _stream()), "ucsa_tsdf_integrate")
     return volume
+
+
+# ---------------------------------------------------------------------------
+# voxel map (per-voxel class votes, ray-caster over the TSDF volume)
+# ---------------------------------------------------------------------------
+def _volume_lattice(volume):
+    """(nx, ny, nz), device of a ``tsdf_volume`` checked as ``integrate_tsdf`` does"""
+    for k in ("tsdf", "weight"):
+        _inplace_f32(volume[k], f"volume['{k}']")
+    tsdf, weight = volume["tsdf"], volume["weight"]
+    if tsdf.dim() != 3 or weight.shape != tsdf.shape or weight.device != tsdf.device:
+        raise _lib.UcsaError("volume: tsdf and weight must be [nx,ny,nz] on one device")
+    dev = tsdf.device
+    if dev.index != torch.cuda.current_device():
+        raise _lib.UcsaError(f"the volume is on {dev} but the current device is cuda:"
+                             f"{torch.cuda.current_device()}: call torch.cuda.set_device first")
+    rgb = volume.get("rgb")
+    if rgb is not None:
+        _inplace_f32(rgb, "volume['rgb']")
+        if tuple(rgb.shape) != tuple(tsdf.shape) + (3,) or rgb.device != dev:
+            raise _lib.UcsaError("volume: rgb must be [nx,ny,nz,3] on the volume's device")
+    return tuple(int(s) for s in tsdf.shape), dev
+
+
+def _u8_on(t, name, shape, dev):
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == dev):
+        raise _lib.UcsaError(f"{name} must be a GPU tensor on the volume's device: the HIP "
+                             "path has no CPU fallback")
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+        raise _lib.UcsaError(f"{name} must be uint8 {list(shape)}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    return t.contiguous()
+
+
+def voxel_votes(volume, n_classes: int):
+    """The zeroed vote table of a ``tsdf_volume`` for ``vote_voxel_labels``:
+    [C+1, nx, ny, nz] uint16, class-major (plane = class id, plane 0 unused),
+    1 <= C <= 255."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    Cn = int(n_classes)
+    if not 1 <= Cn <= 255:
+        raise _lib.UcsaError(f"voxel_votes: n_classes must be in 1..255, got {n_classes}")
+    if (Cn + 1) * nx * ny * nz > 1 << 40:
+        raise _lib.UcsaError("voxel_votes: (C+1)*nx*ny*nz must be at most 2^40")
+    return torch.zeros(Cn + 1, nx, ny, nz, dtype=torch.uint16, device=dev)
+
+
+def _vote_planes(votes):
+    if not (torch.is_tensor(votes) and votes.is_cuda and votes.dtype == torch.uint16
+            and votes.is_contiguous()):
+        raise _lib.UcsaError("votes must be a contiguous uint16 tensor on the GPU")
+    if votes.dim() != 4 or not 2 <= votes.shape[0] <= 256:
+        raise _lib.UcsaError(f"votes must be [C+1,nx,ny,nz] with 1 <= C <= 255, got "
+                             f"{tuple(votes.shape)}")
+    return int(votes.shape[0]) - 1
+
+
+def vote_voxel_labels(votes, volume, depth, pred, poses, intrinsics, trunc: float,
+                      depth_min: float = 1e-6, depth_max: float = 3.0e38):
+    """B posed views vote into ``votes`` (``voxel_votes``), in place; returns
+    ``votes``.  ``depth`` [B,H,W] f32, ``poses`` [B,4,4], ``intrinsics`` as for
+    ``integrate_tsdf``; ``pred`` [B,H,W] uint8 class ids.  A voxel votes for
+    pred's class at the pixel it projects to iff the depth there puts it in the
+    band |z - c_z| <= trunc and 1 <= pred <= C; counts saturate at 65535.
+    Contract of ucsa_tsdf_vote (include/ucsa_hip.h): independent of the TSDF
+    state, and the same bytes for every split and order of the views."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    Cn = _vote_planes(votes)
+    if tuple(votes.shape[1:]) != (nx, ny, nz) or votes.device != dev:
+        raise _lib.UcsaError(f"votes must be [C+1,{nx},{ny},{nz}] on the volume's device, got "
+                             f"{tuple(votes.shape)} on {votes.device}")
+    depth = _f32(depth, "depth")
+    poses = _f32(poses, "poses")
+    if depth.dim() != 3:
+        raise _lib.UcsaError(f"depth must be [B,H,W], got {tuple(depth.shape)}")
+    B, H, W = (int(s) for s in depth.shape)
+    if poses.dim() != 3 or tuple(poses.shape) != (B, 4, 4):
+        raise _lib.UcsaError(f"poses must be [{B},4,4], got {tuple(poses.shape)}")
+    if depth.device != dev or poses.device != dev:
+        raise _lib.UcsaError("depth and poses must be on the volume's device")
+    pred = _u8_on(pred, "pred", (B, H, W), dev)
+    fx, fy, cx, cy = [float(v) for v in intrinsics]
+    check(lib().ucsa_tsdf_vote(
+        _ptr(votes), votes.numel(), Cn, nx, ny, nz, fvec(volume["origin"]),
+        fvec(volume["spacing"]), _ptr(depth), _ptr(pred), _ptr(poses), B, fx, fy, cx, cy,
+        H, W, float(trunc), float(depth_min), float(depth_max), _stream()), "ucsa_tsdf_vote")
+    return votes
+
+
+def resolve_voxel_labels(votes, min_votes: int = 1):
+    """``votes`` [C+1,nx,ny,nz] -> dict of device tensors [nx,ny,nz]: ``label``
+    uint8 (the class with the most votes, ties to the lower id, 0 where the
+    voxel's total is below ``min_votes``), ``total`` and ``winner`` uint32
+    (confidence = winner / total).  ucsa_voxel_label_resolve."""
+    Cn = _vote_planes(votes)
+    min_votes = int(min_votes)
+    if not 1 <= min_votes < 1 << 32:
+        raise _lib.UcsaError(f"min_votes must be in 1..2^32-1, got {min_votes}")
+    shape, dev = tuple(votes.shape[1:]), votes.device
+    n = int(votes[0].numel())
+    out = {"label": torch.empty(shape, dtype=torch.uint8, device=dev),
+           "total": torch.empty(shape, dtype=torch.uint32, device=dev),
+           "winner": torch.empty(shape, dtype=torch.uint32, device=dev)}
+    check(lib().ucsa_voxel_label_resolve(_ptr(votes), Cn, n, min_votes, _ptr(out["label"]),
+                                         _ptr(out["total"]), _ptr(out["winner"]), n,
+                                         _stream()), "ucsa_voxel_label_resolve")
+    return out
+
+
+def raycast_tsdf(volume, poses, intrinsics, H: int, W: int, near: float, far: float,
+                 step: Optional[float] = None, min_weight: float = 1.0, voxel_labels=None,
+                 trunc: Optional[float] = None, _plain_march: bool = False):
+    """The model view of a TSDF volume from B posed cameras -> dict of device
+    tensors: ``depth`` [B,H,W] f32 (z-depth of the first surface along the
+    pixel's ray, 0 = miss), ``voxel_id`` [B,H,W] int32 (linear index of the
+    nearest lattice point, -1 = miss), ``normal`` [B,H,W,3] f32 (world frame,
+    toward free space), ``rgb`` [B,H,W,3] f32 when the volume has colour,
+    ``label`` [B,H,W] int32 when ``voxel_labels`` [nx,ny,nz] uint8 is given.
+    ``trunc`` is the truncation distance the volume was integrated with
+    (default: ``volume["trunc"]``, which utils/voxel_map.py records);
+    ``step`` the march step in scene units (default trunc / 2, must stay below
+    trunc); only cells whose eight corners have weight >= ``min_weight`` are
+    seen (the masked mesh's cell rule).  Contract of ucsa_tsdf_raycast
+    (include/ucsa_hip.h); ``_plain_march`` selects the march without
+    empty-space skipping, which gives the same bytes."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    poses = _f32(poses, "poses")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.device != dev:
+        raise _lib.UcsaError(f"poses must be [B,4,4] on the volume's device, got "
+                             f"{tuple(poses.shape)} on {poses.device}")
+    B, H, W = int(poses.shape[0]), int(H), int(W)
+    if B < 1 or H < 1 or W < 1:
+        raise _lib.UcsaError("raycast_tsdf: B, H, W must be >= 1")
+    if trunc is None:
+        trunc = volume.get("trunc")
+    if trunc is None:
+        raise _lib.UcsaError("raycast_tsdf: pass trunc, the truncation distance the volume "
+                             "was integrated with (or record it as volume['trunc'])")
+    trunc = float(trunc)
+    step = 0.5 * trunc if step is None else float(step)
+    rgb = volume.get("rgb")
+    labels = None if voxel_labels is None else _u8_on(voxel_labels, "voxel_labels",
+                                                       (nx, ny, nz), dev)
+    out = {"depth": torch.empty(B, H, W, device=dev),
+           "voxel_id": torch.empty(B, H, W, dtype=torch.int32, device=dev),
+           "normal": torch.empty(B, H, W, 3, device=dev)}
+    if rgb is not None:
+        out["rgb"] = torch.empty(B, H, W, 3, device=dev)
+    if labels is not None:
+        out["label"] = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    ws, ws_bytes = None, 0
+    if not _plain_march:
+        ws_bytes = int(lib().ucsa_tsdf_raycast_workspace_bytes(nx, ny, nz))
+        ws = _scratch_named("raycast", ws_bytes, dev)
+    fx, fy, cx, cy = [float(v) for v in intrinsics]
+    check(lib().ucsa_tsdf_raycast(
+        _ptr(volume["tsdf"]), _ptr(volume["weight"]), _ptr(rgb), _ptr(labels), nx, ny, nz,
+        fvec(volume["origin"]), fvec(volume["spacing"]), _ptr(poses), B, fx, fy, cx, cy, H, W,
+        float(near), float(far), trunc, step, float(min_weight), _ptr(out["depth"]),
+        _ptr(out["voxel_id"]), _ptr(out["normal"]), _ptr(out.get("rgb")),
+        _ptr(out.get("label")), B * H * W, _ptr(ws), ws_bytes, 1 if _plain_march else 0,
+        _stream()), "ucsa_tsdf_raycast")
+    return out

@@ -10,9 +10,10 @@ from a scene directory alone:
 voxel state is read and written once per batch); ``ops.marching_cubes`` with
 ``valid = weight >= min_weight`` meshes ``-tsdf`` at 0 and leaves out every cell
 with an unobserved corner (no second sheet one truncation distance behind the
-walls).  Out of scope: sparse / hashed voxel blocks, per-voxel class votes,
-ray-cast updates, bilinear depth lookup, distance- or angle-dependent weights,
-pose refinement, anything in the training loop."""
+walls).  Per-voxel class votes and the ray-cast model view of the volume are in
+``utils/voxel_map.py``.  Out of scope: sparse / hashed voxel blocks, bilinear
+depth lookup, distance- or angle-dependent weights, pose refinement, anything in
+the training loop."""
 from __future__ import annotations
 
 import time

@@ -1,0 +1,91 @@
+"""The voxel route of the mapping-based pseudo-label baseline, on the GPU: a
+semantic voxel map instead of a labelled mesh.
+
+    depth/ + poses + label maps --fuse_semantic_views--> volume, votes, labels
+        --render_voxel_map--> map_label, map_depth
+
+While ``ops.integrate_tsdf`` fuses a batch of depth views, ``ops.vote_voxel_labels``
+lets the same views vote for their classes in the voxels of the truncation band;
+``ops.resolve_voxel_labels`` keeps the winner per voxel and ``ops.raycast_tsdf``
+ray-casts the volume into any posed view (depth, normal, the nearest voxel's
+label).  No mesh is extracted and no per-view vertex-id render is needed.  Out
+of scope: sparse / hashed blocks, soft votes, view-dependent weights, pose
+refinement."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ops
+from .mesh_fusion import _batch
+from .tsdf_fusion import depth_points_aabb
+
+
+def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_maps=None,
+                        aabb=None, voxel=0.05, trunc=None, batch=16, num_classes=40,
+                        min_votes=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
+                        device="cuda"):
+    """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps`` /
+    ``label_maps`` / ``color_maps``: sequences or callables ``i -> [H,W]`` fp32
+    z-depth in scene units (0 = none), ``[H,W]`` uint8 class ids (0 = no vote),
+    ``[H,W,3]`` uint8 or None, read batch by batch.  The volume is picked as
+    ``fuse_depth_views`` picks it (``aabb``, else the box of the back-projected
+    depth points padded by ``trunc``; ``trunc`` defaults to 4 voxels).  -> dict:
+    ``volume`` (``ops.tsdf_volume`` with ``trunc`` recorded), ``votes``
+    [C+1,nx,ny,nz] uint16, ``labels`` [nx,ny,nz] uint8, ``total`` / ``winner``
+    uint32, all on the device, and ``dims``, ``observed`` (share of voxels with
+    weight >= 1), ``labelled`` (share with a label)."""
+    dev = torch.device(device)
+    voxel = float(voxel)
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    if not (voxel > 0 and trunc > 0):
+        raise ValueError("voxel and trunc must be > 0")
+    poses = torch.as_tensor(np.asarray(poses, np.float32)).reshape(-1, 4, 4)
+    N = int(poses.shape[0])
+    if N == 0:
+        raise ValueError("no views")
+    if aabb is None:
+        box = depth_points_aabb(poses, intrinsics, depth_maps, H, W, batch, depth_min,
+                                depth_max, dev)
+        box = box + np.array([[-trunc], [trunc]], np.float32)
+    else:
+        box = np.asarray(aabb, np.float32).reshape(2, 3)
+    dims = [max(2, int(np.ceil(float(box[1, a] - box[0, a]) / voxel - 1e-6)) + 1)
+            for a in range(3)]
+    vol = ops.tsdf_volume(dims, box[0].tolist(), voxel, with_color=color_maps is not None,
+                          device=dev)
+    vol["trunc"] = trunc
+    votes = ops.voxel_votes(vol, num_classes)
+    for a in range(0, N, batch):
+        b = min(a + batch, N)
+        z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
+        lab = _batch(label_maps, a, b, np.uint8, H, W, "label_maps").to(dev)
+        col = None
+        if color_maps is not None:
+            col = np.stack([np.asarray(color_maps(i) if callable(color_maps) else color_maps[i])
+                            for i in range(a, b)])
+            if col.shape[1:] != (H, W, 3):
+                raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape[1:]}")
+            col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))).to(dev)
+        P = poses[a:b].to(dev)
+        ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
+                           depth_min=depth_min, depth_max=depth_max)
+        ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
+                              depth_max=depth_max)
+    res = ops.resolve_voxel_labels(votes, min_votes)
+    return {"volume": vol, "votes": votes, "labels": res["label"], "total": res["total"],
+            "winner": res["winner"], "dims": tuple(dims),
+            "observed": float((vol["weight"] >= 1.0).float().mean()),
+            "labelled": float((res["label"] > 0).float().mean())}
+
+
+def render_voxel_map(volume, voxel_labels, poses, intrinsics, H, W, near, far, step=None,
+                     min_weight=1.0, batch=16):
+    """Yields (first view index, ``ops.raycast_tsdf`` dict of device tensors) for
+    the views in batches of ``batch``."""
+    dev = volume["tsdf"].device
+    poses = torch.as_tensor(np.asarray(poses, np.float32)).reshape(-1, 4, 4)
+    for a in range(0, poses.shape[0], batch):
+        yield a, ops.raycast_tsdf(volume, poses[a:a + batch].to(dev), intrinsics, H, W, near,
+                                  far, step=step, min_weight=min_weight,
+                                  voxel_labels=voxel_labels)
