@@ -1561,6 +1561,85 @@ int32_t ucsa_tsdf_raycast(const float* tsdf, const float* weight, const float* r
                           int32_t* label, uint64_t max_pixels, void* workspace,
                           uint64_t workspace_bytes, uint32_t flags, void* stream);
 
+/* ---- soft label fusion: per-class evidence sums (not in the reference) -----
+ * The soft sibling of the two hard-vote paths above.  A pixel's belief is a row
+ * of C uint8 evidence codes, e_c = 255 - rint(255 * min(-ln p_c, 8) / 8)
+ * (ops.log_evidence: p = 1 gives 255, p <= e^-8 gives 0); a sum of codes over
+ * views is the clamped log-likelihood sum, scaled by 255/8 and shifted by a
+ * constant, and its argmax is the MAP class under independent views and a
+ * uniform prior.  An ALL-ZERO row means "this pixel abstains" (no softmax over
+ * C <= 255 classes produces one).  scores is pixel-major, [B,H,W,C] uint8: the
+ * C codes of a pixel are C consecutive bytes at scores + pixel*C, at any
+ * alignment.  Everything is integer adds; tests/evidence_numpy.py restates the
+ * three contracts and the outputs match it bit for bit.
+ *
+ * ucsa_tsdf_evidence: B views add into evidence [C+1][nx][ny][nz] uint32,
+ *   class-major, allocated AND zeroed by the caller, accumulated over calls.
+ *   Plane c (1..C) is the evidence sum of class c, plane 0 the number of
+ *   (view, voxel) contributions.  Lattice, depth, poses, intrinsics as for
+ *   ucsa_tsdf_integrate.  Per voxel, for b = 0..B-1: the pixel and the band of
+ *   ucsa_tsdf_vote verbatim (the projection of ucsa_tsdf_integrate, z finite
+ *   and depth_min <= z <= depth_max, -trunc <= z - c_z <= trunc); the voxel
+ *   takes the row of that pixel iff the row is not all zero, and then
+ *     evidence[c][voxel] = min(evidence[c][voxel] + row[c-1], 2^32-1), c = 1..C,
+ *     evidence[0][voxel] = min(evidence[0][voxel] + 1, 2^32-1).
+ *   Independent of the TSDF state.  One thread owns a voxel: no atomics;
+ *   saturating adds of non-negative numbers commute, so every split and every
+ *   order of the views over calls gives the same bytes, and so do two runs.
+ *   Within a launch (up to 32 views) a thread carries its running sums in
+ *   registers, 40 classes at a time (8 when C <= 8; for C > 40 the views are
+ *   walked once per group of 40 classes), and reads and writes its C+1 table
+ *   entries once, and only if a view of the launch contributed: a voxel that no
+ *   view of the call reaches in its band is neither read nor written, so a call
+ *   costs the band, not the volume.  A work-group skips a view for its whole
+ *   1x4x64 brick by ucsa_tsdf_integrate's corner test.  A row is fetched as the
+ *   aligned 32-bit words that hold a byte of it (never a word wholly outside
+ *   the row).
+ *   Limits as for ucsa_tsdf_vote: dims (arguments 3..5), 1 <= C <= 255
+ *   (argument 2), (C+1)*nx*ny*nz <= 2^40 and evidence_capacity (uint32
+ *   elements) >= that (argument 1), B*H*W*C <= 2^40 (argument 9); an argument
+ *   error comes before any launch and nothing is written.
+ * ucsa_voxel_evidence_resolve: per voxel x of n_voxels, s_c = evidence[c][x]:
+ *   views[x] = evidence[0][x]; best[x] = max of s_c over c = 1..C; margin[x] =
+ *   best[x] minus the largest s_c over the other classes (the runner-up; for
+ *   C = 1 margin = best); label[x] (uint8) = the lowest c with s_c == best[x]
+ *   if views[x] >= min_views and margin[x] >= min_margin, else 0.
+ *   min_views >= 1.  label feeds ucsa_tsdf_raycast's voxel_labels.  The planes
+ *   are read one after the other, coalesced; no atomics.  The four outputs hold
+ *   max_voxels >= n_voxels elements each.
+ * ucsa_label_fuse_evidence: N pixels add into votes [V][C+1] uint64, the table
+ *   of ucsa_label_fuse_accumulate (column 0 is never touched).  Pixel i adds
+ *   iff 1 <= vertex_id[i] <= V and it passes the optional depth gate of
+ *   ucsa_label_fuse_accumulate (same rule, same arguments), and then
+ *     votes[vertex_id[i]-1][c] += scores[i*C + c-1]   for c = 1..C
+ *   (an all-zero row adds nothing: it abstains).  ucsa_label_fuse_resolve reads
+ *   the table as it is; min_votes is then in evidence units.  Sums are uint64,
+ *   integer adds commute: the table does not depend on the order or grouping of
+ *   pixels or calls.  row_width is the scheduling hint of
+ *   ucsa_label_fuse_accumulate: a wave takes a 16x16 pixel tile as four 8x8
+ *   patches and, per distinct vertex of the tile, walks the pixels that hold it
+ *   with lane l summing classes l+1, l+65, ... (one coalesced read of the row
+ *   per pixel), then issues ONE 64-bit integer atomic add per class with a
+ *   non-zero sum: a wave wholly on one wall issues C atomics, not 256*C.
+ *   Limits: those of ucsa_label_fuse_accumulate; an argument error comes before
+ *   any launch.  V == 0 or N == 0: returns 0, launches nothing. */
+int32_t ucsa_tsdf_evidence(uint32_t* evidence, uint64_t evidence_capacity, uint32_t C,
+                           uint32_t nx, uint32_t ny, uint32_t nz, const float* origin3,
+                           const float* spacing3, const float* depth,
+                           const uint8_t* scores, const float* poses, uint32_t B, float fx,
+                           float fy, float cx, float cy, uint32_t H, uint32_t W,
+                           float trunc, float depth_min, float depth_max, void* stream);
+int32_t ucsa_voxel_evidence_resolve(const uint32_t* evidence, uint32_t C,
+                                    uint64_t n_voxels, uint32_t min_views,
+                                    uint32_t min_margin, uint8_t* label, uint32_t* views,
+                                    uint32_t* best, uint32_t* margin, uint64_t max_voxels,
+                                    void* stream);
+int32_t ucsa_label_fuse_evidence(const int32_t* vertex_id, const uint8_t* scores,
+                                 const float* mesh_depth, const float* sensor_depth,
+                                 float depth_tol, uint64_t N, uint32_t row_width,
+                                 uint32_t V, uint32_t C, uint64_t* votes,
+                                 uint64_t votes_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

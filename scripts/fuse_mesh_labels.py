@@ -7,7 +7,7 @@ sibling of ``scripts/render_mesh_labels.py``, which goes the other way.
     python scripts/fuse_mesh_labels.py --scene_root <root>/<scene> --mesh M.ply \\
         [--pose_frame] --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] \\
         [--depth_tol METRES] [--min_votes K] [--every N] --out FUSED.ply \\
-        [--render] [--score]
+        [--render] [--score] [--scores {seg_evidence,<dir>} [--min_margin M]]
 
 ``--labels``: ``label_40`` is ``<scene>/label_40``; ``seg_label`` / ``nerf_label``
 are ``<scene>/<exp_name>/...`` (the predict pass's output); anything else is a
@@ -25,7 +25,14 @@ and the tolerance as ``float32(METRES * one_m_to_scene_uom)``.
 ``map_label/<stem>.png`` (uint8) under ``--out_dir`` (default: ``<scene>/<exp_name>``
 or the scene root).  ``--score`` (implies ``--render``) scores ``map_label`` and
 the input label maps against ``label_40``: one JSON line with the input mIoU
-next to the fused one."""
+next to the fused one.
+``--scores DIR`` fuses soft instead (``ops.fuse_label_evidence``): DIR holds
+``<stem>.npy``, uint8 evidence codes ``[C,H,W]`` or ``[H,W,C]``
+(``ops.log_evidence``; ``seg_evidence`` is ``<scene>/<exp_name>/seg_evidence``).
+A vertex's label is the class with the largest evidence sum; ``--min_votes`` is
+then the least total in evidence units and ``--min_margin`` the least lead of
+the winner over the runner-up.  ``--labels`` is then not fused; if given it
+names the maps scored as the input (default: the argmax of the score maps)."""
 import argparse
 import json
 import os
@@ -48,8 +55,12 @@ def parse_args(argv=None):
     p.add_argument("--mesh", required=True, help="mesh to label (.ply)")
     p.add_argument("--pose_frame", action="store_true",
                    help="the mesh is in the JSON pose frame, in metres")
-    p.add_argument("--labels", required=True,
+    p.add_argument("--labels", default=None,
                    help="seg_label | nerf_label | label_40 | a directory of <stem>.png")
+    p.add_argument("--scores", default=None,
+                   help="fuse evidence instead: seg_evidence | a directory of <stem>.npy")
+    p.add_argument("--min_margin", type=int, default=0,
+                   help="with --scores: least lead over the runner-up, evidence units")
     p.add_argument("--exp_name", default=None)
     p.add_argument("--depth_tol", type=float, default=None, help="metres")
     p.add_argument("--min_votes", type=int, default=1)
@@ -75,11 +86,34 @@ def label_dir(a):
     return a.labels
 
 
+def score_dir(a):
+    if a.scores == "seg_evidence":
+        if a.exp_name is None:
+            raise SystemExit("--scores seg_evidence reads <scene>/<exp_name>/seg_evidence: "
+                             "give --exp_name")
+        return os.path.join(a.scene_root, a.exp_name, a.scores)
+    return a.scores
+
+
+def codes_argmax(codes, H, W):
+    """the label map [H,W] uint8 that a view of evidence codes stands for: its
+    largest code's class, 0 where the row abstains"""
+    if codes.shape[:2] != (H, W):
+        codes = codes.transpose(1, 2, 0)
+    return np.where(codes.any(-1), codes.argmax(-1) + 1, 0).astype(np.uint8)
+
+
 def main(argv=None):
     from PIL import Image
     a = parse_args(argv)
     if a.every < 1 or a.min_votes < 1:
         raise SystemExit("--every and --min_votes must be >= 1")
+    if a.labels is None and a.scores is None:
+        raise SystemExit("give --labels, or --scores to fuse evidence")
+    if a.min_margin and a.scores is None:
+        raise SystemExit("--min_margin goes with --scores")
+    if a.min_margin < 0:
+        raise SystemExit("--min_margin must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -88,20 +122,27 @@ def main(argv=None):
     H, W = fr["H"], fr["W"]
     raw = read_ply(a.mesh)
     mesh = load_mesh(a.mesh, pose_frame=a.pose_frame, one_m_to_scene_uom=uom)
-    src = label_dir(a)
+    src = None if a.labels is None else label_dir(a)
+    ssrc = None if a.scores is None else score_dir(a)
 
     def png(folder, i):
         return np.asarray(Image.open(os.path.join(folder, stems[i] + ".png")))
+
+    def codes(i):
+        return np.load(os.path.join(ssrc, stems[i] + ".npy"))
 
     def depth(i):
         mm = png(os.path.join(a.scene_root, "depth"), i)
         return (mm.astype(np.float32) / np.float32(1000.0)) * np.float32(uom)
 
     gated = a.depth_tol is not None
-    fused = fuse_views(mesh, poses, fr["intrinsics"], H, W, a.near, lambda i: png(src, i),
+    soft = ssrc is not None
+    fused = fuse_views(mesh, poses, fr["intrinsics"], H, W, a.near,
+                       None if soft else (lambda i: png(src, i)),
                        depth_maps=depth if gated else None,
                        depth_tol=float(np.float32(a.depth_tol * uom)) if gated else None,
-                       num_classes=a.num_classes, batch=a.batch, min_votes=a.min_votes)
+                       num_classes=a.num_classes, batch=a.batch, min_votes=a.min_votes,
+                       **({"score_maps": codes, "min_margin": a.min_margin} if soft else {}))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     write_ply(a.out, raw["verts"], raw["faces"], normals=raw.get("normals"),
               rgb=raw.get("rgb"), labels=fused["labels"])
@@ -110,6 +151,8 @@ def main(argv=None):
            "faces": int(mesh["faces"].shape[0]), "observed": fused["observed"],
            "fuse_ms_per_view": {"rasterize": round(fused["rasterize_ms"] / max(n, 1), 3),
                                 "accumulate": round(fused["accumulate_ms"] / max(n, 1), 3)}}
+    if soft:
+        rec["scores"] = ssrc
     if a.render or a.score:
         out_dir = a.out_dir or os.path.join(a.scene_root, a.exp_name or "")
         os.makedirs(os.path.join(out_dir, "map_label"), exist_ok=True)
@@ -124,7 +167,8 @@ def main(argv=None):
         rec["map_label"] = os.path.join(out_dir, "map_label")
         if a.score:
             truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
-            given = np.stack([png(src, i) for i in range(n)])
+            given = np.stack([png(src, i) if src is not None else
+                              codes_argmax(codes(i), H, W) for i in range(n)])
             rec["input"] = score_label_maps(given, truth, a.num_classes)
             rec["fused"] = score_label_maps(np.concatenate(maps), truth, a.num_classes)
     print(json.dumps(rec))

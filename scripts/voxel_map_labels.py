@@ -8,7 +8,8 @@ voxel-route sibling of ``fuse_tsdf_mesh.py`` + ``fuse_mesh_labels.py --render``.
     python scripts/voxel_map_labels.py --scene_root <root>/<scene> \\
         --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] --out_dir D \\
         [--voxel METRES] [--trunc METRES] [--step METRES] [--every N] \\
-        [--min_votes K] [--aabb x0 y0 z0 x1 y1 z1] [--score]
+        [--min_votes K] [--aabb x0 y0 z0 x1 y1 z1] [--score] \\
+        [--scores {seg_evidence,<dir>} [--min_margin M]]
 
 Writes ``D/map_label/<stem>.png`` (uint8 NYU40 id, 0 = nothing) and
 ``D/map_depth/<stem>.png`` (uint16 millimetres, 0 = nothing; the layout of
@@ -17,7 +18,15 @@ transforms_train.json that were used (every ``--every``-th).  ``--labels`` as
 for ``fuse_mesh_labels.py``.  The volume is ``--aabb`` (NGP frame, scene units)
 or the box of the back-projected depth points padded by the truncation
 distance.  ``--score`` scores ``map_label`` and the input label maps against
-``label_40``: one JSON line with the input mIoU next to the voxel map's."""
+``label_40``: one JSON line with the input mIoU next to the voxel map's.
+``--scores DIR`` fuses soft instead (``ops.accumulate_voxel_evidence``): DIR
+holds ``<stem>.npy``, uint8 evidence codes ``[C,H,W]`` or ``[H,W,C]``
+(``ops.log_evidence``; ``seg_evidence`` is ``<scene>/<exp_name>/seg_evidence``,
+the predict pass's output), a voxel's label is the class with the largest
+evidence sum, ``--min_votes`` counts contributing views and ``--min_margin`` is
+the least lead over the runner-up in evidence units.  ``--labels`` is then not
+fused; if given it names the maps scored as the input (default: the argmax of
+the score maps)."""
 import argparse
 import json
 import os
@@ -39,8 +48,12 @@ from ucsa_neural_rendering_amd.utils.voxel_map import (  # noqa: E402
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--scene_root", required=True, help="<root>/<scene>")
-    p.add_argument("--labels", required=True,
+    p.add_argument("--labels", default=None,
                    help="seg_label | nerf_label | label_40 | a directory of <stem>.png")
+    p.add_argument("--scores", default=None,
+                   help="fuse evidence instead: seg_evidence | a directory of <stem>.npy")
+    p.add_argument("--min_margin", type=int, default=0,
+                   help="with --scores: least lead over the runner-up, evidence units")
     p.add_argument("--exp_name", default=None)
     p.add_argument("--out_dir", required=True, help="where map_label/ and map_depth/ go")
     p.add_argument("--voxel", type=float, default=0.04, help="metres")
@@ -71,21 +84,48 @@ def label_dir(a):
     return a.labels
 
 
+def score_dir(a):
+    if a.scores == "seg_evidence":
+        if a.exp_name is None:
+            raise SystemExit("--scores seg_evidence reads <scene>/<exp_name>/seg_evidence: "
+                             "give --exp_name")
+        return os.path.join(a.scene_root, a.exp_name, a.scores)
+    return a.scores
+
+
+def codes_argmax(codes, H, W):
+    """the label map [H,W] uint8 that a view of evidence codes stands for: its
+    largest code's class, 0 where the row abstains"""
+    if codes.shape[:2] != (H, W):
+        codes = codes.transpose(1, 2, 0)
+    return np.where(codes.any(-1), codes.argmax(-1) + 1, 0).astype(np.uint8)
+
+
 def main(argv=None):
     from PIL import Image
     a = parse_args(argv)
     if a.every < 1 or a.min_votes < 1 or a.batch < 1:
         raise SystemExit("--every, --min_votes and --batch must be >= 1")
+    if a.labels is None and a.scores is None:
+        raise SystemExit("give --labels, or --scores to fuse evidence")
+    if a.min_margin and a.scores is None:
+        raise SystemExit("--min_margin goes with --scores")
+    if a.min_margin < 0:
+        raise SystemExit("--min_margin must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
     stems = [fr["stems"][i] for i in keep]
     poses = fr["poses"][keep]
     H, W = fr["H"], fr["W"]
-    src = label_dir(a)
+    src = None if a.labels is None else label_dir(a)
+    ssrc = None if a.scores is None else score_dir(a)
 
     def png(folder, i):
         return np.asarray(Image.open(os.path.join(folder, stems[i] + ".png")))
+
+    def codes(i):
+        return np.load(os.path.join(ssrc, stems[i] + ".npy"))
 
     def depth(i):
         mm = png(os.path.join(a.scene_root, "depth"), i)
@@ -93,11 +133,13 @@ def main(argv=None):
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    fused = fuse_semantic_views(poses, fr["intrinsics"], H, W, depth, lambda i: png(src, i),
+    soft = {} if ssrc is None else {"score_maps": codes, "min_margin": a.min_margin}
+    fused = fuse_semantic_views(poses, fr["intrinsics"], H, W, depth,
+                                None if soft else (lambda i: png(src, i)),
                                 aabb=a.aabb, voxel=a.voxel * uom,
                                 trunc=None if a.trunc is None else a.trunc * uom,
                                 batch=a.batch, num_classes=a.num_classes,
-                                min_votes=a.min_votes)
+                                min_votes=a.min_votes, **soft)
     torch.cuda.synchronize()
     t_fuse = time.perf_counter() - t0
     vol = fused["volume"]
@@ -132,9 +174,12 @@ def main(argv=None):
            "observed": round(fused["observed"], 4), "labelled": round(fused["labelled"], 4),
            "fuse_ms_per_view": round(1e3 * t_fuse / max(n, 1), 3),
            "raycast_ms_per_view": round(1e3 * t_cast / max(n, 1), 3)}
+    if soft:
+        rec["scores"] = ssrc
     if a.score:
         truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
-        given = np.stack([png(src, i) for i in range(n)])
+        given = np.stack([png(src, i) if src is not None else codes_argmax(codes(i), H, W)
+                          for i in range(n)])
         rec["input"] = score_label_maps(given, truth, a.num_classes)
         rec["voxel_map"] = score_label_maps(np.concatenate(maps), truth, a.num_classes)
     print(json.dumps(rec))

@@ -331,6 +331,14 @@ SIGNATURES = {
                                       C.POINTER(_f), _p, _u32, _f, _f, _f, _f, _u32, _u32,
                                       _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, C.c_uint64,
                                       _p, C.c_uint64, _u32, _p]),
+    # ---- soft label fusion (per-class evidence sums, voxel map and mesh) ----
+    "ucsa_tsdf_evidence": (C.c_int32, [_p, C.c_uint64, _u32, _u32, _u32, _u32, C.POINTER(_f),
+                                       C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f, _u32,
+                                       _u32, _f, _f, _f, _p]),
+    "ucsa_voxel_evidence_resolve": (C.c_int32, [_p, _u32, C.c_uint64, _u32, _u32, _p, _p, _p,
+                                                _p, C.c_uint64, _p]),
+    "ucsa_label_fuse_evidence": (C.c_int32, [_p, _p, _p, _p, _f, C.c_uint64, _u32, _u32, _u32,
+                                             _p, C.c_uint64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -20,6 +20,14 @@
 //                  tools/label_fusion_time.py; same table.
 // k_lf_resolve     one wave per vertex row, lane c-1 reads class c (coalesced),
 //                  wave reduction of (sum, class) and of the total.
+// k_lf_evidence    the soft sibling (ucsa_label_fuse_evidence): a pixel adds a
+//                  row of C bytes to its vertex's row.  Same tiles and the same
+//                  leader loop over the distinct vertices of a wave; the pixels
+//                  of one vertex are then walked one by one with the classes
+//                  across the lanes (one coalesced read of C bytes each), and
+//                  the sums go out as one atomic per class, C lanes to an
+//                  instruction: a wave on one wall issues C atomics for 256
+//                  pixels, a wave of 256 vertices what one row per pixel costs.
 // Only 64-bit integer atomic adds, no float atomics, no LDS.
 #include <cmath>
 
@@ -122,6 +130,82 @@ k_lf_accumulate(LfArgs a, unsigned long long* __restrict__ votes) {
     if ((alone >> j) & 1u) atomicAdd(votes + key[j], (unsigned long long)w[j]);
 }
 
+// ---- evidence (soft votes): a row of C codes per pixel -----------------------
+struct LeArgs {
+  const int32_t* vid;
+  const uint8_t* scores;
+  const float* mesh_z;
+  const float* sensor_z;
+  float tol;
+  uint32_t N, W, V, C, tilesX, tiles;
+};
+
+constexpr uint32_t LE_STRIDES = 4;  // lane l sums classes l + 64 q: C <= 255
+
+// index of the pixel that slot j of lane l holds; a.N and beyond: none
+__device__ __forceinline__ uint64_t le_pixel(const LeArgs& a, uint32_t tx, uint32_t ty,
+                                             uint32_t j, uint32_t l) {
+  const uint32_t px = tx * LF_TILE + (j & 1u) * 8u + (l & 7u);
+  const uint64_t row = (uint64_t)ty * LF_TILE + (j >> 1) * 8u + (l >> 3);
+  const uint64_t i = row * a.W + px;
+  return px < a.W && i < a.N ? i : (uint64_t)a.N;
+}
+
+__global__ void __launch_bounds__(LF_WAVES * UCSA_WAVE)
+k_lf_evidence(LeArgs a, unsigned long long* __restrict__ votes) {
+  const uint32_t lane = threadIdx.x & (UCSA_WAVE - 1);
+  const uint32_t tile = blockIdx.x * LF_WAVES + threadIdx.x / UCSA_WAVE;
+  if (tile >= a.tiles) return;  // whole waves leave: every ballot below sees 64 lanes
+  const uint32_t ty = tile / a.tilesX, tx = tile - ty * a.tilesX;
+  uint32_t key[LF_SLOTS];  // the pixel's vertex, 0-based
+  unsigned long long todo[LF_SLOTS];
+#pragma unroll
+  for (uint32_t j = 0; j < LF_SLOTS; ++j) {
+    const uint64_t i = le_pixel(a, tx, ty, j, lane);
+    key[j] = LF_NONE;
+    if (i < a.N) {
+      const int32_t v = a.vid[i];
+      bool ok = v >= 1 && (uint32_t)v <= a.V;
+      if (a.mesh_z) {
+        const float s = a.sensor_z[i];
+        ok = ok && s > 0.0f && fabsf(a.mesh_z[i] - s) <= a.tol;
+      }
+      if (ok) key[j] = (uint32_t)(v - 1);
+    }
+    todo[j] = __ballot(key[j] != LF_NONE);
+  }
+#pragma unroll
+  for (uint32_t s = 0; s < LF_SLOTS; ++s) {
+    // slots below s are drained, and with them every vertex they held
+    while (todo[s]) {
+      const uint32_t lead = (uint32_t)__ffsll((long long)todo[s]) - 1u;
+      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key[s], (int)lead);
+      uint32_t sum[LE_STRIDES] = {0u, 0u, 0u, 0u};  // at most 256 * 255 each
+#pragma unroll
+      for (uint32_t j = s; j < LF_SLOTS; ++j) {
+        unsigned long long m = __ballot(key[j] == k);
+        todo[j] &= ~m;
+        while (m) {  // the pixels of vertex k, one after the other: uniform
+          const uint32_t l = (uint32_t)__ffsll((long long)m) - 1u;
+          m &= m - 1ull;
+          const uint8_t* __restrict__ row = a.scores + le_pixel(a, tx, ty, j, l) * a.C;
+#pragma unroll
+          for (uint32_t q = 0; q < LE_STRIDES; ++q) {
+            const uint32_t c = lane + q * UCSA_WAVE;
+            if (c < a.C) sum[q] += row[c];
+          }
+        }
+      }
+      unsigned long long* __restrict__ out = votes + (size_t)k * (a.C + 1u) + 1u;
+#pragma unroll
+      for (uint32_t q = 0; q < LE_STRIDES; ++q) {
+        const uint32_t c = lane + q * UCSA_WAVE;
+        if (c < a.C && sum[q] != 0u) atomicAdd(out + c, (unsigned long long)sum[q]);
+      }
+    }
+  }
+}
+
 struct LfBest {
   unsigned long long sum;
   uint32_t cls;
@@ -205,6 +289,42 @@ extern "C" int32_t ucsa_label_fuse_accumulate(const int32_t* vertex_id, const ui
     hipLaunchKernelGGL(k_lf_accumulate<true>, grid, block, 0, s, a, (unsigned long long*)votes);
   else
     hipLaunchKernelGGL(k_lf_accumulate<false>, grid, block, 0, s, a, (unsigned long long*)votes);
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_label_fuse_evidence(const int32_t* vertex_id, const uint8_t* scores,
+                                            const float* mesh_depth, const float* sensor_depth,
+                                            float depth_tol, uint64_t N, uint32_t row_width,
+                                            uint32_t V, uint32_t C, uint64_t* votes,
+                                            uint64_t votes_capacity, void* stream) {
+  UCSA_CHECK_ARG(C >= 1 && C <= 255, 8);
+  UCSA_CHECK_ARG((uint64_t)V * (C + 1u) <= 0x7FFFFFFFull, 7);
+  UCSA_CHECK_ARG(N <= 0x7FFFFFFFull, 5);
+  UCSA_CHECK_ARG((mesh_depth == nullptr) == (sensor_depth == nullptr), mesh_depth ? 3 : 2);
+  UCSA_CHECK_ARG(!mesh_depth || depth_tol >= 0.0f, 4);
+  if (V == 0 || N == 0) return 0;
+  UCSA_CHECK_ARG(vertex_id, 0);
+  UCSA_CHECK_ARG(scores, 1);
+  UCSA_CHECK_ARG(votes, 9);
+  UCSA_CHECK_ARG(votes_capacity >= (uint64_t)V * (C + 1u), 10);
+  LeArgs a;
+  a.vid = vertex_id;
+  a.scores = scores;
+  a.mesh_z = mesh_depth;
+  a.sensor_z = sensor_depth;
+  a.tol = depth_tol;
+  a.N = (uint32_t)N;
+  a.W = row_width == 0 ? LF_TILE : row_width;
+  if (a.W > a.N) a.W = a.N;
+  a.V = V;
+  a.C = C;
+  const uint32_t rows = ucsa_div_up(N, a.W);
+  a.tilesX = ucsa_div_up(a.W, LF_TILE);
+  a.tiles = a.tilesX * ucsa_div_up(rows, LF_TILE);
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_lf_evidence, dim3(ucsa_div_up(a.tiles, LF_WAVES)),
+                     dim3(LF_WAVES * UCSA_WAVE), 0, (hipStream_t)stream, a,
+                     (unsigned long long*)votes);
   return ucsa_launch_status();
 }
 

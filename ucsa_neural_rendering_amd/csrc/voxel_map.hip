@@ -14,6 +14,16 @@
 //                 read-modify-write) when the class changes: a voxel that every
 //                 view labels alike costs one flush per launch.
 // k_voxel_resolve one thread per voxel, the planes read one after the other.
+// k_tsdf_evidence the soft sibling of k_tsdf_vote (ucsa_tsdf_evidence), same
+//                 bricks and cull: a voxel adds the row of C evidence bytes of
+//                 its pixel to uint32 sums.  CT sums at a time live in
+//                 registers through the views of a launch (CT = 8 or 40; for
+//                 C > 40 the views are walked once per 40 classes, the first
+//                 walk recording which views count) and go out as one
+//                 saturating read-modify-write per plane, only for a voxel
+//                 that a view reached.  A row is fetched as the aligned words
+//                 that hold it and shifted into place.
+// k_evidence_resolve  argmax, runner-up margin and view count per voxel.
 // k_rc_mark       one work-group per brick of 8^3 cells, one thread per cell:
 //                 marks[brick] = 1 iff a cell of it has eight valid corners, one
 //                 of them <= RC_MARK_EPS.
@@ -139,6 +149,180 @@ __global__ void __launch_bounds__(256) k_voxel_resolve(const uint16_t* __restric
   label[x] = (uint8_t)(sum >= min_votes ? arg : 0u);
   total[x] = sum;
   winner[x] = best;
+}
+
+// ---- evidence (soft votes) ---------------------------------------------------
+struct EvArgs {
+  uint32_t* ev;
+  const float* depth;
+  const uint8_t* scores;
+  const float* poses;
+  uint32_t nx, ny, nz, B, H, W, C;
+  float o[3], h[3];
+  float fx, fy, cx, cy, trunc, dmin, dmax;
+};
+
+__device__ __forceinline__ uint32_t ev_sat_add(uint32_t x, uint32_t y) {
+  const uint32_t s = x + y;
+  return s < x ? 0xFFFFFFFFu : s;
+}
+
+// the pixel that view b gives the voxel at p under k_tsdf_vote's rule; false: none
+__device__ __forceinline__ bool ev_pixel(const EvArgs& a, uint32_t b, const float p[3],
+                                         size_t& pix) {
+  float c[3];
+  ts_camera(a.poses + 16u * b, p, c);
+  if (!(c[2] > 0.0f)) return false;
+  const float u = floorf((a.fx * c[0]) / c[2] + a.cx);
+  const float v = floorf((a.fy * c[1]) / c[2] + a.cy);
+  if (!(u >= 0.0f && u < (float)a.W && v >= 0.0f && v < (float)a.H)) return false;
+  pix = ((size_t)b * a.H + (uint32_t)v) * a.W + (uint32_t)u;
+  const float d = a.depth[pix];
+  if (!(isfinite(d) && d >= a.dmin && d <= a.dmax)) return false;
+  const float sdf = d - c[2];
+  return sdf >= -a.trunc && sdf <= a.trunc;
+}
+
+// Bytes [0, nc) of `row` (any alignment), nc <= 4*NW, as NW words with the
+// bytes past nc zeroed.  Only the aligned words that hold a byte of the row are
+// loaded, so nothing outside the words the row lives in is touched.
+template <uint32_t NW>
+__device__ __forceinline__ void ev_row(const uint8_t* row, uint32_t nc, const uint32_t msk[NW],
+                                       uint32_t w[NW]) {
+  const uintptr_t at = (uintptr_t)row;
+  const uint32_t sh = (uint32_t)(at & 3u);
+  const uint32_t* __restrict__ q = (const uint32_t*)(at - sh);
+  const uint32_t end = sh + nc;  // bytes from q to the row's end
+  uint32_t d[NW + 1];
+#pragma unroll
+  for (uint32_t i = 0; i <= NW; ++i) d[i] = 4u * i < end ? q[i] : 0u;
+#pragma unroll
+  for (uint32_t i = 0; i < NW; ++i)
+    w[i] = (uint32_t)((((uint64_t)d[i + 1] << 32) | d[i]) >> (8u * sh)) & msk[i];
+}
+
+// is any of the bytes [0, n) of `row` non-zero?
+__device__ __forceinline__ bool ev_any(const uint8_t* row, uint32_t n) {
+  const uintptr_t at = (uintptr_t)row;
+  const uint32_t sh = (uint32_t)(at & 3u);
+  const uint32_t* __restrict__ q = (const uint32_t*)(at - sh);
+  const uint32_t end = sh + n, words = (end + 3u) >> 2;
+  uint32_t any = 0u;
+  for (uint32_t i = 0; i < words; ++i) {
+    uint32_t x = q[i];
+    if (i == 0u) x &= 0xFFFFFFFFu << (8u * sh);
+    if (i + 1u == words && (end & 3u)) x &= 0xFFFFFFFFu >> (8u * (4u - (end & 3u)));
+    any |= x;
+  }
+  return any != 0u;
+}
+
+// CT: classes carried in registers at a time (a multiple of 4)
+template <uint32_t CT>
+__global__ void __launch_bounds__(VM_BK* VM_BJ) k_tsdf_evidence(EvArgs a) {
+  constexpr uint32_t NW = CT / 4u;
+  __shared__ float s_c[VM_MAXB][8][3];
+  __shared__ uint32_t s_cull;
+  const uint32_t tid = threadIdx.y * VM_BK + threadIdx.x;
+  const uint32_t i = blockIdx.z, j0 = blockIdx.y * VM_BJ, k0 = blockIdx.x * VM_BK;
+  const uint32_t j1 = min(j0 + VM_BJ - 1u, a.ny - 1u), k1 = min(k0 + VM_BK - 1u, a.nz - 1u);
+  float lo[3], hi[3];
+  lo[0] = hi[0] = a.o[0] + (float)i * a.h[0];
+  lo[1] = a.o[1] + (float)j0 * a.h[1];
+  hi[1] = a.o[1] + (float)j1 * a.h[1];
+  lo[2] = a.o[2] + (float)k0 * a.h[2];
+  hi[2] = a.o[2] + (float)k1 * a.h[2];
+#pragma unroll
+  for (int r = 1; r < 3; ++r) {
+    const float x = fminf(lo[r], hi[r]), y = fmaxf(lo[r], hi[r]);
+    lo[r] = x;
+    hi[r] = y;
+  }
+  if (tid == 0) s_cull = 0u;
+  if (tid < 8u * a.B) {
+    const uint32_t v = tid >> 3, q = tid & 7u;
+    const float p[3] = {lo[0], (q & 1u) ? hi[1] : lo[1], (q & 2u) ? hi[2] : lo[2]};
+    float c[3];
+    ts_camera(a.poses + 16u * v, p, c);
+    s_c[v][q][0] = c[0];
+    s_c[v][q][1] = c[1];
+    s_c[v][q][2] = c[2];
+  }
+  __syncthreads();
+  if (tid < a.B && ts_cull(a, a.poses + 16u * tid, lo, hi, s_c[tid])) atomicOr(&s_cull, 1u << tid);
+  __syncthreads();
+  const uint32_t cull = s_cull;
+
+  const uint32_t j = j0 + threadIdx.y, k = k0 + threadIdx.x;
+  if (j >= a.ny || k >= a.nz) return;
+  const size_t n = (size_t)a.nx * a.ny * a.nz;
+  const size_t idx = ((size_t)i * a.ny + j) * a.nz + k;
+  const float p[3] = {lo[0], a.o[1] + (float)j * a.h[1], a.o[2] + (float)k * a.h[2]};
+  uint32_t took = 0u;  // bit b: view b's row is added (set in the first pass)
+  for (uint32_t c0 = 0; c0 < a.C; c0 += CT) {  // uniform over the grid
+    const uint32_t nc = min(CT, a.C - c0);
+    uint32_t msk[NW];
+#pragma unroll
+    for (uint32_t q = 0; q < NW; ++q) {
+      const uint32_t r = nc > 4u * q ? nc - 4u * q : 0u;
+      msk[q] = r >= 4u ? 0xFFFFFFFFu : (1u << (8u * r)) - 1u;
+    }
+    uint32_t acc[CT];
+#pragma unroll
+    for (uint32_t c = 0; c < CT; ++c) acc[c] = 0u;
+    for (uint32_t b = 0; b < a.B; ++b) {
+      if ((cull >> b) & 1u) continue;  // uniform over the work-group
+      if (c0 != 0u && !((took >> b) & 1u)) continue;
+      size_t pix;
+      if (!ev_pixel(a, b, p, pix)) continue;
+      const uint8_t* row = a.scores + pix * a.C;
+      uint32_t w[NW];
+      ev_row<NW>(row + c0, nc, msk, w);
+      if (c0 == 0u) {
+        uint32_t any = 0u;
+#pragma unroll
+        for (uint32_t q = 0; q < NW; ++q) any |= w[q];
+        if (any == 0u && !(a.C > CT && ev_any(row + CT, a.C - CT))) continue;  // abstains
+        took |= 1u << b;
+      }
+#pragma unroll
+      for (uint32_t c = 0; c < CT; ++c) acc[c] += (w[c >> 2] >> (8u * (c & 3u))) & 0xFFu;
+    }
+    if (took == 0u) return;  // no view of the launch reaches the voxel: not touched
+    uint32_t* __restrict__ e = a.ev + (size_t)(c0 + 1u) * n + idx;
+#pragma unroll
+    for (uint32_t c = 0; c < CT; ++c)
+      if (c < nc) e[(size_t)c * n] = ev_sat_add(e[(size_t)c * n], acc[c]);
+  }
+  a.ev[idx] = ev_sat_add(a.ev[idx], (uint32_t)__popc(took));
+}
+
+__global__ void __launch_bounds__(256) k_evidence_resolve(const uint32_t* __restrict__ ev,
+                                                           uint32_t C, uint64_t n,
+                                                           uint32_t min_views,
+                                                           uint32_t min_margin,
+                                                           uint8_t* __restrict__ label,
+                                                           uint32_t* __restrict__ views,
+                                                           uint32_t* __restrict__ best_out,
+                                                           uint32_t* __restrict__ margin) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (x >= n) return;
+  uint32_t best = ev[n + x], second = 0u, arg = 1u;
+  for (uint32_t c = 2; c <= C; ++c) {
+    const uint32_t s = ev[(uint64_t)c * n + x];
+    if (s > best) {
+      second = best;
+      best = s;
+      arg = c;
+    } else if (s > second) {
+      second = s;
+    }
+  }
+  const uint32_t nv = ev[x], m = best - second;
+  label[x] = (uint8_t)(nv >= min_views && m >= min_margin ? arg : 0u);
+  views[x] = nv;
+  best_out[x] = best;
+  margin[x] = m;
 }
 
 // ---- ray-caster ------------------------------------------------------------
@@ -471,6 +655,97 @@ extern "C" int32_t ucsa_voxel_label_resolve(const uint16_t* votes, uint32_t C,
   UCSA_CLEAR_ERR();
   hipLaunchKernelGGL(k_voxel_resolve, dim3(ucsa_div_up(n_voxels, 256)), dim3(256), 0,
                      (hipStream_t)stream, votes, C, n_voxels, min_votes, label, total, winner);
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_tsdf_evidence(uint32_t* evidence, uint64_t evidence_capacity, uint32_t C,
+                                      uint32_t nx, uint32_t ny, uint32_t nz,
+                                      const float* origin3, const float* spacing3,
+                                      const float* depth, const uint8_t* scores,
+                                      const float* poses, uint32_t B, float fx, float fy,
+                                      float cx, float cy, uint32_t H, uint32_t W, float trunc,
+                                      float depth_min, float depth_max, void* stream) {
+  UCSA_CHECK_ARG(evidence, 0);
+  UCSA_CHECK_ARG(C >= 1 && C <= 255, 2);
+  UCSA_CHECK_ARG(nx >= 2 && (uint64_t)nx * ny * nz <= 0x7FFFFFFFull, 3);
+  UCSA_CHECK_ARG(ny >= 2, 4);
+  UCSA_CHECK_ARG(nz >= 2, 5);
+  const uint64_t need = (uint64_t)(C + 1u) * ((uint64_t)nx * ny * nz);
+  UCSA_CHECK_ARG(need <= (1ull << 40) && evidence_capacity >= need, 1);
+  UCSA_CHECK_ARG(origin3, 6);
+  UCSA_CHECK_ARG(spacing3, 7);
+  UCSA_CHECK_ARG(depth, 8);
+  UCSA_CHECK_ARG(scores, 9);
+  UCSA_CHECK_ARG(poses, 10);
+  UCSA_CHECK_ARG(B >= 1, 11);
+  UCSA_CHECK_ARG(fx > 0.0f && std::isfinite(fx), 12);
+  UCSA_CHECK_ARG(fy > 0.0f && std::isfinite(fy), 13);
+  UCSA_CHECK_ARG(std::isfinite(cx), 14);
+  UCSA_CHECK_ARG(std::isfinite(cy), 15);
+  UCSA_CHECK_ARG(H >= 1 && H <= 16384, 16);
+  UCSA_CHECK_ARG(W >= 1 && W <= 16384, 17);
+  UCSA_CHECK_ARG((uint64_t)B * H * W * C <= (1ull << 40), 9);
+  UCSA_CHECK_ARG(trunc > 0.0f && std::isfinite(trunc), 18);
+  UCSA_CHECK_ARG(!std::isnan(depth_min), 19);
+  UCSA_CHECK_ARG(depth_max >= depth_min, 20);
+  const uint32_t gy = ucsa_div_up(ny, VM_BJ);
+  UCSA_CHECK_ARG(gy <= 65535u, 4);
+  UCSA_CHECK_ARG(nx <= 65535u, 3);
+  EvArgs a;
+  a.ev = evidence;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.H = H;
+  a.W = W;
+  a.C = C;
+  for (int r = 0; r < 3; ++r) {
+    a.o[r] = origin3[r];
+    a.h[r] = spacing3[r];
+  }
+  a.fx = fx;
+  a.fy = fy;
+  a.cx = cx;
+  a.cy = cy;
+  a.trunc = trunc;
+  a.dmin = depth_min;
+  a.dmax = depth_max;
+  const dim3 grid(ucsa_div_up(nz, VM_BK), gy, nx), block(VM_BK, VM_BJ);
+  hipStream_t s = (hipStream_t)stream;
+  UCSA_CLEAR_ERR();
+  for (uint32_t b0 = 0; b0 < B; b0 += VM_MAXB) {
+    a.B = B - b0 < VM_MAXB ? B - b0 : VM_MAXB;
+    a.depth = depth + (size_t)b0 * H * W;
+    a.scores = scores + (size_t)b0 * H * W * C;
+    a.poses = poses + 16 * (size_t)b0;
+    if (C <= 8u)
+      hipLaunchKernelGGL(k_tsdf_evidence<8>, grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL(k_tsdf_evidence<40>, grid, block, 0, s, a);
+  }
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_voxel_evidence_resolve(const uint32_t* evidence, uint32_t C,
+                                               uint64_t n_voxels, uint32_t min_views,
+                                               uint32_t min_margin, uint8_t* label,
+                                               uint32_t* views, uint32_t* best,
+                                               uint32_t* margin, uint64_t max_voxels,
+                                               void* stream) {
+  UCSA_CHECK_ARG(evidence, 0);
+  UCSA_CHECK_ARG(C >= 1 && C <= 255, 1);
+  UCSA_CHECK_ARG(n_voxels <= 0x7FFFFFFFull, 2);
+  UCSA_CHECK_ARG(min_views >= 1, 3);
+  UCSA_CHECK_ARG(label, 5);
+  UCSA_CHECK_ARG(views, 6);
+  UCSA_CHECK_ARG(best, 7);
+  UCSA_CHECK_ARG(margin, 8);
+  UCSA_CHECK_ARG(max_voxels >= n_voxels, 9);
+  if (n_voxels == 0) return 0;
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_evidence_resolve, dim3(ucsa_div_up(n_voxels, 256)), dim3(256), 0,
+                     (hipStream_t)stream, evidence, C, n_voxels, min_views, min_margin, label,
+                     views, best, margin);
   return ucsa_launch_status();
 }
 

@@ -145,6 +145,10 @@ class JointTrainLightningNet(nn.Module):
         self.automatic_optimization = False
         self.joint_train = False
         self.fix_nerf = exp.get("fix_nerf", False)
+        # opt-in: the predict pass also writes seg_evidence/<stem>.npy, the evidence
+        # codes of the segmentation softmax (ops.log_evidence) that
+        # scripts/voxel_map_labels.py and fuse_mesh_labels.py --scores fuse
+        self.write_seg_evidence = bool(exp.get("write_seg_evidence", False))
         self.root_new_scene = os.path.join(
             env.get("scannet", "."), str(exp["scenes"][-1]),
             str(exp.get("exp_name", "debug")))
@@ -657,7 +661,8 @@ class JointTrainLightningNet(nn.Module):
         self._mode = "predict"
         if self.predict_to_disk:
             for sub in ("", "novel_viewpoints"):
-                for name in ("nerf_image", "nerf_label", "seg_label"):
+                for name in ("nerf_image", "nerf_label", "seg_label") + \
+                        (("seg_evidence",) if self.write_seg_evidence else ()):
                     os.makedirs(os.path.join(self.root_new_scene, sub, name),
                                 exist_ok=True)
 
@@ -687,6 +692,12 @@ class JointTrainLightningNet(nn.Module):
                 for name in ("nerf_label", "seg_label"):
                     Image.fromarray(lab8[name][i]).save(os.path.join(
                         self.root_new_scene, sub, name, idx + ".png"))
+            if self.write_seg_evidence:
+                codes = ops.log_evidence(seg["seg_logits"].detach(), from_logits=True)
+                codes = codes.cpu().numpy()               # [B,H,W,C] uint8
+                for i, idx in enumerate(batch["current_index"]):
+                    np.save(os.path.join(self.root_new_scene, sub, "seg_evidence",
+                                         idx + ".npy"), codes[i])
         return res
 
     def on_predict_epoch_end(self):

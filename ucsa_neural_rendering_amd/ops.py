@@ -1744,7 +1744,9 @@ def resolve_label_votes(votes, min_votes: int = 1):
     """``votes`` [V, C+1] -> dict of device tensors: ``label`` [V] int32 (the
     class with the largest sum, ties to the lower id, 0 where the row's total
     is below ``min_votes``), ``total`` and ``winner`` [V] int64 (the bits of
-    uint64 sums; confidence = winner / total).  ucsa_label_fuse_resolve."""
+    uint64 sums; confidence = winner / total).  ucsa_label_fuse_resolve.  On a
+    table filled by ``fuse_label_evidence`` the sums are evidence sums and
+    ``min_votes`` is in evidence units (a confident view adds about 255)."""
     V, Cn = _vote_table(votes)
     min_votes = int(min_votes)
     if not 1 <= min_votes < 1 << 64:
@@ -1757,6 +1759,77 @@ def resolve_label_votes(votes, min_votes: int = 1):
                                         _ptr(out["total"]), _ptr(out["winner"]), V,
                                         _stream()), "ucsa_label_fuse_resolve")
     return out
+
+
+def log_evidence(x, from_logits: bool = False, floor_nats: float = 8.0):
+    """Class beliefs ``x`` [B,C,H,W] (probabilities, or logits with
+    ``from_logits``) -> evidence codes uint8 [B,H,W,C], pixel-major (the C
+    codes of a pixel are C consecutive bytes, as ``accumulate_voxel_evidence``
+    and ``fuse_label_evidence`` read them):
+    e_c = 255 - rint(255 * min(-ln p_c, L) / L) with L = ``floor_nats``: p = 1
+    gives 255, p <= e^-L gives 0.  A sum of codes over views is the clamped
+    log-likelihood sum scaled by 255 / L; an all-zero row means "abstain" and
+    cannot come out of a softmax over C <= 255 classes with L = 8.  Plain
+    torch in fp32 on x's device (elementwise plumbing; the HIP is in the
+    accumulation)."""
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.is_floating_point()):
+        raise _lib.UcsaError("log_evidence: x must be a floating-point tensor [B,C,H,W]")
+    if not 1 <= x.shape[1] <= 255:
+        raise _lib.UcsaError(f"log_evidence: 1 <= C <= 255, got {x.shape[1]}")
+    L = float(floor_nats)
+    if not (L > 0.0 and L < float("inf")):
+        raise _lib.UcsaError(f"log_evidence: floor_nats must be > 0 and finite, got {floor_nats}")
+    x = x.float()
+    nl = -(torch.log_softmax(x, dim=1) if from_logits else torch.log(x))
+    nl = torch.nan_to_num(nl, nan=L, posinf=L, neginf=0.0).clamp_(0.0, L)
+    e = 255.0 - torch.round(nl * 255.0 / L)
+    return e.to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def fuse_label_evidence(votes, vertex_id, scores, mesh_depth=None, sensor_depth=None,
+                        depth_tol=None):
+    """The soft form of ``fuse_label_votes``: pixels add their row of evidence
+    codes to their vertex's row of ``votes`` [V, C+1] int64 (the same table;
+    column 0 is left untouched), in place; returns ``votes``.  ``vertex_id``
+    int32 [...] as for ``fuse_label_votes``, ``scores`` uint8 [..., C]
+    (``log_evidence``; an all-zero row abstains), the optional depth gate as
+    for ``fuse_label_votes``.  A pixel with 1 <= vertex_id <= V that passes the
+    gate adds scores[pixel, c-1] to votes[vertex_id-1, c] for c = 1..C.
+    ``resolve_label_votes`` reads the table as it is; its ``min_votes`` is then
+    in evidence units.  Contract of ucsa_label_fuse_evidence
+    (include/ucsa_hip.h): integer sums, the same bytes whatever the order of
+    pixels and calls."""
+    V, Cn = _vote_table(votes)
+    if not torch.is_tensor(vertex_id):
+        raise _lib.UcsaError("vertex_id must be a GPU tensor")
+    n = vertex_id.numel()
+    vid = _fuse_input(vertex_id, "vertex_id", torch.int32, n)
+    if n > 0x7FFFFFFF:
+        raise _lib.UcsaError("fuse_label_evidence: at most 2^31-1 pixels per call")
+    if not (torch.is_tensor(scores) and scores.dim() >= 1
+            and tuple(scores.shape) == tuple(vertex_id.shape) + (Cn,)):
+        raise _lib.UcsaError(f"scores must be uint8 {list(vertex_id.shape) + [Cn]} (vertex_id's "
+                             "shape, then the table's C)")
+    sc = _fuse_input(scores, "scores", torch.uint8, n * Cn)
+    if (mesh_depth is None) != (sensor_depth is None):
+        raise _lib.UcsaError("mesh_depth and sensor_depth come as a pair")
+    md = sd = None
+    tol = 0.0
+    if mesh_depth is not None:
+        if depth_tol is None:
+            raise _lib.UcsaError("the depth gate needs depth_tol")
+        tol = float(depth_tol)
+        if not tol >= 0.0:
+            raise _lib.UcsaError(f"depth_tol must be >= 0, got {depth_tol}")
+        md = _fuse_input(mesh_depth, "mesh_depth", torch.float32, n)
+        sd = _fuse_input(sensor_depth, "sensor_depth", torch.float32, n)
+    elif depth_tol is not None:
+        raise _lib.UcsaError("depth_tol given without mesh_depth / sensor_depth")
+    row_width = int(vertex_id.shape[-1]) if vertex_id.dim() >= 2 else 0
+    check(lib().ucsa_label_fuse_evidence(
+        _ptr(vid), _ptr(sc), _ptr(md), _ptr(sd), tol, n, row_width, V, Cn, _ptr(votes),
+        votes.numel(), _stream()), "ucsa_label_fuse_evidence")
+    return votes
 
 
 # ---------------------------------------------------------------------------
@@ -1943,6 +2016,92 @@ def resolve_voxel_labels(votes, min_votes: int = 1):
     check(lib().ucsa_voxel_label_resolve(_ptr(votes), Cn, n, min_votes, _ptr(out["label"]),
                                          _ptr(out["total"]), _ptr(out["winner"]), n,
                                          _stream()), "ucsa_voxel_label_resolve")
+    return out
+
+
+def voxel_evidence(volume, n_classes: int):
+    """The zeroed evidence table of a ``tsdf_volume`` for
+    ``accumulate_voxel_evidence``: [C+1, nx, ny, nz] uint32, class-major; plane
+    c (1..C) is the evidence sum of class c, plane 0 the number of (view,
+    voxel) contributions.  Limits as for ``voxel_votes``."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    Cn = int(n_classes)
+    if not 1 <= Cn <= 255:
+        raise _lib.UcsaError(f"voxel_evidence: n_classes must be in 1..255, got {n_classes}")
+    if (Cn + 1) * nx * ny * nz > 1 << 40:
+        raise _lib.UcsaError("voxel_evidence: (C+1)*nx*ny*nz must be at most 2^40")
+    return torch.zeros(Cn + 1, nx, ny, nz, dtype=torch.uint32, device=dev)
+
+
+def _evidence_planes(evidence):
+    if not (torch.is_tensor(evidence) and evidence.is_cuda and evidence.dtype == torch.uint32
+            and evidence.is_contiguous()):
+        raise _lib.UcsaError("evidence must be a contiguous uint32 tensor on the GPU")
+    if evidence.dim() != 4 or not 2 <= evidence.shape[0] <= 256:
+        raise _lib.UcsaError(f"evidence must be [C+1,nx,ny,nz] with 1 <= C <= 255, got "
+                             f"{tuple(evidence.shape)}")
+    return int(evidence.shape[0]) - 1
+
+
+def accumulate_voxel_evidence(evidence, volume, depth, scores, poses, intrinsics, trunc: float,
+                              depth_min: float = 1e-6, depth_max: float = 3.0e38):
+    """The soft form of ``vote_voxel_labels``: B posed views add evidence into
+    ``evidence`` (``voxel_evidence``), in place; returns ``evidence``.
+    ``depth`` [B,H,W] f32, ``poses`` [B,4,4], ``intrinsics`` as for
+    ``integrate_tsdf``; ``scores`` [B,H,W,C] uint8 (``log_evidence``).  A voxel
+    takes the row of the pixel it projects to under exactly the rule of
+    ``vote_voxel_labels`` (the band |z - c_z| <= trunc) unless the row is all
+    zero, adds it to its C planes and 1 to plane 0; all adds saturate at
+    2^32-1.  A voxel that no view of the call reaches is neither read nor
+    written.  Contract of ucsa_tsdf_evidence (include/ucsa_hip.h): independent
+    of the TSDF state, and the same bytes for every split and order of the
+    views."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    Cn = _evidence_planes(evidence)
+    if tuple(evidence.shape[1:]) != (nx, ny, nz) or evidence.device != dev:
+        raise _lib.UcsaError(f"evidence must be [C+1,{nx},{ny},{nz}] on the volume's device, "
+                             f"got {tuple(evidence.shape)} on {evidence.device}")
+    depth = _f32(depth, "depth")
+    poses = _f32(poses, "poses")
+    if depth.dim() != 3:
+        raise _lib.UcsaError(f"depth must be [B,H,W], got {tuple(depth.shape)}")
+    B, H, W = (int(s) for s in depth.shape)
+    if poses.dim() != 3 or tuple(poses.shape) != (B, 4, 4):
+        raise _lib.UcsaError(f"poses must be [{B},4,4], got {tuple(poses.shape)}")
+    if depth.device != dev or poses.device != dev:
+        raise _lib.UcsaError("depth and poses must be on the volume's device")
+    scores = _u8_on(scores, "scores", (B, H, W, Cn), dev)
+    fx, fy, cx, cy = [float(v) for v in intrinsics]
+    check(lib().ucsa_tsdf_evidence(
+        _ptr(evidence), evidence.numel(), Cn, nx, ny, nz, fvec(volume["origin"]),
+        fvec(volume["spacing"]), _ptr(depth), _ptr(scores), _ptr(poses), B, fx, fy, cx, cy,
+        H, W, float(trunc), float(depth_min), float(depth_max), _stream()),
+        "ucsa_tsdf_evidence")
+    return evidence
+
+
+def resolve_voxel_evidence(evidence, min_views: int = 1, min_margin: int = 0):
+    """``evidence`` [C+1,nx,ny,nz] -> dict of device tensors [nx,ny,nz]:
+    ``label`` uint8 (the class with the largest evidence sum, ties to the lower
+    id, 0 where plane 0 < ``min_views`` or margin < ``min_margin``), ``views``
+    (plane 0), ``best`` and ``margin`` uint32 (best minus the runner-up; for
+    C = 1 it is best).  ``label`` feeds ``raycast_tsdf(voxel_labels=...)``.
+    ucsa_voxel_evidence_resolve."""
+    Cn = _evidence_planes(evidence)
+    min_views, min_margin = int(min_views), int(min_margin)
+    if not 1 <= min_views < 1 << 32:
+        raise _lib.UcsaError(f"min_views must be in 1..2^32-1, got {min_views}")
+    if not 0 <= min_margin < 1 << 32:
+        raise _lib.UcsaError(f"min_margin must be in 0..2^32-1, got {min_margin}")
+    shape, dev = tuple(evidence.shape[1:]), evidence.device
+    n = int(evidence[0].numel())
+    out = {"label": torch.empty(shape, dtype=torch.uint8, device=dev),
+           "views": torch.empty(shape, dtype=torch.uint32, device=dev),
+           "best": torch.empty(shape, dtype=torch.uint32, device=dev),
+           "margin": torch.empty(shape, dtype=torch.uint32, device=dev)}
+    check(lib().ucsa_voxel_evidence_resolve(
+        _ptr(evidence), Cn, n, min_views, min_margin, _ptr(out["label"]), _ptr(out["views"]),
+        _ptr(out["best"]), _ptr(out["margin"]), n, _stream()), "ucsa_voxel_evidence_resolve")
     return out
 
 

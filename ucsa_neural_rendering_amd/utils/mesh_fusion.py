@@ -8,8 +8,11 @@ Every pixel of every view votes for the mesh vertex that the rasterizer gives it
 (``ops.rasterize_mesh`` with ``vertex_labels = 1..V``: the nearest corner of the
 hit point) with its frame's class; ``ops.fuse_label_votes`` sums the votes in a
 uint64 table that stays on the device, ``ops.resolve_label_votes`` takes the
-majority.  Hard votes only.  Out of scope: soft (probability-vector) votes,
-filling unobserved vertices from their neighbours, voxel maps, registering a
+majority.  With ``score_maps`` (rows of evidence codes per pixel,
+``ops.log_evidence``) a pixel adds its row to its vertex instead
+(``ops.fuse_label_evidence``, same table) and the majority becomes the MAP
+class.  Out of scope: float probabilities on the device, priors,
+filling unobserved vertices from their neighbours, registering a
 mesh to the poses' frame (``load_mesh(..., pose_frame=True)`` covers the one
 rigid motion the project records), anything in the training loop."""
 from __future__ import annotations
@@ -33,9 +36,26 @@ def _batch(src, a, b, dtype, H, W, name):
     return torch.from_numpy(np.ascontiguousarray(arr.astype(dtype, copy=False)))
 
 
+def _score_batch(src, a, b, H, W, C):
+    """views a..b of ``src`` as one uint8 [b-a,H,W,C] tensor; a view is [H,W,C] or
+    [C,H,W], told apart by shape ([H,W,C] where both fit)"""
+    out = []
+    for i in range(a, b):
+        arr = np.asarray(_view(src, i))
+        if arr.dtype != np.uint8:
+            raise ValueError(f"score_maps: views must be uint8, got {arr.dtype}")
+        if arr.shape == (C, H, W) and arr.shape != (H, W, C):
+            arr = arr.transpose(1, 2, 0)
+        if arr.shape != (H, W, C):
+            raise ValueError(f"score_maps: views must be [{H},{W},{C}] or [{C},{H},{W}], got "
+                             f"{arr.shape}")
+        out.append(arr)
+    return torch.from_numpy(np.ascontiguousarray(np.stack(out)))
+
+
 def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
                depth_tol=None, weights=None, num_classes=40, batch=16, min_votes=1,
-               device="cuda"):
+               device="cuda", score_maps=None, min_margin=0):
     """``mesh``: dict with verts [V,3] f32 and faces [F,3] int32 in the poses'
     (NGP) frame (``load_mesh``); ``poses`` [N,4,4]; ``label_maps``: a sequence
     or a callable ``i -> [H,W]`` integer class ids per view (NYU40: 1..C vote,
@@ -46,7 +66,19 @@ def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
     in [0, 65535].  -> dict of numpy arrays ``labels`` [V] int32 (0 =
     unobserved or below ``min_votes``), ``total`` / ``winner`` [V] uint64,
     ``observed`` (count of labelled vertices), and the wall time split
-    ``rasterize_ms`` / ``accumulate_ms`` (device-synchronised host clock)."""
+    ``rasterize_ms`` / ``accumulate_ms`` (device-synchronised host clock).
+    With ``score_maps`` (``i -> [H,W,C]`` or ``[C,H,W]`` uint8 evidence codes,
+    C = ``num_classes``; ``label_maps`` is then not read and may be None,
+    ``weights`` must be None) a pixel adds its row of codes instead of one
+    vote; ``total`` / ``winner`` and ``min_votes`` are then in evidence units,
+    the dict carries ``margin`` [V] uint64 (the winner's lead over the
+    runner-up; the winner itself for one class) and a vertex whose margin is
+    below ``min_margin`` gets label 0."""
+    soft = score_maps is not None
+    if not soft and min_margin:
+        raise ValueError("min_margin applies to score_maps only")
+    if soft and weights is not None:
+        raise ValueError("weights apply to label_maps only")
     if (depth_maps is None) != (depth_tol is None):
         raise ValueError("depth_maps and depth_tol come as a pair")
     dev = torch.device(device)
@@ -65,26 +97,41 @@ def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
                                  vertex_labels=ids)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        lab = _batch(label_maps, a, b, np.int64, H, W, "label_maps")
-        # a class id outside uint8 cannot vote: map it to 0
-        pred = torch.where((lab >= 0) & (lab <= 255), lab, torch.zeros_like(lab)) \
-            .to(torch.uint8).to(dev)
+        if soft:
+            sc = _score_batch(score_maps, a, b, H, W, int(num_classes)).to(dev)
+        else:
+            lab = _batch(label_maps, a, b, np.int64, H, W, "label_maps")
+            # a class id outside uint8 cannot vote: map it to 0
+            pred = torch.where((lab >= 0) & (lab <= 255), lab, torch.zeros_like(lab)) \
+                .to(torch.uint8).to(dev)
         w = None if weights is None else \
             _batch(weights, a, b, np.int32, H, W, "weights").to(dev)
         sd = None if depth_maps is None else \
             _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        ops.fuse_label_votes(votes, out["label"], pred, weight=w,
-                             mesh_depth=None if sd is None else out["depth"],
-                             sensor_depth=sd, depth_tol=depth_tol)
+        if soft:
+            ops.fuse_label_evidence(votes, out["label"], sc,
+                                    mesh_depth=None if sd is None else out["depth"],
+                                    sensor_depth=sd, depth_tol=depth_tol)
+        else:
+            ops.fuse_label_votes(votes, out["label"], pred, weight=w,
+                                 mesh_depth=None if sd is None else out["depth"],
+                                 sensor_depth=sd, depth_tol=depth_tol)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         t_r += t1 - t0
         t_a += t3 - t2
     res = ops.resolve_label_votes(votes, min_votes)
+    extra = {}
+    if soft:
+        top = votes[:, 1:].topk(min(2, votes.shape[1] - 1), dim=1).values
+        margin = top[:, 0] - top[:, 1] if top.shape[1] == 2 else top[:, 0]
+        res["label"] = torch.where(margin >= int(min_margin), res["label"],
+                                   torch.zeros_like(res["label"]))
+        extra["margin"] = margin.cpu().numpy().view(np.uint64)
     labels = res["label"].cpu().numpy()
-    return {"labels": labels,
+    return {**extra, "labels": labels,
             "total": res["total"].cpu().numpy().view(np.uint64),
             "winner": res["winner"].cpu().numpy().view(np.uint64),
             "observed": int((labels > 0).sum()),

@@ -3,28 +3,33 @@ semantic voxel map instead of a labelled mesh.
 
     depth/ + poses + label maps --fuse_semantic_views--> volume, votes, labels
         --render_voxel_map--> map_label, map_depth
+    depth/ + poses + score maps --fuse_semantic_views--> volume, evidence, labels
 
 While ``ops.integrate_tsdf`` fuses a batch of depth views, ``ops.vote_voxel_labels``
 lets the same views vote for their classes in the voxels of the truncation band;
 ``ops.resolve_voxel_labels`` keeps the winner per voxel and ``ops.raycast_tsdf``
 ray-casts the volume into any posed view (depth, normal, the nearest voxel's
-label).  No mesh is extracted and no per-view vertex-id render is needed.  Out
-of scope: sparse / hashed blocks, soft votes, view-dependent weights, pose
-refinement."""
+label).  No mesh is extracted and no per-view vertex-id render is needed.  With
+``score_maps`` (rows of evidence codes per pixel, ``ops.log_evidence``) the
+views add per-class evidence instead of one vote each
+(``ops.accumulate_voxel_evidence`` / ``ops.resolve_voxel_evidence``): the label
+of a voxel is then the MAP class of its views, not their majority.  Out of
+scope: sparse / hashed blocks, float probabilities on the device, priors,
+view-dependent weights, pose refinement."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from .. import ops
-from .mesh_fusion import _batch
+from .mesh_fusion import _batch, _score_batch
 from .tsdf_fusion import depth_points_aabb
 
 
 def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_maps=None,
                         aabb=None, voxel=0.05, trunc=None, batch=16, num_classes=40,
                         min_votes=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
-                        device="cuda"):
+                        device="cuda", score_maps=None, min_margin=0):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps`` /
     ``label_maps`` / ``color_maps``: sequences or callables ``i -> [H,W]`` fp32
     z-depth in scene units (0 = none), ``[H,W]`` uint8 class ids (0 = no vote),
@@ -34,8 +39,19 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
     ``volume`` (``ops.tsdf_volume`` with ``trunc`` recorded), ``votes``
     [C+1,nx,ny,nz] uint16, ``labels`` [nx,ny,nz] uint8, ``total`` / ``winner``
     uint32, all on the device, and ``dims``, ``observed`` (share of voxels with
-    weight >= 1), ``labelled`` (share with a label)."""
+    weight >= 1), ``labelled`` (share with a label).
+    With ``score_maps`` (``i -> [H,W,C]`` or ``[C,H,W]`` uint8 evidence codes,
+    C = ``num_classes``; ``label_maps`` is then not read and may be None) the
+    TSDF integration runs as before and the evidence path replaces the vote
+    path: the dict carries ``evidence`` [C+1,nx,ny,nz] uint32 instead of
+    ``votes``, ``labels`` resolved with ``min_votes`` as the least number of
+    contributing views and ``min_margin`` as the least lead of the best class
+    over the runner-up in evidence units, and ``views`` / ``best`` / ``margin``
+    uint32 instead of ``total`` / ``winner``."""
     dev = torch.device(device)
+    soft = score_maps is not None
+    if not soft and min_margin:
+        raise ValueError("min_margin applies to score_maps only")
     voxel = float(voxel)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
     if not (voxel > 0 and trunc > 0):
@@ -55,11 +71,14 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
     vol = ops.tsdf_volume(dims, box[0].tolist(), voxel, with_color=color_maps is not None,
                           device=dev)
     vol["trunc"] = trunc
-    votes = ops.voxel_votes(vol, num_classes)
+    votes = ops.voxel_evidence(vol, num_classes) if soft else ops.voxel_votes(vol, num_classes)
     for a in range(0, N, batch):
         b = min(a + batch, N)
         z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
-        lab = _batch(label_maps, a, b, np.uint8, H, W, "label_maps").to(dev)
+        if soft:
+            sc = _score_batch(score_maps, a, b, H, W, int(num_classes)).to(dev)
+        else:
+            lab = _batch(label_maps, a, b, np.uint8, H, W, "label_maps").to(dev)
         col = None
         if color_maps is not None:
             col = np.stack([np.asarray(color_maps(i) if callable(color_maps) else color_maps[i])
@@ -70,8 +89,18 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
         P = poses[a:b].to(dev)
         ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
                            depth_min=depth_min, depth_max=depth_max)
-        ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
-                              depth_max=depth_max)
+        if soft:
+            ops.accumulate_voxel_evidence(votes, vol, z, sc, P, intrinsics, trunc,
+                                          depth_min=depth_min, depth_max=depth_max)
+        else:
+            ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
+                                  depth_max=depth_max)
+    if soft:
+        res = ops.resolve_voxel_evidence(votes, min_votes, min_margin)
+        return {"volume": vol, "evidence": votes, "labels": res["label"], "views": res["views"],
+                "best": res["best"], "margin": res["margin"], "dims": tuple(dims),
+                "observed": float((vol["weight"] >= 1.0).float().mean()),
+                "labelled": float((res["label"] > 0).float().mean())}
     res = ops.resolve_voxel_labels(votes, min_votes)
     return {"volume": vol, "votes": votes, "labels": res["label"], "total": res["total"],
             "winner": res["winner"], "dims": tuple(dims),
