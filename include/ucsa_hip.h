@@ -1640,6 +1640,66 @@ int32_t ucsa_label_fuse_evidence(const int32_t* vertex_id, const uint8_t* scores
                                  uint32_t V, uint32_t C, uint64_t* votes,
                                  uint64_t votes_capacity, void* stream);
 
+/* ---- neighbourhood pooling of fused label tables (not in the reference) ----
+ * Every voxel and every vertex of the tables above decides on its own.  These
+ * two entries pool a table over the immediate neighbourhood, in integers, into
+ * a NEW table of the same layout that the resolve entries read as it is (their
+ * thresholds then count pooled units: up to centre + 26 times what one voxel
+ * held).  The input is never modified.  tests/smooth_numpy.py restates both
+ * contracts; the outputs match it bit for bit.
+ *
+ * ucsa_voxel_table_smooth: in / out are tables [C+1][nx][ny][nz], class-major,
+ *   of elem_bytes = 4 (uint32: ucsa_tsdf_evidence) or 2 (uint16:
+ *   ucsa_tsdf_vote) per element; weight [nx][ny][nz] fp32 is the volume's.
+ *   obs(v) = weight[v] >= min_weight (an fp32 compare, the ray-caster's cell
+ *   rule; a NaN weight is not observed).  For a voxel v with obs(v) and every
+ *   plane p = 0..C, plane 0 included:
+ *     out[p][v] = min(SAT, centre * in[p][v] + sum of in[p][n] over n in N(v)),
+ *   N(v) = the 6 face neighbours (neighbourhood = 6) or the 26 other voxels of
+ *   the 3x3x3 cube around v (neighbourhood = 26) that lie inside the lattice
+ *   AND have obs(n); SAT = 2^32-1 or 65535; the sum is exact (it cannot exceed
+ *   281 * SAT).  For a voxel without obs(v), out[p][v] = in[p][v]: evidence
+ *   neither crosses into an unobserved voxel nor comes out of one.  Plane 0 of
+ *   an evidence table becomes a pooled contribution count.  k calls, each
+ *   reading the previous call's output, are k iterations.
+ *   One launch for all planes: a work-group owns a tile of 4 x 4 x 64 voxels,
+ *   the gate is folded into a 27-bit mask per thread once and reused for every
+ *   plane, and each plane's tile with its one-voxel halo goes through LDS; a
+ *   halo cell outside the lattice is not loaded (nothing outside in, out and
+ *   weight is touched).  A tile without an observed voxel is copied.  No
+ *   atomics: two runs give the same bytes.
+ *   Limits: elem_bytes 2 or 4 (argument 2), 1 <= C <= 255 and
+ *   (C+1)*nx*ny*nz <= 2^40 (argument 3), dims >= 2 each, nx*ny*nz <= 2^31-1,
+ *   nx, ny <= 262140 (arguments 4..6), min_weight not NaN (argument 8),
+ *   neighbourhood 6 or 26 (argument 9), 1 <= centre <= 255 (argument 10); out
+ *   must not overlap in or weight, in == out included (argument 1).  An
+ *   argument error comes before any launch and nothing is written.
+ * ucsa_label_table_smooth: in / out are tables [V][C+1] uint64 (the table of
+ *   ucsa_label_fuse_accumulate / ucsa_label_fuse_evidence); the mesh's edges
+ *   come as compressed rows: the neighbours of vertex v are
+ *   neighbours[offsets[v] .. offsets[v+1]), offsets int32 [V+1], neighbours
+ *   int32 [E] (ops.mesh_adjacency: each undirected edge once per direction, no
+ *   self edges, no duplicates).  For every vertex v and column c = 0..C:
+ *     out[v][c] = centre * in[v][c] + sum of in[n][c] over n in the list of v,
+ *   modulo 2^64 (the table's own adds wrap); a vertex with an empty list gets
+ *   centre * in[v].  A list entry outside 0..V-1 is the caller's error and is
+ *   skipped, and offsets are clamped into [0, E]: a malformed list reads
+ *   nothing outside the arrays.  The columns go across the lanes of a group of
+ *   G lanes per vertex (G = the power of two >= min(C+1, 64)), which walks the
+ *   list with one coalesced row read per neighbour and one store per element.
+ *   No atomics.
+ *   Limits: 1 <= C <= 255 (argument 3), V*(C+1) <= 2^31-1 (argument 2),
+ *   E <= 2^31-1 (argument 6), 1 <= centre <= 255 (argument 7); out must not
+ *   overlap in, offsets or neighbours (argument 1).  V == 0: returns 0,
+ *   launches nothing. */
+int32_t ucsa_voxel_table_smooth(const void* in, void* out, uint32_t elem_bytes, uint32_t C,
+                                uint32_t nx, uint32_t ny, uint32_t nz, const float* weight,
+                                float min_weight, uint32_t neighbourhood, uint32_t centre,
+                                void* stream);
+int32_t ucsa_label_table_smooth(const uint64_t* in, uint64_t* out, uint32_t V, uint32_t C,
+                                const int32_t* offsets, const int32_t* neighbours, uint64_t E,
+                                uint32_t centre, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ sibling of ``scripts/render_mesh_labels.py``, which goes the other way.
     python scripts/fuse_mesh_labels.py --scene_root <root>/<scene> --mesh M.ply \\
         [--pose_frame] --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] \\
         [--depth_tol METRES] [--min_votes K] [--every N] --out FUSED.ply \\
-        [--render] [--score] [--scores {seg_evidence,<dir>} [--min_margin M]]
+        [--render] [--score] [--scores {seg_evidence,<dir>} [--min_margin M]] \\
+        [--smooth N]
 
 ``--labels``: ``label_40`` is ``<scene>/label_40``; ``seg_label`` / ``nerf_label``
 are ``<scene>/<exp_name>/...`` (the predict pass's output); anything else is a
@@ -32,7 +33,14 @@ next to the fused one.
 A vertex's label is the class with the largest evidence sum; ``--min_votes`` is
 then the least total in evidence units and ``--min_margin`` the least lead of
 the winner over the runner-up.  ``--labels`` is then not fused; if given it
-names the maps scored as the input (default: the argmax of the score maps)."""
+names the maps scored as the input (default: the argmax of the score maps).
+``--smooth N`` pools the table N times over each vertex's edge neighbours
+before it is resolved (``ops.smooth_label_table``): unobserved vertices are
+filled from their neighbours.  ``--min_votes`` and ``--min_margin`` then apply
+to the pooled table, whose units grow with pooling (a vertex's sum is added to
+those of its neighbours).  The gain is largest for label noise that is
+independent per pixel; spatially correlated mistakes gain less.  0 (the
+default) changes nothing."""
 import argparse
 import json
 import os
@@ -60,10 +68,17 @@ def parse_args(argv=None):
     p.add_argument("--scores", default=None,
                    help="fuse evidence instead: seg_evidence | a directory of <stem>.npy")
     p.add_argument("--min_margin", type=int, default=0,
-                   help="with --scores: least lead over the runner-up, evidence units")
+                   help="with --scores: least lead over the runner-up, evidence units "
+                        "(of the pooled table with --smooth: the units grow with pooling)")
+    p.add_argument("--smooth", type=int, default=0,
+                   help="pool the table N times over edge neighbours before resolving; "
+                        "--min_votes / --min_margin then count pooled units, which grow with "
+                        "pooling (default 0: off)")
     p.add_argument("--exp_name", default=None)
     p.add_argument("--depth_tol", type=float, default=None, help="metres")
-    p.add_argument("--min_votes", type=int, default=1)
+    p.add_argument("--min_votes", type=int, default=1,
+                   help="least total of a labelled vertex; with --smooth it counts pooled "
+                        "units, which grow with pooling")
     p.add_argument("--every", type=int, default=1, help="use every N-th frame")
     p.add_argument("--out", required=True, help="the labelled mesh to write (.ply)")
     p.add_argument("--render", action="store_true")
@@ -114,6 +129,8 @@ def main(argv=None):
         raise SystemExit("--min_margin goes with --scores")
     if a.min_margin < 0:
         raise SystemExit("--min_margin must be >= 0")
+    if a.smooth < 0:
+        raise SystemExit("--smooth must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -142,6 +159,7 @@ def main(argv=None):
                        depth_maps=depth if gated else None,
                        depth_tol=float(np.float32(a.depth_tol * uom)) if gated else None,
                        num_classes=a.num_classes, batch=a.batch, min_votes=a.min_votes,
+                       smooth=a.smooth,
                        **({"score_maps": codes, "min_margin": a.min_margin} if soft else {}))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     write_ply(a.out, raw["verts"], raw["faces"], normals=raw.get("normals"),
@@ -153,6 +171,8 @@ def main(argv=None):
                                 "accumulate": round(fused["accumulate_ms"] / max(n, 1), 3)}}
     if soft:
         rec["scores"] = ssrc
+    if a.smooth:
+        rec["smooth"] = a.smooth
     if a.render or a.score:
         out_dir = a.out_dir or os.path.join(a.scene_root, a.exp_name or "")
         os.makedirs(os.path.join(out_dir, "map_label"), exist_ok=True)

@@ -9,7 +9,8 @@ voxel-route sibling of ``fuse_tsdf_mesh.py`` + ``fuse_mesh_labels.py --render``.
         --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] --out_dir D \\
         [--voxel METRES] [--trunc METRES] [--step METRES] [--every N] \\
         [--min_votes K] [--aabb x0 y0 z0 x1 y1 z1] [--score] \\
-        [--scores {seg_evidence,<dir>} [--min_margin M]]
+        [--scores {seg_evidence,<dir>} [--min_margin M]] \\
+        [--smooth N [--smooth_neighbourhood {6,26}]]
 
 Writes ``D/map_label/<stem>.png`` (uint8 NYU40 id, 0 = nothing) and
 ``D/map_depth/<stem>.png`` (uint16 millimetres, 0 = nothing; the layout of
@@ -26,7 +27,15 @@ the predict pass's output), a voxel's label is the class with the largest
 evidence sum, ``--min_votes`` counts contributing views and ``--min_margin`` is
 the least lead over the runner-up in evidence units.  ``--labels`` is then not
 fused; if given it names the maps scored as the input (default: the argmax of
-the score maps)."""
+the score maps).
+``--smooth N`` pools the table (votes or evidence) N times over each observed
+voxel's observed 6 or 26 neighbours before it is resolved
+(``ops.smooth_voxel_table``): voxels the geometry saw but no label reached are
+filled, and a voxel decides with its neighbourhood.  ``--min_votes`` and
+``--min_margin`` then apply to the pooled table, whose units grow with pooling
+(a pass over 26 neighbours multiplies a flat region's sums by up to 27).  The
+gain is largest for label noise that is independent per pixel; spatially
+correlated mistakes gain less.  0 (the default) changes nothing."""
 import argparse
 import json
 import os
@@ -53,7 +62,13 @@ def parse_args(argv=None):
     p.add_argument("--scores", default=None,
                    help="fuse evidence instead: seg_evidence | a directory of <stem>.npy")
     p.add_argument("--min_margin", type=int, default=0,
-                   help="with --scores: least lead over the runner-up, evidence units")
+                   help="with --scores: least lead over the runner-up, evidence units "
+                        "(of the pooled table with --smooth: the units grow with pooling)")
+    p.add_argument("--smooth", type=int, default=0,
+                   help="pool the table N times over observed neighbours before resolving; "
+                        "--min_votes / --min_margin then count pooled units, which grow with "
+                        "pooling (default 0: off)")
+    p.add_argument("--smooth_neighbourhood", type=int, choices=(6, 26), default=26)
     p.add_argument("--exp_name", default=None)
     p.add_argument("--out_dir", required=True, help="where map_label/ and map_depth/ go")
     p.add_argument("--voxel", type=float, default=0.04, help="metres")
@@ -61,7 +76,9 @@ def parse_args(argv=None):
     p.add_argument("--step", type=float, default=None,
                    help="ray-cast step in metres (default: trunc / 2)")
     p.add_argument("--every", type=int, default=1, help="use every N-th frame")
-    p.add_argument("--min_votes", type=int, default=1)
+    p.add_argument("--min_votes", type=int, default=1,
+                   help="least votes (with --scores: contributing views) of a labelled voxel; "
+                        "with --smooth it counts pooled units, which grow with pooling")
     p.add_argument("--aabb", type=float, nargs=6, default=None,
                    help="x0 y0 z0 x1 y1 z1, NGP frame, scene units")
     p.add_argument("--near", type=float, default=0.05, help="near plane, scene units")
@@ -112,6 +129,8 @@ def main(argv=None):
         raise SystemExit("--min_margin goes with --scores")
     if a.min_margin < 0:
         raise SystemExit("--min_margin must be >= 0")
+    if a.smooth < 0:
+        raise SystemExit("--smooth must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -139,7 +158,8 @@ def main(argv=None):
                                 aabb=a.aabb, voxel=a.voxel * uom,
                                 trunc=None if a.trunc is None else a.trunc * uom,
                                 batch=a.batch, num_classes=a.num_classes,
-                                min_votes=a.min_votes, **soft)
+                                min_votes=a.min_votes, smooth=a.smooth,
+                                smooth_neighbourhood=a.smooth_neighbourhood, **soft)
     torch.cuda.synchronize()
     t_fuse = time.perf_counter() - t0
     vol = fused["volume"]
@@ -176,6 +196,8 @@ def main(argv=None):
            "raycast_ms_per_view": round(1e3 * t_cast / max(n, 1), 3)}
     if soft:
         rec["scores"] = ssrc
+    if a.smooth:
+        rec["smooth"] = [a.smooth, a.smooth_neighbourhood]
     if a.score:
         truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
         given = np.stack([png(src, i) if src is not None else codes_argmax(codes(i), H, W)

@@ -339,6 +339,10 @@ SIGNATURES = {
                                                 _p, C.c_uint64, _p]),
     "ucsa_label_fuse_evidence": (C.c_int32, [_p, _p, _p, _p, _f, C.c_uint64, _u32, _u32, _u32,
                                              _p, C.c_uint64, _p]),
+    # ---- neighbourhood pooling of the fused label tables ----
+    "ucsa_voxel_table_smooth": (C.c_int32, [_p, _p, _u32, _u32, _u32, _u32, _u32, _p, _f, _u32,
+                                            _u32, _p]),
+    "ucsa_label_table_smooth": (C.c_int32, [_p, _p, _u32, _u32, _p, _p, C.c_uint64, _u32, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -2159,3 +2159,127 @@ def raycast_tsdf(volume, poses, intrinsics, H: int, W: int, near: float, far: fl
         _ptr(out.get("label")), B * H * W, _ptr(ws), ws_bytes, 1 if _plain_march else 0,
         _stream()), "ucsa_tsdf_raycast")
     return out
+
+
+# ---------------------------------------------------------------------------
+# neighbourhood pooling of the fused label tables
+# ---------------------------------------------------------------------------
+def _centre(centre) -> int:
+    if isinstance(centre, bool) or not isinstance(centre, int) or not 1 <= centre <= 255:
+        raise _lib.UcsaError(f"centre must be an integer in 1..255, got {centre!r}")
+    return centre
+
+
+def smooth_voxel_table(table, volume, neighbourhood: int = 26, iterations: int = 1,
+                       centre: int = 1, min_weight: float = 1.0):
+    """Pool a voxel table over each voxel's observed neighbours -> a NEW table
+    of the same dtype and shape; ``table`` is not modified.  ``table``
+    [C+1,nx,ny,nz], contiguous, on the volume's device: uint32
+    (``voxel_evidence``) or uint16 (``voxel_votes``).  With obs(v) =
+    ``volume["weight"][v] >= min_weight`` (fp32, the ray-caster's cell rule), a
+    voxel with obs(v) gets, in every plane p = 0..C,
+    min(SAT, centre * table[p, v] + the sum of table[p, n]) over its 6 face
+    neighbours or the 26 neighbours of the 3x3x3 cube (``neighbourhood``) that
+    lie inside the lattice and have obs(n); a voxel without obs(v) keeps its
+    column.  SAT is 2^32-1 / 65535.  ``iterations`` = k gives the bytes of k
+    single calls.  Plane 0 of an evidence table becomes a pooled contribution
+    count: ``resolve_voxel_evidence(min_views=...)`` then applies to that count,
+    and ``min_margin`` / ``min_votes`` to pooled sums (up to centre + 26 times a
+    single voxel's).  Contract of ucsa_voxel_table_smooth (include/ucsa_hip.h)."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    if not (torch.is_tensor(table) and table.is_cuda
+            and table.dtype in (torch.uint32, torch.uint16) and table.is_contiguous()):
+        raise _lib.UcsaError("table must be a contiguous uint32 or uint16 tensor on the GPU")
+    if table.dim() != 4 or not 2 <= table.shape[0] <= 256:
+        raise _lib.UcsaError(f"table must be [C+1,nx,ny,nz] with 1 <= C <= 255, got "
+                             f"{tuple(table.shape)}")
+    if tuple(table.shape[1:]) != (nx, ny, nz) or table.device != dev:
+        raise _lib.UcsaError(f"table must be [C+1,{nx},{ny},{nz}] on the volume's device, got "
+                             f"{tuple(table.shape)} on {table.device}")
+    if neighbourhood not in (6, 26):
+        raise _lib.UcsaError(f"neighbourhood must be 6 or 26, got {neighbourhood!r}")
+    centre = _centre(centre)
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+        raise _lib.UcsaError(f"iterations must be an integer >= 1, got {iterations!r}")
+    Cn = int(table.shape[0]) - 1
+    weight = volume["weight"]
+    src, spare = table, None
+    for _ in range(iterations):
+        dst = torch.empty_like(table) if spare is None else spare
+        check(lib().ucsa_voxel_table_smooth(
+            _ptr(src), _ptr(dst), table.element_size(), Cn, nx, ny, nz, _ptr(weight),
+            float(min_weight), int(neighbourhood), centre, _stream()), "ucsa_voxel_table_smooth")
+        # ping-pong between two fresh buffers; the input is only ever read
+        spare = src if src is not table else None
+        src = dst
+    return src
+
+
+def mesh_adjacency(faces, n_vertices: int):
+    """The vertex adjacency of a triangle mesh as compressed rows, for
+    ``smooth_label_table``: ``faces`` [F,3] int32 on the GPU -> (``offsets``
+    int32 [V+1], ``neighbours`` int32 [E]); the neighbours of vertex v are
+    ``neighbours[offsets[v]:offsets[v+1]]``, ascending.  Every undirected edge
+    is stored once per direction, a face listed twice adds nothing, a
+    degenerate face contributes only its proper edges (no self edges).  Plain
+    torch on the device (sort and unique: plumbing, not a kernel)."""
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32
+            and faces.dim() == 2 and faces.shape[1] == 3):
+        raise _lib.UcsaError("faces must be an int32 [F,3] tensor on the GPU")
+    V = int(n_vertices)
+    if not 0 <= V <= 0x7FFFFFFF:
+        raise _lib.UcsaError(f"n_vertices must be in 0..2^31-1, got {n_vertices}")
+    f = faces.long()
+    if f.numel() and (int(f.min()) < 0 or int(f.max()) >= V):
+        raise _lib.UcsaError(f"faces index vertices outside 0..{V - 1}")
+    a = torch.cat([f[:, 0], f[:, 1], f[:, 2]])
+    b = torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+    keep = a != b
+    a, b = a[keep], b[keep]
+    key = torch.unique(torch.cat([a * V + b, b * V + a]))       # sorted: by vertex, then neighbour
+    if key.numel() > 0x7FFFFFFF:
+        raise _lib.UcsaError("mesh_adjacency: more than 2^31-1 directed edges")
+    src = torch.div(key, max(V, 1), rounding_mode="floor")
+    offsets = torch.zeros(V + 1, dtype=torch.int64, device=faces.device)
+    offsets[1:] = torch.cumsum(torch.bincount(src, minlength=V), 0)
+    return offsets.to(torch.int32), (key - src * V).to(torch.int32)
+
+
+def smooth_label_table(votes, adjacency, iterations: int = 1, centre: int = 1):
+    """Pool a mesh table over each vertex's neighbours -> a NEW table; ``votes``
+    [V, C+1] int64 (the bits of the uint64 table of ``fuse_label_votes`` /
+    ``fuse_label_evidence``) is not modified.  ``adjacency`` is
+    ``mesh_adjacency``'s pair.  out[v, :] = centre * votes[v, :] + the sum of
+    votes[n, :] over the neighbours n of v, in all C+1 columns, modulo 2^64; a
+    vertex without neighbours gets centre * votes[v].  ``iterations`` = k gives
+    the bytes of k single calls.  ``resolve_label_votes`` reads the result as
+    it is; ``min_votes`` then counts pooled units.  Contract of
+    ucsa_label_table_smooth (include/ucsa_hip.h)."""
+    V, Cn = _vote_table(votes)
+    if votes.device.index != torch.cuda.current_device():
+        raise _lib.UcsaError(f"votes is on {votes.device} but the current device is cuda:"
+                             f"{torch.cuda.current_device()}: call torch.cuda.set_device first")
+    try:
+        offsets, neighbours = adjacency
+    except (TypeError, ValueError):
+        raise _lib.UcsaError("adjacency must be the (offsets, neighbours) pair of mesh_adjacency")
+    for t, name in ((offsets, "offsets"), (neighbours, "neighbours")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == votes.device
+                and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()):
+            raise _lib.UcsaError(f"adjacency: {name} must be a contiguous int32 vector on the "
+                                 "table's device")
+    if offsets.numel() != V + 1:
+        raise _lib.UcsaError(f"adjacency: offsets has {offsets.numel()} entries, the table has "
+                             f"{V} vertices")
+    centre = _centre(centre)
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+        raise _lib.UcsaError(f"iterations must be an integer >= 1, got {iterations!r}")
+    src, spare = votes, None
+    for _ in range(iterations):
+        dst = torch.empty_like(votes) if spare is None else spare
+        check(lib().ucsa_label_table_smooth(
+            _ptr(src), _ptr(dst), V, Cn, _ptr(offsets), _ptr(neighbours), neighbours.numel(),
+            centre, _stream()), "ucsa_label_table_smooth")
+        spare = src if src is not votes else None
+        src = dst
+    return src

@@ -11,8 +11,10 @@ uint64 table that stays on the device, ``ops.resolve_label_votes`` takes the
 majority.  With ``score_maps`` (rows of evidence codes per pixel,
 ``ops.log_evidence``) a pixel adds its row to its vertex instead
 (``ops.fuse_label_evidence``, same table) and the majority becomes the MAP
-class.  Out of scope: float probabilities on the device, priors,
-filling unobserved vertices from their neighbours, registering a
+class.  With ``smooth`` the table is pooled over each vertex's edge neighbours
+before it is resolved (``ops.smooth_label_table``), which also fills unobserved
+vertices from their neighbours.  Out of scope: float probabilities on the
+device, priors, registering a
 mesh to the poses' frame (``load_mesh(..., pose_frame=True)`` covers the one
 rigid motion the project records), anything in the training loop."""
 from __future__ import annotations
@@ -55,7 +57,7 @@ def _score_batch(src, a, b, H, W, C):
 
 def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
                depth_tol=None, weights=None, num_classes=40, batch=16, min_votes=1,
-               device="cuda", score_maps=None, min_margin=0):
+               device="cuda", score_maps=None, min_margin=0, smooth=0):
     """``mesh``: dict with verts [V,3] f32 and faces [F,3] int32 in the poses'
     (NGP) frame (``load_mesh``); ``poses`` [N,4,4]; ``label_maps``: a sequence
     or a callable ``i -> [H,W]`` integer class ids per view (NYU40: 1..C vote,
@@ -73,7 +75,15 @@ def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
     vote; ``total`` / ``winner`` and ``min_votes`` are then in evidence units,
     the dict carries ``margin`` [V] uint64 (the winner's lead over the
     runner-up; the winner itself for one class) and a vertex whose margin is
-    below ``min_margin`` gets label 0."""
+    below ``min_margin`` gets label 0.
+    ``smooth`` = N > 0 pools the table N times over each vertex's edge
+    neighbours (``ops.mesh_adjacency`` / ``ops.smooth_label_table``) before it
+    is resolved: an unobserved vertex takes its neighbours' label, and
+    ``min_votes`` / ``min_margin`` count pooled units.  0 leaves everything as
+    it was."""
+    smooth = int(smooth)
+    if smooth < 0:
+        raise ValueError("smooth must be >= 0")
     soft = score_maps is not None
     if not soft and min_margin:
         raise ValueError("min_margin applies to score_maps only")
@@ -122,6 +132,8 @@ def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
         t3 = time.perf_counter()
         t_r += t1 - t0
         t_a += t3 - t2
+    if smooth:
+        votes = ops.smooth_label_table(votes, ops.mesh_adjacency(faces, V), iterations=smooth)
     res = ops.resolve_label_votes(votes, min_votes)
     extra = {}
     if soft:

@@ -13,7 +13,11 @@ label).  No mesh is extracted and no per-view vertex-id render is needed.  With
 ``score_maps`` (rows of evidence codes per pixel, ``ops.log_evidence``) the
 views add per-class evidence instead of one vote each
 (``ops.accumulate_voxel_evidence`` / ``ops.resolve_voxel_evidence``): the label
-of a voxel is then the MAP class of its views, not their majority.  Out of
+of a voxel is then the MAP class of its views, not their majority.  With
+``smooth`` the table is pooled over each observed voxel's observed neighbours
+first (``ops.smooth_voxel_table``): a voxel that one view reached decides with
+its neighbourhood, and a voxel that the geometry saw but no label reached takes
+its neighbours' label.  Out of
 scope: sparse / hashed blocks, float probabilities on the device, priors,
 view-dependent weights, pose refinement."""
 from __future__ import annotations
@@ -29,7 +33,8 @@ from .tsdf_fusion import depth_points_aabb
 def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_maps=None,
                         aabb=None, voxel=0.05, trunc=None, batch=16, num_classes=40,
                         min_votes=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
-                        device="cuda", score_maps=None, min_margin=0):
+                        device="cuda", score_maps=None, min_margin=0, smooth=0,
+                        smooth_neighbourhood=26):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps`` /
     ``label_maps`` / ``color_maps``: sequences or callables ``i -> [H,W]`` fp32
     z-depth in scene units (0 = none), ``[H,W]`` uint8 class ids (0 = no vote),
@@ -47,7 +52,16 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
     ``votes``, ``labels`` resolved with ``min_votes`` as the least number of
     contributing views and ``min_margin`` as the least lead of the best class
     over the runner-up in evidence units, and ``views`` / ``best`` / ``margin``
-    uint32 instead of ``total`` / ``winner``."""
+    uint32 instead of ``total`` / ``winner``.
+    ``smooth`` = N > 0 pools the table it built (votes or evidence) N times over
+    each observed voxel's observed neighbours (``ops.smooth_voxel_table``,
+    ``smooth_neighbourhood`` 6 or 26) before it is resolved; the dict then
+    carries the pooled table, and ``min_votes`` / ``min_margin`` count pooled
+    units (one pass over 26 neighbours multiplies a flat region's sums by up to
+    27).  0 leaves everything as it was."""
+    smooth = int(smooth)
+    if smooth < 0:
+        raise ValueError("smooth must be >= 0")
     dev = torch.device(device)
     soft = score_maps is not None
     if not soft and min_margin:
@@ -95,6 +109,9 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
         else:
             ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
                                   depth_max=depth_max)
+    if smooth:
+        votes = ops.smooth_voxel_table(votes, vol, neighbourhood=smooth_neighbourhood,
+                                       iterations=smooth)
     if soft:
         res = ops.resolve_voxel_evidence(votes, min_votes, min_margin)
         return {"volume": vol, "evidence": votes, "labels": res["label"], "views": res["views"],
