@@ -1700,6 +1700,59 @@ int32_t ucsa_label_table_smooth(const uint64_t* in, uint64_t* out, uint32_t V, u
                                 const int32_t* offsets, const int32_t* neighbours, uint64_t E,
                                 uint32_t centre, void* stream);
 
+/* ---- connected components (not in the reference) ----
+ * Which pieces of a map hang together: of a voxel mask, of a mesh's vertex
+ * graph, and how large each piece is.  A label is the smallest index of its
+ * component, which is unique whatever the schedule does, and the counts are
+ * integer adds: tests/components_numpy.py restates the three contracts and the
+ * outputs match it byte for byte; two runs give the same bytes.  The inputs are
+ * never modified.  Union-find in the output array itself (parent[x] <= x at
+ * every instant, so every walk strictly descends; the larger root is hooked
+ * under the smaller with a 32-bit integer atomic min; a last launch makes every
+ * element point at its root): a fixed number of launches per call, no host
+ * read-back, and no loop whose exit waits for another wave.
+ *
+ * ucsa_voxel_components: mask [nx][ny][nz] uint8, labels [nx][ny][nz] int32.
+ *   Two voxels with mask != 0 are neighbours if they differ by one step along
+ *   one axis (connectivity = 6) or lie in each other's 3x3x3 cube (connectivity
+ *   = 26, the neighbourhoods of ucsa_voxel_table_smooth).  labels[v] = the
+ *   smallest linear index (i*ny + j)*nz + k over the component of v if
+ *   mask[v] != 0, else -1.  Three launches: a work-group labels its tile of
+ *   4 x 4 x 64 voxels in LDS (each voxel hooks to the earlier half of its
+ *   neighbourhood, 3 of 6 or 13 of 26) and writes the tile's roots as global
+ *   indices; unions across tile faces, edges and corners with global atomics;
+ *   flatten.  Nothing outside mask and labels is touched.
+ *   Limits: dims >= 1 each, nx*ny*nz <= 2^31-1, nx, ny <= 262140 (arguments
+ *   2..4), connectivity 6 or 26 (argument 5); labels must not overlap mask
+ *   (argument 1).  An argument error comes before any launch and nothing is
+ *   written.
+ * ucsa_graph_components: the graph comes as the compressed rows of
+ *   ucsa_label_table_smooth (ops.mesh_adjacency): offsets int32 [V+1],
+ *   neighbours int32 [E], each undirected edge once per direction (what counts
+ *   is that every edge is listed in the row of its larger end).  labels[v]
+ *   (int32 [V]) = the smallest vertex index of v's component; an isolated
+ *   vertex gets v.  A lane per vertex hooks over its neighbours n < v; a row of
+ *   more than 64 entries is walked by the whole wave, 64 entries at a time.  A
+ *   list entry outside 0..V-1 is skipped and offsets are clamped into [0, E]: a
+ *   malformed list reads nothing outside the arrays.
+ *   Limits: V <= 2^31-1 (argument 2), E <= 2^31-1 (argument 3); labels must not
+ *   overlap offsets or neighbours (argument 4).  V == 0: returns 0, launches
+ *   nothing; E == 0: labels[v] = v.
+ * ucsa_component_sizes: labels, sizes, scratch int32 [n] each.  sizes[x] = the
+ *   number of elements y with labels[y] == labels[x] if 0 <= labels[x] < n,
+ *   else 0 (the -1 of an unset voxel).  scratch is zeroed, every element adds 1
+ *   to scratch[labels[x]] with 32-bit integer atomics -- the lanes of a wave
+ *   that share a label are counted first and add once -- and sizes gathers.
+ *   scratch holds the count of label r at r afterwards.
+ *   Limits: n <= 2^31-1 (argument 3); the three arrays must not overlap
+ *   (arguments 1, 2).  n == 0: returns 0, launches nothing. */
+int32_t ucsa_voxel_components(const uint8_t* mask, int32_t* labels, uint32_t nx, uint32_t ny,
+                              uint32_t nz, uint32_t connectivity, void* stream);
+int32_t ucsa_graph_components(const int32_t* offsets, const int32_t* neighbours, uint32_t V,
+                              uint64_t E, int32_t* labels, void* stream);
+int32_t ucsa_component_sizes(const int32_t* labels, int32_t* sizes, int32_t* scratch,
+                             uint64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

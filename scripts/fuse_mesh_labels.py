@@ -8,7 +8,7 @@ sibling of ``scripts/render_mesh_labels.py``, which goes the other way.
         [--pose_frame] --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] \\
         [--depth_tol METRES] [--min_votes K] [--every N] --out FUSED.ply \\
         [--render] [--score] [--scores {seg_evidence,<dir>} [--min_margin M]] \\
-        [--smooth N]
+        [--smooth N] [--min_component N]
 
 ``--labels``: ``label_40`` is ``<scene>/label_40``; ``seg_label`` / ``nerf_label``
 are ``<scene>/<exp_name>/...`` (the predict pass's output); anything else is a
@@ -40,7 +40,12 @@ filled from their neighbours.  ``--min_votes`` and ``--min_margin`` then apply
 to the pooled table, whose units grow with pooling (a vertex's sum is added to
 those of its neighbours).  The gain is largest for label noise that is
 independent per pixel; spatially correlated mistakes gain less.  0 (the
-default) changes nothing."""
+default) changes nothing.
+``--min_component N`` drops the mesh's connected components with fewer than N
+vertices right after loading it (``filter_mesh_components``: the floaters of a
+reconstruction), so that they neither collect votes nor occlude; the written
+mesh is the filtered one and the statistics are printed.  0 (the default)
+changes nothing."""
 import argparse
 import json
 import os
@@ -51,7 +56,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ucsa_neural_rendering_amd.utils.mesh_fusion import fuse_views  # noqa: E402
+from ucsa_neural_rendering_amd.utils.mesh_fusion import (  # noqa: E402
+    filter_mesh_components, fuse_views)
 from ucsa_neural_rendering_amd.utils.mesh_render import (  # noqa: E402
     load_mesh, read_frames, render_views, score_label_maps)
 from ucsa_neural_rendering_amd.utils.ply import read_ply, write_ply  # noqa: E402
@@ -70,6 +76,9 @@ def parse_args(argv=None):
     p.add_argument("--min_margin", type=int, default=0,
                    help="with --scores: least lead over the runner-up, evidence units "
                         "(of the pooled table with --smooth: the units grow with pooling)")
+    p.add_argument("--min_component", type=int, default=0,
+                   help="drop the mesh's connected components with fewer vertices than this "
+                        "after loading it (default 0: off)")
     p.add_argument("--smooth", type=int, default=0,
                    help="pool the table N times over edge neighbours before resolving; "
                         "--min_votes / --min_margin then count pooled units, which grow with "
@@ -131,6 +140,8 @@ def main(argv=None):
         raise SystemExit("--min_margin must be >= 0")
     if a.smooth < 0:
         raise SystemExit("--smooth must be >= 0")
+    if a.min_component < 0:
+        raise SystemExit("--min_component must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -139,6 +150,13 @@ def main(argv=None):
     H, W = fr["H"], fr["W"]
     raw = read_ply(a.mesh)
     mesh = load_mesh(a.mesh, pose_frame=a.pose_frame, one_m_to_scene_uom=uom)
+    components = None
+    if a.min_component > 0:
+        mesh, components = filter_mesh_components(mesh, min_vertices=a.min_component)
+        vi = mesh["vertex_index"]
+        raw = {**raw, "faces": mesh["faces"],
+               **{k: raw[k][vi] for k in ("verts", "normals", "rgb") if raw.get(k) is not None}}
+        print("components: " + json.dumps(components))
     src = None if a.labels is None else label_dir(a)
     ssrc = None if a.scores is None else score_dir(a)
 
@@ -173,6 +191,8 @@ def main(argv=None):
         rec["scores"] = ssrc
     if a.smooth:
         rec["smooth"] = a.smooth
+    if components is not None:
+        rec["components"] = components
     if a.render or a.score:
         out_dir = a.out_dir or os.path.join(a.scene_root, a.exp_name or "")
         os.makedirs(os.path.join(out_dir, "map_label"), exist_ok=True)

@@ -6,7 +6,8 @@ first stage of the mapping-based pseudo-label baseline.
 
     python scripts/fuse_tsdf_mesh.py --scene_root <root>/<scene> --out M.ply \\
         [--voxel METRES] [--trunc METRES] [--aabb X0 Y0 Z0 X1 Y1 Z1] [--every N] \\
-        [--min_weight K] [--no_color] [--pose_frame]
+        [--min_weight K] [--no_color] [--pose_frame] \\
+        [--min_component N] [--component_connectivity {6,26}]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
 ``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement; scene units as
@@ -17,7 +18,11 @@ units (default: the bounding box of the back-projected depth points, padded by
 the truncation distance).  The mesh is written in the NGP frame, or with
 ``--pose_frame`` in the frame of the JSON poses in metres (read it back with
 ``fuse_mesh_labels.py --pose_frame``), with normals and, unless ``--no_color``,
-vertex colours; no labels.  Prints one JSON line."""
+vertex colours; no labels.  ``--min_component N`` returns the connected
+components of the truncation band with fewer than N voxels to the unobserved
+state before the mesh is extracted (``remove_small_components``: the floaters
+that a few bad depth pixels leave in free space) and prints their statistics;
+0, the default, changes nothing.  Prints one JSON line last."""
 import argparse
 import json
 import os
@@ -49,6 +54,9 @@ def parse_args(argv=None):
     p.add_argument("--pose_frame", action="store_true",
                    help="write the mesh in the JSON pose frame, in metres")
     p.add_argument("--batch", type=int, default=16, help="views per integration call")
+    p.add_argument("--min_component", type=int, default=0,
+                   help="drop band components with fewer voxels than this (default 0: off)")
+    p.add_argument("--component_connectivity", type=int, choices=(6, 26), default=26)
     return p.parse_args(argv)
 
 
@@ -57,6 +65,8 @@ def main(argv=None):
     a = parse_args(argv)
     if a.every < 1 or a.min_weight < 1 or a.batch < 1:
         raise SystemExit("--every, --min_weight and --batch must be >= 1")
+    if a.min_component < 0:
+        raise SystemExit("--min_component must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -77,7 +87,9 @@ def main(argv=None):
     mesh = fuse_depth_views(poses, fr["intrinsics"], H, W, depth,
                             color_maps=None if a.no_color else color, aabb=a.aabb,
                             voxel=voxel, trunc=None if a.trunc is None else a.trunc * uom,
-                            min_weight=a.min_weight, batch=a.batch)
+                            min_weight=a.min_weight, batch=a.batch,
+                            min_component=a.min_component,
+                            component_connectivity=a.component_connectivity)
     verts = mesh["verts"]
     normals = mesh["normals"]
     if a.pose_frame:
@@ -92,6 +104,9 @@ def main(argv=None):
            "observed": round(mesh["observed"], 4),
            "integrate_ms_per_view": round(mesh["integrate_ms"] / max(n, 1), 3),
            "extract_ms": round(mesh["extract_ms"], 3)}
+    if "components" in mesh:
+        rec["components"] = mesh["components"]
+        print("components: " + json.dumps(mesh["components"]))
     print(json.dumps(rec))
     return rec
 

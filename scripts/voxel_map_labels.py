@@ -35,7 +35,11 @@ filled, and a voxel decides with its neighbourhood.  ``--min_votes`` and
 ``--min_margin`` then apply to the pooled table, whose units grow with pooling
 (a pass over 26 neighbours multiplies a flat region's sums by up to 27).  The
 gain is largest for label noise that is independent per pixel; spatially
-correlated mistakes gain less.  0 (the default) changes nothing."""
+correlated mistakes gain less.  0 (the default) changes nothing.
+``--min_component N`` returns the connected components of the truncation band
+with fewer than N voxels to the unobserved state before the table is resolved
+and the volume ray-cast (``remove_small_components``: no ray hits a floater any
+more) and prints their statistics; 0 (the default) changes nothing."""
 import argparse
 import json
 import os
@@ -69,6 +73,9 @@ def parse_args(argv=None):
                         "--min_votes / --min_margin then count pooled units, which grow with "
                         "pooling (default 0: off)")
     p.add_argument("--smooth_neighbourhood", type=int, choices=(6, 26), default=26)
+    p.add_argument("--min_component", type=int, default=0,
+                   help="drop band components with fewer voxels than this (default 0: off)")
+    p.add_argument("--component_connectivity", type=int, choices=(6, 26), default=26)
     p.add_argument("--exp_name", default=None)
     p.add_argument("--out_dir", required=True, help="where map_label/ and map_depth/ go")
     p.add_argument("--voxel", type=float, default=0.04, help="metres")
@@ -131,6 +138,8 @@ def main(argv=None):
         raise SystemExit("--min_margin must be >= 0")
     if a.smooth < 0:
         raise SystemExit("--smooth must be >= 0")
+    if a.min_component < 0:
+        raise SystemExit("--min_component must be >= 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -159,7 +168,9 @@ def main(argv=None):
                                 trunc=None if a.trunc is None else a.trunc * uom,
                                 batch=a.batch, num_classes=a.num_classes,
                                 min_votes=a.min_votes, smooth=a.smooth,
-                                smooth_neighbourhood=a.smooth_neighbourhood, **soft)
+                                smooth_neighbourhood=a.smooth_neighbourhood,
+                                min_component=a.min_component,
+                                component_connectivity=a.component_connectivity, **soft)
     torch.cuda.synchronize()
     t_fuse = time.perf_counter() - t0
     vol = fused["volume"]
@@ -198,6 +209,9 @@ def main(argv=None):
         rec["scores"] = ssrc
     if a.smooth:
         rec["smooth"] = [a.smooth, a.smooth_neighbourhood]
+    if "components" in fused:
+        rec["components"] = fused["components"]
+        print("components: " + json.dumps(fused["components"]))
     if a.score:
         truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
         given = np.stack([png(src, i) if src is not None else codes_argmax(codes(i), H, W)

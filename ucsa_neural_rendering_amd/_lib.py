@@ -343,6 +343,10 @@ SIGNATURES = {
     "ucsa_voxel_table_smooth": (C.c_int32, [_p, _p, _u32, _u32, _u32, _u32, _u32, _p, _f, _u32,
                                             _u32, _p]),
     "ucsa_label_table_smooth": (C.c_int32, [_p, _p, _u32, _u32, _p, _p, C.c_uint64, _u32, _p]),
+    # ---- connected components (voxel mask, mesh graph, component sizes) ----
+    "ucsa_voxel_components": (C.c_int32, [_p, _p, _u32, _u32, _u32, _u32, _p]),
+    "ucsa_graph_components": (C.c_int32, [_p, _p, _u32, C.c_uint64, _p, _p]),
+    "ucsa_component_sizes": (C.c_int32, [_p, _p, _p, C.c_uint64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -26,7 +26,9 @@ const char* const kEnvNames[] = {
     "UCSA_SHADE_BWD_SPLIT", "UCSA_BWD_OVERLAP", "UCSA_BWD_BIN_SCALE",
     // lab only (tools/encode_*.py, tools/coresident_exp.py)
     "UCSA_ENC_ORDER", "UCSA_ENC_SIMPLE", "UCSA_ENC_SIMPLE_H", "UCSA_ENC_SIMPLE_RAYS",
-    "UCSA_ENC_LDS_PAD", "UCSA_SORT_BINS", "UCSA_SORT_EXACT"};
+    "UCSA_ENC_LDS_PAD", "UCSA_SORT_BINS", "UCSA_SORT_EXACT",
+    // lab only (tools/components_time.py): the lattice labelling without its LDS stage
+    "UCSA_COMPONENTS_NO_LDS"};
 constexpr int kEnvCount = (int)(sizeof(kEnvNames) / sizeof(kEnvNames[0]));
 struct EnvTable {
   char value[kEnvCount][64];

@@ -2283,3 +2283,81 @@ def smooth_label_table(votes, adjacency, iterations: int = 1, centre: int = 1):
         spare = src if src is not votes else None
         src = dst
     return src
+
+
+# ---------------------------------------------------------------------------
+# connected components (voxel mask, mesh graph, component sizes)
+# ---------------------------------------------------------------------------
+def _on_current_device(t, name):
+    if t.device.index != torch.cuda.current_device():
+        raise _lib.UcsaError(f"{name} is on {t.device} but the current device is cuda:"
+                             f"{torch.cuda.current_device()}: call torch.cuda.set_device first")
+
+
+def voxel_components(mask, connectivity: int = 26):
+    """Connected components of a voxel mask -> int32 [nx,ny,nz]: the smallest
+    linear index ``(i*ny + j)*nz + k`` of the voxel's component where ``mask``
+    is set, -1 elsewhere.  ``mask`` [nx,ny,nz] bool or uint8 (non-zero = set) on
+    the GPU; it is not modified.  ``connectivity`` 6 (face neighbours) or 26
+    (the 3x3x3 cube), the neighbourhoods of ``smooth_voxel_table``.  Contract of
+    ucsa_voxel_components (include/ucsa_hip.h)."""
+    if not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)):
+        raise _lib.UcsaError("mask must be a bool or uint8 tensor on the GPU: the HIP path has "
+                             "no CPU fallback")
+    if mask.dim() != 3 or mask.numel() == 0 or mask.numel() > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"mask must be [nx,ny,nz] with 1 to 2^31-1 voxels, got "
+                             f"{tuple(mask.shape)}")
+    if isinstance(connectivity, bool) or connectivity not in (6, 26):
+        raise _lib.UcsaError(f"connectivity must be 6 or 26, got {connectivity!r}")
+    _on_current_device(mask, "mask")
+    m = mask.contiguous()
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    nx, ny, nz = (int(s) for s in m.shape)
+    labels = torch.empty((nx, ny, nz), dtype=torch.int32, device=m.device)
+    check(lib().ucsa_voxel_components(_ptr(m), _ptr(labels), nx, ny, nz, int(connectivity),
+                                      _stream()), "ucsa_voxel_components")
+    return labels
+
+
+def mesh_components(adjacency):
+    """Connected components of a mesh's vertex graph -> int32 [V]: the smallest
+    vertex index of each vertex's component (an isolated vertex gets its own).
+    ``adjacency`` is ``mesh_adjacency``'s (offsets, neighbours) pair; it is not
+    modified.  Contract of ucsa_graph_components (include/ucsa_hip.h)."""
+    try:
+        offsets, neighbours = adjacency
+    except (TypeError, ValueError):
+        raise _lib.UcsaError("adjacency must be the (offsets, neighbours) pair of mesh_adjacency")
+    for t, name in ((offsets, "offsets"), (neighbours, "neighbours")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1
+                and t.is_contiguous() and t.device == offsets.device):
+            raise _lib.UcsaError(f"adjacency: {name} must be a contiguous int32 vector on the "
+                                 "GPU, both on one device")
+    if offsets.numel() < 1:
+        raise _lib.UcsaError("adjacency: offsets has V + 1 entries, got none")
+    _on_current_device(offsets, "adjacency")
+    V = offsets.numel() - 1
+    labels = torch.empty(V, dtype=torch.int32, device=offsets.device)
+    check(lib().ucsa_graph_components(_ptr(offsets), _ptr(neighbours), V, neighbours.numel(),
+                                      _ptr(labels), _stream()), "ucsa_graph_components")
+    return labels
+
+
+def component_sizes(labels):
+    """The size of each element's component -> int32 of ``labels``' shape:
+    the number of elements that carry ``labels[x]``, 0 where ``labels[x]`` < 0.
+    ``labels`` int32 on the GPU, any shape, as ``voxel_components`` /
+    ``mesh_components`` give it (values below the number of elements); it is not
+    modified.  Contract of ucsa_component_sizes (include/ucsa_hip.h)."""
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int32):
+        raise _lib.UcsaError("labels must be an int32 tensor on the GPU: the HIP path has no "
+                             "CPU fallback")
+    if labels.numel() > 0x7FFFFFFF:
+        raise _lib.UcsaError("labels must have at most 2^31-1 elements")
+    _on_current_device(labels, "labels")
+    lab = labels.contiguous()
+    sizes = torch.empty_like(lab)
+    scratch = torch.empty_like(lab)
+    check(lib().ucsa_component_sizes(_ptr(lab), _ptr(sizes), _ptr(scratch), lab.numel(),
+                                     _stream()), "ucsa_component_sizes")
+    return sizes

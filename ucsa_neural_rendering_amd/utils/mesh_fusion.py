@@ -148,3 +148,58 @@ def fuse_views(mesh, poses, intrinsics, H, W, near, label_maps, depth_maps=None,
             "winner": res["winner"].cpu().numpy().view(np.uint64),
             "observed": int((labels > 0).sum()),
             "rasterize_ms": 1e3 * t_r, "accumulate_ms": 1e3 * t_a}
+
+
+def filter_mesh_components(mesh, min_vertices=0, keep_largest=None, device="cuda"):
+    """Drop the small connected components of a mesh: the floaters of a
+    reconstruction.  ``mesh`` is a dict as ``load_mesh`` gives it (numpy: verts
+    [V,3], faces [F,3] int32, optional normals / rgb / labels per vertex).  Kept
+    are the components (over the mesh's edges; a vertex no face uses is a
+    component of one) with at least ``min_vertices`` vertices and, if
+    ``keep_largest`` = K is given, among the K with the most vertices, ties
+    going to the component with the smaller label (its smallest vertex index).
+    -> (new dict, statistics): verts, normals, rgb and labels compacted, faces
+    renumbered, surviving vertices and faces in their former relative order,
+    every other entry passed on, plus ``vertex_index`` / ``face_index`` (int64:
+    which of the input's vertices and faces survive);
+    {"components": n, "removed_components": m, "removed_vertices": k,
+    "largest": s}.  The labelling runs in the kernels (``ops.mesh_adjacency``,
+    ``ops.mesh_components``, ``ops.component_sizes``); the compaction is torch
+    indexing."""
+    if keep_largest is not None and int(keep_largest) < 1:
+        raise ValueError("keep_largest must be >= 1")
+    dev = torch.device(device)
+    verts = np.asarray(mesh["verts"])
+    V = int(verts.shape[0])
+    faces = torch.from_numpy(np.ascontiguousarray(mesh["faces"], np.int32)).to(dev)
+    labels = ops.mesh_components(ops.mesh_adjacency(faces, V))
+    sizes = ops.component_sizes(labels).long()
+    ids = torch.arange(V, device=dev)
+    roots = ids[labels.long() == ids]                      # ascending: by label
+    root_sizes = sizes[roots]
+    keep_root = root_sizes >= int(min_vertices)
+    if keep_largest is not None:
+        # by size, largest first; a stable sort keeps equal sizes in label order
+        order = torch.sort(root_sizes, descending=True, stable=True).indices
+        top = torch.zeros_like(keep_root)
+        top[order[:int(keep_largest)]] = True
+        keep_root &= top
+    keep_label = torch.zeros(V, dtype=torch.bool, device=dev)
+    keep_label[roots[keep_root]] = True
+    keep_v = keep_label[labels.long()] if V else keep_label
+    new_id = torch.cumsum(keep_v.long(), 0) - 1
+    fl = faces.long()
+    keep_f = keep_v[fl].all(1) if fl.numel() else torch.zeros(0, dtype=torch.bool, device=dev)
+    new_faces = new_id[fl[keep_f]].to(torch.int32)
+    vi, fi = ids[keep_v].cpu().numpy(), torch.nonzero(keep_f).view(-1).cpu().numpy()
+    out = dict(mesh)
+    for k in ("verts", "normals", "rgb", "labels"):
+        if mesh.get(k) is not None:
+            out[k] = np.ascontiguousarray(np.asarray(mesh[k])[vi])
+    out["faces"] = new_faces.cpu().numpy().reshape(-1, 3)
+    out["vertex_index"], out["face_index"] = vi, fi
+    gone = ~keep_root
+    stats = {"components": int(roots.numel()), "removed_components": int(gone.sum()),
+             "removed_vertices": int(root_sizes[gone].sum()),
+             "largest": int(root_sizes.max()) if roots.numel() else 0}
+    return out, stats

@@ -13,7 +13,13 @@ with an unobserved corner (no second sheet one truncation distance behind the
 walls).  Per-voxel class votes and the ray-cast model view of the volume are in
 ``utils/voxel_map.py``.  Out of scope: sparse / hashed voxel blocks, bilinear
 depth lookup, distance- or angle-dependent weights, pose refinement, anything in
-the training loop."""
+the training loop.
+
+``remove_small_components`` drops the floaters first: the specks of truncation
+band that a few bad depth pixels leave in observed free space.  The band
+(``band_mask``) is labelled by ``ops.voxel_components``, sized by
+``ops.component_sizes``, and every component below a voxel count goes back to
+the volume's empty state, so that neither the mesh nor the ray-caster sees it."""
 from __future__ import annotations
 
 import time
@@ -71,9 +77,54 @@ def extract_mesh(volume, min_weight=1):
     return verts, faces, normals, rgb
 
 
+def band_mask(volume, min_weight=1):
+    """bool [nx,ny,nz]: the observed voxels that are not free space,
+    ``(weight >= min_weight) & (tsdf < 1)``.  A NaN weight is not observed, as
+    everywhere else."""
+    return (volume["weight"] >= float(min_weight)) & (volume["tsdf"] < 1.0)
+
+
+def component_stats(sizes, is_root, min_size):
+    """``sizes`` int32 (``ops.component_sizes``), ``is_root`` bool of the same
+    shape (one element per component) -> the statistics dict; the elements of
+    the components below ``min_size`` count as removed."""
+    root_sizes = sizes[is_root]
+    small = root_sizes < int(min_size)
+    return {"components": int(root_sizes.numel()), "removed_components": int(small.sum()),
+            "removed": int(root_sizes[small].sum()),
+            "largest": int(root_sizes.max()) if root_sizes.numel() else 0}
+
+
+def remove_small_components(volume, min_voxels, connectivity=26, min_weight=1):
+    """Return every voxel of ``band_mask(volume, min_weight)`` whose component
+    (``connectivity`` 6 or 26) has fewer than ``min_voxels`` voxels to
+    ``ops.tsdf_volume``'s empty state, in place: tsdf 1, weight 0, rgb 0.  The
+    cleared voxels are unobserved again: ``marching_cubes(valid=)`` and
+    ``raycast_tsdf`` ignore them and a later ``integrate_tsdf`` restarts them
+    clean.  -> {"components": n, "removed_components": m, "removed_voxels": k,
+    "largest": s}.  ``min_voxels`` <= 1 touches nothing.  The labelling and the
+    counts are the kernels'; the clear is torch indexing."""
+    band = band_mask(volume, min_weight)
+    labels = ops.voxel_components(band, connectivity)
+    sizes = ops.component_sizes(labels)
+    n = labels.numel()
+    is_root = labels.view(-1) == torch.arange(n, dtype=torch.int32, device=labels.device)
+    st = component_stats(sizes.view(-1), is_root, min_voxels)
+    out = {"components": st["components"], "removed_components": st["removed_components"],
+           "removed_voxels": st["removed"], "largest": st["largest"]}
+    if int(min_voxels) > 1 and out["removed_voxels"]:
+        drop = band & (sizes < int(min_voxels))
+        volume["tsdf"][drop] = 1.0
+        volume["weight"][drop] = 0.0
+        if volume.get("rgb") is not None:
+            volume["rgb"][drop] = 0.0
+    return out
+
+
 def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=None,
                      voxel=0.05, trunc=None, min_weight=1, batch=16, max_weight=65504.0,
-                     depth_min=1e-6, depth_max=3.0e38, device="cuda"):
+                     depth_min=1e-6, depth_max=3.0e38, device="cuda", min_component=0,
+                     component_connectivity=26):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps``: a sequence
     or a callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), read
     batch by batch; ``color_maps`` likewise ``i -> [H,W,3]`` uint8 or None;
@@ -84,7 +135,10 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     frame): verts [V,3] f32, faces [F,3] int32, normals [V,3] f32, rgb [V,3]
     f32 in [0,1] or None, labels None; plus ``dims``, ``origin``, ``spacing``,
     ``observed`` (share of voxels with weight >= min_weight) and the wall-time
-    split ``integrate_ms`` / ``extract_ms`` (device-synchronised host clock)."""
+    split ``integrate_ms`` / ``extract_ms`` (device-synchronised host clock).
+    ``min_component`` > 0 runs ``remove_small_components`` with that voxel count
+    (and ``component_connectivity``) before the mesh is extracted and adds its
+    statistics as ``components``."""
     dev = torch.device(device)
     voxel = float(voxel)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
@@ -122,12 +176,18 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                            depth_min=depth_min, depth_max=depth_max)
         torch.cuda.synchronize()
         t_i += time.perf_counter() - t0
+    stats = None
+    if int(min_component) > 0:
+        stats = remove_small_components(vol, int(min_component), component_connectivity,
+                                        min_weight)
+        torch.cuda.synchronize()
     t0 = time.perf_counter()
     verts, faces, normals, rgb = extract_mesh(vol, min_weight)
     torch.cuda.synchronize()
     t_e = time.perf_counter() - t0
     observed = float((vol["weight"] >= float(min_weight)).float().mean())
-    return {"verts": verts.cpu().numpy(), "faces": faces.cpu().numpy(),
+    extra = {} if stats is None else {"components": stats}
+    return {**extra, "verts": verts.cpu().numpy(), "faces": faces.cpu().numpy(),
             "normals": normals.cpu().numpy(),
             "rgb": None if rgb is None else rgb.cpu().numpy(), "labels": None,
             "dims": tuple(dims), "origin": vol["origin"], "spacing": vol["spacing"],

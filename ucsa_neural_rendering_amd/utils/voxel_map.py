@@ -27,14 +27,14 @@ import torch
 
 from .. import ops
 from .mesh_fusion import _batch, _score_batch
-from .tsdf_fusion import depth_points_aabb
+from .tsdf_fusion import depth_points_aabb, remove_small_components
 
 
 def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_maps=None,
                         aabb=None, voxel=0.05, trunc=None, batch=16, num_classes=40,
                         min_votes=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
                         device="cuda", score_maps=None, min_margin=0, smooth=0,
-                        smooth_neighbourhood=26):
+                        smooth_neighbourhood=26, min_component=0, component_connectivity=26):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps`` /
     ``label_maps`` / ``color_maps``: sequences or callables ``i -> [H,W]`` fp32
     z-depth in scene units (0 = none), ``[H,W]`` uint8 class ids (0 = no vote),
@@ -58,7 +58,14 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
     ``smooth_neighbourhood`` 6 or 26) before it is resolved; the dict then
     carries the pooled table, and ``min_votes`` / ``min_margin`` count pooled
     units (one pass over 26 neighbours multiplies a flat region's sums by up to
-    27).  0 leaves everything as it was."""
+    27).  0 leaves everything as it was.
+    ``min_component`` = N > 0 returns the components of the truncation band with
+    fewer than N voxels to the unobserved state first
+    (``tsdf_fusion.remove_small_components``, ``component_connectivity`` 6 or
+    26), before the table is pooled and resolved and before any ray-cast: the
+    floaters carry no label and no ray hits them; the dict then has their
+    statistics as ``components``.  The table itself is not cleared: a removed
+    voxel's column is never read again."""
     smooth = int(smooth)
     if smooth < 0:
         raise ValueError("smooth must be >= 0")
@@ -109,17 +116,21 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
         else:
             ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
                                   depth_max=depth_max)
+    extra = {}
+    if int(min_component) > 0:
+        extra["components"] = remove_small_components(vol, int(min_component),
+                                                      component_connectivity)
     if smooth:
         votes = ops.smooth_voxel_table(votes, vol, neighbourhood=smooth_neighbourhood,
                                        iterations=smooth)
     if soft:
         res = ops.resolve_voxel_evidence(votes, min_votes, min_margin)
-        return {"volume": vol, "evidence": votes, "labels": res["label"], "views": res["views"],
+        return {**extra, "volume": vol, "evidence": votes, "labels": res["label"], "views": res["views"],
                 "best": res["best"], "margin": res["margin"], "dims": tuple(dims),
                 "observed": float((vol["weight"] >= 1.0).float().mean()),
                 "labelled": float((res["label"] > 0).float().mean())}
     res = ops.resolve_voxel_labels(votes, min_votes)
-    return {"volume": vol, "votes": votes, "labels": res["label"], "total": res["total"],
+    return {**extra, "volume": vol, "votes": votes, "labels": res["label"], "total": res["total"],
             "winner": res["winner"], "dims": tuple(dims),
             "observed": float((vol["weight"] >= 1.0).float().mean()),
             "labelled": float((res["label"] > 0).float().mean())}
