@@ -1753,6 +1753,65 @@ int32_t ucsa_graph_components(const int32_t* offsets, const int32_t* neighbours,
 int32_t ucsa_component_sizes(const int32_t* labels, int32_t* sizes, int32_t* scratch,
                              uint64_t n, void* stream);
 
+/* ---- nearest point within a radius (not in the reference) ----
+ * For each query the nearest of n points within max_dist: what carries labels
+ * from one mesh to another and what accuracy, completeness and F-score of a
+ * mesh are made of.  tests/nearest_numpy.py states the contract as plain brute
+ * force and the outputs match it byte for byte:
+ *   every operation is rounded to float32 and nothing is fused; per pair
+ *   dx = q.x - p.x (dy, dz likewise), d2 = (dx*dx + dy*dy) + dz*dz; point j
+ *   matches query i iff d2 <= max_dist*max_dist (inclusive; a NaN compares
+ *   false, so a non-finite point never matches and a non-finite query matches
+ *   nothing); index[i] = the matching j with the smallest d2, among equal d2 the
+ *   smallest j; dist2[i] = that d2; no match: index[i] = -1, dist2[i] = +inf.
+ * The result therefore does not depend on the cell size, on the grid's origin
+ * or on the order in which queries are processed.  The grid is cells of edge
+ * `cell` from `origin`, dims[0] x dims[1] x dims[2] of them, linear index
+ * (x*dims[1] + y)*dims[2] + z; origin[3] and dims[3] are host arrays.
+ *
+ * ucsa_point_cell_keys: points [n][3] float32 -> keys [n] int32.  The cell
+ *   coordinate is floor((p - origin) / cell) per axis (float32, the division
+ *   correctly rounded), clamped into the grid as a float before it becomes an
+ *   integer.  clamp = 1 (the points): a finite point outside the box gets its
+ *   border cell, a non-finite point the key dims[0]*dims[1]*dims[2], which sorts
+ *   last and is never visited.  clamp = 0 (a sort key for queries): a point
+ *   outside the grid gets that last key as well.
+ *   A stable sort of the keys gives `order`; offsets [cells + 1] int32 is the
+ *   position of each cell's first point in that order (offsets[cells] = the
+ *   number of finite points); sorted_points [n][4] float32 holds x, y, z of
+ *   point order[k] and, in w, the bits of the int32 order[k] (ops.point_grid
+ *   builds the three in torch).
+ * ucsa_nearest_point: one lane per query; lane t takes query q_order[t]
+ *   (int32 [nq], a permutation; NULL: query t) and writes that query's slots of
+ *   index [nq] int32 and dist2 [nq] float32.  The lane walks Chebyshev rings of
+ *   cells around the query's clamped cell; a run of cells along z costs two
+ *   offset reads.  After each ring every slab of unvisited cells whose near
+ *   wall is farther than min(best d2, max_dist^2) is cut off, strictly and with
+ *   a margin: the gap to the wall is shortened by 2^-20 * (|origin| + |origin +
+ *   dims*cell| + |q|) on that axis and its square must exceed the bound times
+ *   1 + 2^-20, which covers the rounding of the cell assignment, of the wall
+ *   and of d2, and keeps ties (an unvisited point's d2 is strictly larger).  The
+ *   walk ends when no slab is left; every loop is bounded by dims; offsets are
+ *   clamped into [0, n].  No atomics, no LDS, no lane waits for another.  A
+ *   query farther than max_dist from the box [origin, origin + dims*cell]
+ *   writes -1 without a ring: points are expected inside that box (as
+ *   ops.point_grid makes it); a point outside it sits in a border cell and is
+ *   still found by every query within max_dist of the box.
+ *   Cost: a query with nothing within max_dist walks every cell within
+ *   max_dist; max_dist = the scene's diagonal costs what brute force costs.
+ *   Limits (both entry points): origin finite, cell > 0 and finite with a finite
+ *   far corner, dims >= 1 each with at most 2^24 cells, n and nq <= 2^31-1,
+ *   max_dist > 0 with a finite float32 square, sorted_points 16-byte aligned; an
+ *   argument error comes before any launch and nothing is written.  n == 0:
+ *   every query gets -1 (sorted_points and offsets may be NULL); nq == 0:
+ *   returns 0, launches nothing. */
+int32_t ucsa_point_cell_keys(const float* points, uint32_t n, const float* origin, float cell,
+                             const uint32_t* dims, uint32_t clamp, int32_t* keys, void* stream);
+int32_t ucsa_nearest_point(const float* sorted_points, const int32_t* offsets, uint32_t n,
+                           const float* origin, float cell, const uint32_t* dims,
+                           const float* queries, const int32_t* q_order, uint32_t nq,
+                           float max_dist, int32_t* index, float* dist2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ sibling of ``scripts/render_mesh_labels.py``, which goes the other way.
         [--pose_frame] --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] \\
         [--depth_tol METRES] [--min_votes K] [--every N] --out FUSED.ply \\
         [--render] [--score] [--scores {seg_evidence,<dir>} [--min_margin M]] \\
-        [--smooth N] [--min_component N]
+        [--smooth N] [--min_component N] [--gt_mesh G.ply [--gt_max_dist M]]
 
 ``--labels``: ``label_40`` is ``<scene>/label_40``; ``seg_label`` / ``nerf_label``
 are ``<scene>/<exp_name>/...`` (the predict pass's output); anything else is a
@@ -45,7 +45,12 @@ default) changes nothing.
 vertices right after loading it (``filter_mesh_components``: the floaters of a
 reconstruction), so that they neither collect votes nor occlude; the written
 mesh is the filtered one and the statistics are printed.  0 (the default)
-changes nothing."""
+changes nothing.
+``--gt_mesh G.ply`` scores the fused labels in 3D (``utils/mesh_eval.score_labels_3d``):
+every labelled vertex of G, read in the frame ``--mesh`` is read in, takes the
+label of the nearest fused vertex within ``--gt_max_dist`` scene units (default
+0.2), and one ``3d: {...}`` line is printed.  Without the flag the output is
+unchanged."""
 import argparse
 import json
 import os
@@ -83,6 +88,10 @@ def parse_args(argv=None):
                    help="pool the table N times over edge neighbours before resolving; "
                         "--min_votes / --min_margin then count pooled units, which grow with "
                         "pooling (default 0: off)")
+    p.add_argument("--gt_mesh", default=None,
+                   help="score the fused labels in 3D at this labelled mesh's vertices (.ply)")
+    p.add_argument("--gt_max_dist", type=float, default=0.2,
+                   help="with --gt_mesh: search radius, scene units")
     p.add_argument("--exp_name", default=None)
     p.add_argument("--depth_tol", type=float, default=None, help="metres")
     p.add_argument("--min_votes", type=int, default=1,
@@ -193,6 +202,14 @@ def main(argv=None):
         rec["smooth"] = a.smooth
     if components is not None:
         rec["components"] = components
+    if a.gt_mesh is not None:
+        from ucsa_neural_rendering_amd.utils.mesh_eval import score_labels_3d
+        gt = load_mesh(a.gt_mesh, pose_frame=a.pose_frame, one_m_to_scene_uom=uom)
+        if gt["labels"] is None:
+            raise SystemExit(f"--gt_mesh {a.gt_mesh} carries no labels")
+        rec["3d"] = score_labels_3d(mesh["verts"], fused["labels"], gt["verts"], gt["labels"],
+                                    a.gt_max_dist, a.num_classes)
+        print("3d: " + json.dumps(rec["3d"]))
     if a.render or a.score:
         out_dir = a.out_dir or os.path.join(a.scene_root, a.exp_name or "")
         os.makedirs(os.path.join(out_dir, "map_label"), exist_ok=True)

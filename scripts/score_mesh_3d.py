@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Score a fused mesh in 3D against a ground-truth mesh (GPU: ``ops.point_grid`` +
+``ops.nearest_point``, ``utils/mesh_eval.py``): the labels by ScanNet's protocol
+-- every ground-truth vertex takes the label of the nearest predicted vertex --
+and the geometry as accuracy, completeness, chamfer and F-score.
+
+    python scripts/score_mesh_3d.py --pred P.ply --gt G.ply [--max_dist M] \\
+        [--threshold T] [--pred_pose_frame] [--gt_pose_frame] [--one_m_to_scene_uom U] \\
+        [--gt_transform T.txt] [--num_classes C]
+
+Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
+read a mesh in the frame of the JSON poses in metres (what the export and fusion
+scripts write with ``--pose_frame``) and take it to the NGP frame, scaled by
+``--one_m_to_scene_uom``.  ``--gt_transform`` names a text file with a 4 x 4
+rigid motion applied to the ground-truth vertices after that; finding it is not
+done here.  ``--max_dist`` (scene units, default 0.2) bounds the search: a vertex
+with nothing within it is unmatched (its label counts as wrong, its distance as
+``max_dist``).  ``--threshold`` (default 0.05) is the F-score's distance.
+Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ucsa_neural_rendering_amd.utils.mesh_eval import (  # noqa: E402
+    mesh_distance, score_labels_3d)
+from ucsa_neural_rendering_amd.utils.mesh_render import load_mesh  # noqa: E402
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--pred", required=True, help="the fused mesh (.ply)")
+    p.add_argument("--gt", required=True, help="the ground-truth mesh (.ply)")
+    p.add_argument("--max_dist", type=float, default=0.2, help="search radius, scene units")
+    p.add_argument("--threshold", type=float, default=0.05, help="F-score distance, scene units")
+    p.add_argument("--pred_pose_frame", action="store_true")
+    p.add_argument("--gt_pose_frame", action="store_true")
+    p.add_argument("--one_m_to_scene_uom", type=float, default=None)
+    p.add_argument("--gt_transform", default=None, help="text file: 4 x 4 rigid motion for --gt")
+    p.add_argument("--num_classes", type=int, default=40)
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    if not (a.max_dist > 0 and a.threshold > 0):
+        raise SystemExit("--max_dist and --threshold must be > 0")
+    pred = load_mesh(a.pred, pose_frame=a.pred_pose_frame, one_m_to_scene_uom=a.one_m_to_scene_uom)
+    gt = load_mesh(a.gt, pose_frame=a.gt_pose_frame, one_m_to_scene_uom=a.one_m_to_scene_uom)
+    gv = gt["verts"]
+    if a.gt_transform is not None:
+        T = np.loadtxt(a.gt_transform, dtype=np.float64).reshape(4, 4)
+        gv = (gv.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    rec = {}
+    if pred["labels"] is not None and gt["labels"] is not None:
+        rec["3d"] = score_labels_3d(pred["verts"], pred["labels"], gv, gt["labels"], a.max_dist,
+                                    a.num_classes)
+        print("3d: " + json.dumps(rec["3d"]))
+    rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist)
+    print("geometry: " + json.dumps(rec["geometry"]))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

@@ -10,7 +10,8 @@ voxel-route sibling of ``fuse_tsdf_mesh.py`` + ``fuse_mesh_labels.py --render``.
         [--voxel METRES] [--trunc METRES] [--step METRES] [--every N] \\
         [--min_votes K] [--aabb x0 y0 z0 x1 y1 z1] [--score] \\
         [--scores {seg_evidence,<dir>} [--min_margin M]] \\
-        [--smooth N [--smooth_neighbourhood {6,26}]]
+        [--smooth N [--smooth_neighbourhood {6,26}]] \\
+        [--gt_mesh G.ply [--gt_pose_frame] [--gt_max_dist M]]
 
 Writes ``D/map_label/<stem>.png`` (uint8 NYU40 id, 0 = nothing) and
 ``D/map_depth/<stem>.png`` (uint16 millimetres, 0 = nothing; the layout of
@@ -39,7 +40,13 @@ correlated mistakes gain less.  0 (the default) changes nothing.
 ``--min_component N`` returns the connected components of the truncation band
 with fewer than N voxels to the unobserved state before the table is resolved
 and the volume ray-cast (``remove_small_components``: no ray hits a floater any
-more) and prints their statistics; 0 (the default) changes nothing."""
+more) and prints their statistics; 0 (the default) changes nothing.
+``--gt_mesh G.ply`` scores the voxel map in 3D
+(``utils/mesh_eval.score_voxel_labels_3d``): every labelled vertex of G (NGP
+frame, or with ``--gt_pose_frame`` the frame of the JSON poses in metres) takes
+the label of the nearest labelled voxel's centre within ``--gt_max_dist`` scene
+units (default 0.2), and one ``3d: {...}`` line is printed.  Without the flag
+the output is unchanged."""
 import argparse
 import json
 import os
@@ -76,6 +83,12 @@ def parse_args(argv=None):
     p.add_argument("--min_component", type=int, default=0,
                    help="drop band components with fewer voxels than this (default 0: off)")
     p.add_argument("--component_connectivity", type=int, choices=(6, 26), default=26)
+    p.add_argument("--gt_mesh", default=None,
+                   help="score the voxel map in 3D at this labelled mesh's vertices (.ply)")
+    p.add_argument("--gt_pose_frame", action="store_true",
+                   help="the ground-truth mesh is in the JSON pose frame, in metres")
+    p.add_argument("--gt_max_dist", type=float, default=0.2,
+                   help="with --gt_mesh: search radius, scene units")
     p.add_argument("--exp_name", default=None)
     p.add_argument("--out_dir", required=True, help="where map_label/ and map_depth/ go")
     p.add_argument("--voxel", type=float, default=0.04, help="metres")
@@ -212,6 +225,15 @@ def main(argv=None):
     if "components" in fused:
         rec["components"] = fused["components"]
         print("components: " + json.dumps(fused["components"]))
+    if a.gt_mesh is not None:
+        from ucsa_neural_rendering_amd.utils.mesh_eval import score_voxel_labels_3d
+        from ucsa_neural_rendering_amd.utils.mesh_render import load_mesh
+        gt = load_mesh(a.gt_mesh, pose_frame=a.gt_pose_frame, one_m_to_scene_uom=uom)
+        if gt["labels"] is None:
+            raise SystemExit(f"--gt_mesh {a.gt_mesh} carries no labels")
+        rec["3d"] = score_voxel_labels_3d(vol, fused["labels"], gt["verts"], gt["labels"],
+                                          a.gt_max_dist, a.num_classes)
+        print("3d: " + json.dumps(rec["3d"]))
     if a.score:
         truth = np.stack([png(os.path.join(a.scene_root, "label_40"), i) for i in range(n)])
         given = np.stack([png(src, i) if src is not None else codes_argmax(codes(i), H, W)

@@ -347,6 +347,11 @@ SIGNATURES = {
     "ucsa_voxel_components": (C.c_int32, [_p, _p, _u32, _u32, _u32, _u32, _p]),
     "ucsa_graph_components": (C.c_int32, [_p, _p, _u32, C.c_uint64, _p, _p]),
     "ucsa_component_sizes": (C.c_int32, [_p, _p, _p, C.c_uint64, _p]),
+    # ---- nearest point within a radius (cell grid) ----
+    "ucsa_point_cell_keys": (C.c_int32, [_p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _u32, _p,
+                                         _p]),
+    "ucsa_nearest_point": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _p,
+                                       _u32, _f, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

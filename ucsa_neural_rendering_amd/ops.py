@@ -2361,3 +2361,124 @@ def component_sizes(labels):
     check(lib().ucsa_component_sizes(_ptr(lab), _ptr(sizes), _ptr(scratch), lab.numel(),
                                      _stream()), "ucsa_component_sizes")
     return sizes
+
+
+# ---------------------------------------------------------------------------
+# nearest point within a radius (cell grid)
+# ---------------------------------------------------------------------------
+POINT_GRID_MAX_CELLS = 1 << 24
+
+
+def _points3(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 2 and t.shape[1] == 3):
+        raise _lib.UcsaError(f"{name} must be an [N,3] tensor on the GPU: the HIP path has no "
+                             "CPU fallback")
+    if t.shape[0] > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"{name} must have at most 2^31-1 rows")
+    return _f32(t, name)
+
+
+def _grid_shape(lo, hi, n, cell):
+    """origin, cell and dims from the finite points' box: host arithmetic in
+    float64 on float32 corners.  The choice changes time only, never a result."""
+    ext = [float(b) - float(a) for a, b in zip(lo, hi)]
+    big = max(ext)
+    if cell is None:
+        pad = [e + max(big, 1e-30) * 1e-3 for e in ext]
+        cell = (pad[0] * pad[1] * pad[2] / max(n, 1)) ** (1.0 / 3.0)
+    cell = float(cell)
+    if not (cell > 0 and math.isfinite(cell)):
+        raise _lib.UcsaError(f"cell must be positive and finite, got {cell!r}")
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    cell = f32(max(cell, big / 1024.0, 1e-30))
+    # more than 64 cells per point buy nothing and cost an offset each
+    cap = min(POINT_GRID_MAX_CELLS, max(4096, 64 * n))
+    while True:
+        dims = tuple(int(math.floor(e / cell)) + 1 for e in ext)
+        if dims[0] * dims[1] * dims[2] <= cap:
+            return cell, dims
+        cell = f32(cell * 1.25)
+
+
+def point_grid(points, cell=None):
+    """A uniform cell grid over ``points`` [N,3] (float32 on the GPU) for
+    ``nearest_point`` -> dict: ``origin`` (3 floats) and ``dims`` (3 ints) from
+    the finite points' bounding box, ``cell``, ``offsets`` int32 [cells+1],
+    ``order`` int32 [N] (the points by cell, ties by index; non-finite points
+    last), ``sorted_points`` float32 [N,4] (x, y, z and the bits of the original
+    index in w), ``n``.  The default cell is the cube root of the padded box's
+    volume per point, at least 1/1024 of the largest extent, and raised until
+    the grid has at most min(2^24, max(4096, 64 N)) cells; an explicit ``cell``
+    is raised the same way.  The cell changes time only, never a result.  The
+    keys are a kernel (ucsa_point_cell_keys), the sort is torch on the device."""
+    pts = _points3(points, "points")
+    n = int(pts.shape[0])
+    dev = pts.device
+    ok = torch.isfinite(pts).all(1)
+    if n and bool(ok.any()):
+        good = pts[ok]
+        lo, hi = good.min(0).values.tolist(), good.max(0).values.tolist()
+    else:
+        lo = hi = [0.0, 0.0, 0.0]
+    cell, dims = _grid_shape(lo, hi, n, cell)
+    ncells = dims[0] * dims[1] * dims[2]
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib().ucsa_point_cell_keys(_ptr(pts), n, fvec(lo), cell, (C.c_uint32 * 3)(*dims), 1,
+                                     _ptr(keys), _stream()), "ucsa_point_cell_keys")
+    order = torch.sort(keys, stable=True).indices.to(torch.int32)
+    offsets = torch.searchsorted(keys[order.long()].contiguous(),
+                                 torch.arange(ncells + 1, dtype=torch.int32, device=dev)
+                                 ).to(torch.int32)
+    packed = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    packed[:, :3] = pts[order.long()].view(torch.int32)
+    packed[:, 3] = order
+    return {"origin": tuple(float(v) for v in lo), "cell": cell, "dims": dims,
+            "offsets": offsets, "order": order, "sorted_points": packed.view(torch.float32),
+            "n": n}
+
+
+def nearest_point(grid, queries, max_dist: float, sort_queries: bool = True):
+    """For each of ``queries`` [Q,3] (float32 on the GPU) the nearest point of
+    ``grid`` (``point_grid``'s dict) within ``max_dist`` -> (``index`` int32 [Q],
+    ``dist2`` float32 [Q]) on the device: the original index of the nearest
+    point and the squared distance, -1 and +inf where no point lies within
+    ``max_dist`` (inclusive).  Among equally near points the smallest index
+    wins; a non-finite point or query matches nothing.  ``max_dist`` is required
+    and finite: an unbounded search is not offered, and a query with nothing
+    near walks every cell within ``max_dist``, so passing the scene's diagonal
+    costs what a brute-force search costs for such queries.  ``sort_queries``
+    hands the queries to the kernel in cell order, so that a wave's lanes walk
+    the same cells; it changes time only.  Contract of ucsa_nearest_point
+    (include/ucsa_hip.h)."""
+    q = _points3(queries, "queries")
+    try:
+        sp, offsets = grid["sorted_points"], grid["offsets"]
+        origin, cell, dims, n = grid["origin"], float(grid["cell"]), grid["dims"], int(grid["n"])
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("grid must be the dict of ops.point_grid")
+    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if not (torch.is_tensor(sp) and sp.is_cuda and sp.dtype == torch.float32 and sp.is_contiguous()
+            and tuple(sp.shape) == (n, 4) and torch.is_tensor(offsets)
+            and offsets.dtype == torch.int32 and offsets.is_contiguous()
+            and offsets.device == sp.device and offsets.numel() == ncells + 1):
+        raise _lib.UcsaError("grid: sorted_points must be float32 [n,4] and offsets int32 "
+                             "[cells+1], contiguous, on one GPU")
+    if sp.device != q.device:
+        raise _lib.UcsaError(f"the grid is on {sp.device}, the queries on {q.device}")
+    max_dist = float(max_dist)
+    if not (max_dist > 0 and math.isfinite(max_dist)):
+        raise _lib.UcsaError(f"max_dist must be positive and finite, got {max_dist!r}")
+    nq = int(q.shape[0])
+    org, dm = fvec(origin), (C.c_uint32 * 3)(*[int(d) for d in dims])
+    q_order = None
+    if sort_queries and nq and n:
+        keys = torch.empty(nq, dtype=torch.int32, device=q.device)
+        check(lib().ucsa_point_cell_keys(_ptr(q), nq, org, cell, dm, 0, _ptr(keys), _stream()),
+              "ucsa_point_cell_keys")
+        q_order = torch.sort(keys, stable=True).indices.to(torch.int32)
+    index = torch.empty(nq, dtype=torch.int32, device=q.device)
+    dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+    check(lib().ucsa_nearest_point(_ptr(sp) if n else None, _ptr(offsets) if n else None, n, org,
+                                   cell, dm, _ptr(q), _ptr(q_order), nq, max_dist, _ptr(index),
+                                   _ptr(dist2), _stream()), "ucsa_nearest_point")
+    return index, dist2

@@ -1,0 +1,126 @@
+"""3D scores of fused maps (``ops.point_grid`` + ``ops.nearest_point``): labels
+carried from one vertex set to another by nearest neighbour, the label score of
+a fused mesh or voxel map at the vertices of a ground-truth mesh (ScanNet's
+protocol: the vertices of ``*_vh_clean_2.labels.ply`` take the label of the
+nearest predicted vertex), and the geometric score of a mesh against another
+(accuracy, completeness, chamfer, precision / recall / F-score).
+
+Meshes come as ``utils.mesh_render.load_mesh`` returns them, both in one frame
+(numpy or tensors; labels are NYU40 ids: class + 1, 0 = unknown).  Finding the
+rigid motion between two frames is not done here.  ``max_dist`` is required: a
+vertex with nothing within it is unmatched, and a query with nothing near costs
+the walk over every cell within ``max_dist``."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ops
+from .mesh_render import score_label_maps
+
+
+def _verts(v, device="cuda"):
+    t = torch.as_tensor(np.asarray(v, np.float32) if not torch.is_tensor(v) else v)
+    return t.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+
+
+def _labels(l, n, device):
+    t = torch.as_tensor(np.asarray(l) if not torch.is_tensor(l) else l).reshape(-1)
+    if t.numel() != n:
+        raise ValueError(f"{t.numel()} labels for {n} vertices")
+    return t.to(device=device, dtype=torch.int32)
+
+
+def transfer_labels(src_verts, src_labels, dst_verts, max_dist, return_match=False):
+    """The label of the nearest ``src`` vertex within ``max_dist`` at every ``dst``
+    vertex -> int32 [D] on the device; 0 where there is none.  Among equally near
+    source vertices the smallest index decides.  ``return_match``: also the
+    ``index`` (-1 = none) and ``dist2`` of ``ops.nearest_point``."""
+    src = _verts(src_verts)
+    dst = _verts(dst_verts, src.device)
+    lab = _labels(src_labels, src.shape[0], src.device)
+    index, dist2 = ops.nearest_point(ops.point_grid(src), dst, max_dist)
+    hit = index >= 0
+    out = torch.zeros(dst.shape[0], dtype=torch.int32, device=src.device)
+    if lab.numel():
+        out = torch.where(hit, lab[index.clamp_min(0).long()], out)
+    return (out, index, dist2) if return_match else out
+
+
+def _score(pred, index, gt_labels, C):
+    gt = torch.as_tensor(np.asarray(gt_labels) if not torch.is_tensor(gt_labels)
+                         else gt_labels).reshape(-1).to(pred.device)
+    if gt.numel() != pred.numel():
+        raise ValueError(f"{gt.numel()} ground-truth labels for {pred.numel()} vertices")
+    s = score_label_maps(pred.cpu().numpy(), gt.cpu().numpy(), C)
+    scored = (gt >= 1) & (gt <= C)
+    n = int(scored.sum())
+    return {"mIoU": s["mIoU"], "total_acc": s["total_acc"], "mean_acc": s["mean_acc"],
+            "vertices": n,
+            "unmatched": float(((index < 0) & scored).sum()) / n if n else float("nan")}
+
+
+def score_labels_3d(pred_verts, pred_labels, gt_verts, gt_labels, max_dist, C=40):
+    """The predicted labels at the ground-truth vertices (``transfer_labels``)
+    scored through ``score_label_maps``: ground truth 0 or above ``C`` is ignored;
+    a prediction of 0, or no predicted vertex within ``max_dist``, counts as
+    wrong, exactly as the 2D score treats it.  -> {"mIoU", "total_acc",
+    "mean_acc", "vertices" (scored), "unmatched" (the share of scored vertices
+    without a match)}."""
+    pred, index, _ = transfer_labels(pred_verts, pred_labels, gt_verts, max_dist,
+                                     return_match=True)
+    return _score(pred, index, gt_labels, C)
+
+
+def voxel_centres(volume, voxel_labels):
+    """-> (centres float32 [M,3], labels int32 [M]) of the voxels whose label is
+    > 0, on the device: ``origin + index * spacing`` in float32."""
+    lab = torch.as_tensor(voxel_labels)
+    if tuple(lab.shape) != tuple(volume["tsdf"].shape):
+        raise ValueError(f"voxel_labels {tuple(lab.shape)} against a volume of "
+                         f"{tuple(volume['tsdf'].shape)}")
+    lab = lab.to(volume["tsdf"].device)
+    ijk = torch.nonzero(lab > 0)
+    origin = torch.tensor(volume["origin"], dtype=torch.float32, device=lab.device)
+    spacing = torch.tensor(volume["spacing"], dtype=torch.float32, device=lab.device)
+    centres = origin[None, :] + ijk.to(torch.float32) * spacing[None, :]
+    return centres, lab[ijk[:, 0], ijk[:, 1], ijk[:, 2]].to(torch.int32)
+
+
+def score_voxel_labels_3d(volume, voxel_labels, gt_verts, gt_labels, max_dist, C=40):
+    """``score_labels_3d`` with the centres of the labelled voxels of a voxel map
+    (``utils.voxel_map``: the volume and its resolved labels) as the predicted
+    point set."""
+    centres, lab = voxel_centres(volume, voxel_labels)
+    return score_labels_3d(centres, lab, gt_verts, gt_labels, max_dist, C)
+
+
+def mesh_distance(pred_verts, gt_verts, threshold, max_dist):
+    """Vertex-to-vertex distances both ways -> {"accuracy": mean pred -> gt,
+    "completeness": mean gt -> pred, "chamfer": their mean, "precision": the share
+    of pred vertices within ``threshold`` of gt, "recall": the share of gt
+    vertices within ``threshold`` of pred, "fscore": their harmonic mean (0 when
+    both are 0)}.  Distances are ``sqrt(dist2)`` in float64 on the device; a
+    vertex with nothing within ``max_dist`` counts as ``max_dist`` (and is not
+    within the threshold).  An empty set gives nan for its direction."""
+    pred = _verts(pred_verts)
+    gt = _verts(gt_verts, pred.device)
+
+    def one_way(a, b):
+        if a.shape[0] == 0:
+            return float("nan"), float("nan")
+        index, dist2 = ops.nearest_point(ops.point_grid(b), a, max_dist)
+        d = torch.where(index >= 0, dist2.double().sqrt(),
+                        torch.full_like(dist2, float(max_dist), dtype=torch.float64))
+        return float(d.mean()), float(((index >= 0) & (d <= float(threshold))).double().mean())
+
+    acc, prec = one_way(pred, gt)
+    comp, rec = one_way(gt, pred)
+    if not prec + rec >= 0:                         # an empty set: nan
+        f = float("nan")
+    elif prec + rec == 0:
+        f = 0.0
+    else:
+        f = 2.0 * prec * rec / (prec + rec)
+    return {"accuracy": acc, "completeness": comp, "chamfer": 0.5 * (acc + comp),
+            "precision": prec, "recall": rec, "fscore": f}
