@@ -1812,6 +1812,86 @@ int32_t ucsa_nearest_point(const float* sorted_points, const int32_t* offsets, u
                            const float* queries, const int32_t* q_order, uint32_t nq,
                            float max_dist, int32_t* index, float* dist2, void* stream);
 
+/* ---- nearest point on a triangle mesh within a radius (not in the reference) ----
+ * For each query the nearest point of the surface of nf triangles within
+ * max_dist: what the 3D scores use when the target mesh is tessellated more
+ * coarsely than the queries.  tests/surface_numpy.py states the contract as
+ * plain brute force over all faces and the outputs match it byte for byte:
+ *   every operation is rounded to float32 and nothing is fused; with
+ *   dot(x,y) = (x0*y0 + x1*y1) + x2*y2 and, per (query q, face A B C),
+ *     a = A - q; b = B - q; c = C - q; ab = b - a; ac = c - a
+ *     d1 = dot(ab,-a); d2 = dot(ac,-a); d3 = dot(ab,-b); d4 = dot(ac,-b);
+ *     d5 = dot(ab,-c); d6 = dot(ac,-c)
+ *     vc = d1*d4 - d3*d2; vb = d5*d2 - d1*d6; va = d3*d6 - d5*d4
+ *   the first that holds decides (v, w):
+ *     d1 <= 0 and d2 <= 0                    (0, 0)
+ *     d3 >= 0 and d4 <= d3                   (1, 0)
+ *     vc <= 0 and d1 >= 0 and d3 <= 0        (d1/(d1-d3), 0)
+ *     d6 >= 0 and d5 <= d6                   (0, 1)
+ *     vb <= 0 and d2 >= 0 and d6 <= 0        (0, d2/(d2-d6))
+ *     va <= 0 and d4-d3 >= 0 and d5-d6 >= 0  wb = (d4-d3)/((d4-d3)+(d5-d6)): (1-wb, wb)
+ *     otherwise  den = 1/((va+vb)+vc); v = vb*den; w = vc*den, then as selects
+ *                (a NaN stays a NaN) v = v<0 ? 0 : v; v = v>1 ? 1 : v; t = 1-v;
+ *                w = w<0 ? 0 : w; w = w>t ? t : w
+ *   p = (a + ab*v) + ac*w per component; dist2 = (p0*p0 + p1*p1) + p2*p2.
+ *   A face matches iff dist2 <= max_dist*max_dist (inclusive; a NaN compares
+ *   false); the smallest dist2 wins, among equal ones the smallest face index.
+ *   face[i] = that face, dist2[i] = its dist2, bary[i] = ((1-v)-w, v, w); no
+ *   match: -1, +inf and a zero row.  A face with a corner index outside [0, nv)
+ *   or a non-finite corner matches nothing; a non-finite query matches nothing.
+ * The result does not depend on the cell size, on the grid's origin or on the
+ * order of the queries.  The grid is the one of ucsa_point_cell_keys; all
+ * finite vertices are expected inside its box (as ops.triangle_grid makes it).
+ *
+ * ucsa_triangle_cell_counts: verts [nv][3] float32, faces [nf][3] int32 ->
+ *   counts [nf] int32.  A lane per face: per axis the face covers the cells from
+ *   the cell of its smallest corner coordinate to the cell of its largest (the
+ *   cell of ucsa_point_cell_keys: (x - origin)/cell, clamped, floored);
+ *   counts[f] is the number of cells of that box, 0 for an invalid face.
+ * ucsa_triangle_cell_pairs: first [nf] int32 is the exclusive scan of counts
+ *   and n_pairs their sum; face f writes the linear keys of its cells, in x, y, z
+ *   order, to keys[first[f] ...] and f to pair_face at the same places: fixed
+ *   positions, no atomics.  A position outside [0, n_pairs) is not written.
+ *   A stable sort of keys gives the pairs by cell with faces ascending in a
+ *   cell; offsets [cells + 1] int32 is the position of each cell's first pair;
+ *   records [n_pairs][12] float32 holds per sorted pair A.xyz and the bits of
+ *   the int32 face index, B.xyz and 0, C.xyz and 0 (ops.triangle_grid builds
+ *   the three in torch).
+ * ucsa_nearest_triangle: one lane per query; lane t takes query q_order[t]
+ *   (int32 [nq], a permutation; NULL: query t; an entry outside [0, nq) writes
+ *   nothing) and writes that query's slots of face [nq] int32, dist2 [nq]
+ *   float32 and bary [nq][3] float32.  The walk is ucsa_nearest_point's: rings
+ *   of cells around the query's clamped cell, a run of cells along z as two
+ *   offset reads, and after each ring every slab of unvisited cells whose near
+ *   wall is farther than min(best dist2, max_dist^2) cut off.  A face none of
+ *   whose cells was visited lies with all corners, and so with its closest
+ *   point, beyond such a wall.  The margin: the gap to the wall is shortened by
+ *   2^-19 * (|origin| + |origin + dims*cell| + |q|) on that axis and its square
+ *   must exceed the bound times 1 + 2^-20 (docs/DESIGN_NOTEBOOK.md, section NT).
+ *   A face registered in several cells is evaluated more than once, which does
+ *   not change a minimum.  Every loop is bounded by dims; offsets are clamped
+ *   into [0, n_pairs]; no atomics, no LDS, no lane waits for another.  A query
+ *   farther than max_dist from the grid's box gets no match without a ring.
+ *   Limits: origin finite, cell > 0 and finite with a finite far corner, dims
+ *   >= 1 each with at most 2^24 cells, nv, nf, n_pairs and nq <= 2^31-1,
+ *   max_dist > 0 with a finite float32 square, records 16-byte aligned; an
+ *   argument error comes before any launch and nothing is written.  nf == 0 or
+ *   n_pairs == 0 in the two build calls: returns 0, launches nothing.
+ *   n_pairs == 0 in the search: every query gets no match (records and offsets
+ *   may be NULL); nq == 0: returns 0, launches nothing. */
+int32_t ucsa_triangle_cell_counts(const float* verts, uint32_t nv, const int32_t* faces,
+                                  uint32_t nf, const float* origin, float cell,
+                                  const uint32_t* dims, int32_t* counts, void* stream);
+int32_t ucsa_triangle_cell_pairs(const float* verts, uint32_t nv, const int32_t* faces,
+                                 uint32_t nf, const float* origin, float cell,
+                                 const uint32_t* dims, const int32_t* first, uint32_t n_pairs,
+                                 int32_t* keys, int32_t* pair_face, void* stream);
+int32_t ucsa_nearest_triangle(const float* records, const int32_t* offsets, uint32_t n_pairs,
+                              const float* origin, float cell, const uint32_t* dims,
+                              const float* queries, const int32_t* q_order, uint32_t nq,
+                              float max_dist, int32_t* face, float* dist2, float* bary,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

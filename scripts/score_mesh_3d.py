@@ -6,7 +6,7 @@ and the geometry as accuracy, completeness, chamfer and F-score.
 
     python scripts/score_mesh_3d.py --pred P.ply --gt G.ply [--max_dist M] \\
         [--threshold T] [--pred_pose_frame] [--gt_pose_frame] [--one_m_to_scene_uom U] \\
-        [--gt_transform T.txt] [--num_classes C]
+        [--gt_transform T.txt] [--num_classes C] [--surface]
 
 Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
 read a mesh in the frame of the JSON poses in metres (what the export and fusion
@@ -16,6 +16,11 @@ rigid motion applied to the ground-truth vertices after that; finding it is not
 done here.  ``--max_dist`` (scene units, default 0.2) bounds the search: a vertex
 with nothing within it is unmatched (its label counts as wrong, its distance as
 ``max_dist``).  ``--threshold`` (default 0.05) is the F-score's distance.
+``--surface`` uses the faces of both PLYs (``ops.triangle_grid`` +
+``ops.nearest_triangle``): labels come from the nearest point of the predicted
+surface and every distance is from a vertex to the other mesh's surface, which
+is what a coarsely tessellated ground truth needs; both lines then carry a
+``"surface"`` entry (``true`` in ``3d:``, ``[true, true]`` in ``geometry:``).
 Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
 import argparse
 import json
@@ -43,6 +48,8 @@ def parse_args(argv=None):
     p.add_argument("--one_m_to_scene_uom", type=float, default=None)
     p.add_argument("--gt_transform", default=None, help="text file: 4 x 4 rigid motion for --gt")
     p.add_argument("--num_classes", type=int, default=40)
+    p.add_argument("--surface", action="store_true",
+                   help="measure to the nearest point on the other mesh's faces, not its vertices")
     return p.parse_args(argv)
 
 
@@ -57,11 +64,17 @@ def main(argv=None):
         T = np.loadtxt(a.gt_transform, dtype=np.float64).reshape(4, 4)
         gv = (gv.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
     rec = {}
+    pf, gf = (pred["faces"], gt["faces"]) if a.surface else (None, None)
+    if a.surface and (pf is None or gf is None or not len(pf) or not len(gf)):
+        raise SystemExit("--surface needs faces in both meshes")
     if pred["labels"] is not None and gt["labels"] is not None:
         rec["3d"] = score_labels_3d(pred["verts"], pred["labels"], gv, gt["labels"], a.max_dist,
-                                    a.num_classes)
+                                    a.num_classes, pred_faces=pf)
+        if a.surface:
+            rec["3d"]["surface"] = True
         print("3d: " + json.dumps(rec["3d"]))
-    rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist)
+    rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist, pred_faces=pf,
+                                    gt_faces=gf)
     print("geometry: " + json.dumps(rec["geometry"]))
     return rec
 

@@ -352,6 +352,13 @@ SIGNATURES = {
                                          _p]),
     "ucsa_nearest_point": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _p,
                                        _u32, _f, _p, _p, _p]),
+    # ---- nearest point on a triangle mesh within a radius (cell grid of faces) ----
+    "ucsa_triangle_cell_counts": (C.c_int32, [_p, _u32, _p, _u32, C.POINTER(_f), _f,
+                                              C.POINTER(_u32), _p, _p]),
+    "ucsa_triangle_cell_pairs": (C.c_int32, [_p, _u32, _p, _u32, C.POINTER(_f), _f,
+                                             C.POINTER(_u32), _p, _u32, _p, _p, _p]),
+    "ucsa_nearest_triangle": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p,
+                                          _p, _u32, _f, _p, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

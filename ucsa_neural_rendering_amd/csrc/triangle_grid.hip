@@ -1,0 +1,385 @@
+// Nearest point on a triangle mesh within a radius over a uniform cell grid (not
+// in the reference): ucsa_triangle_cell_counts, ucsa_triangle_cell_pairs and
+// ucsa_nearest_triangle.  The contract is stated in include/ucsa_hip.h;
+// tests/surface_numpy.py restates it as plain brute force (nearest_triangle) and
+// models this file's traversal (nearest_triangle_grid, the same float32
+// expressions), and the outputs match the brute force byte for byte: the result
+// does not depend on the cell size, the origin or the order of the queries.
+//
+// k_tri_counts     a lane per face: per axis the cells [pg_cell(min corner),
+//                  pg_cell(max corner)]; the count is the product of the three
+//                  range lengths, 0 for a face with a corner index outside
+//                  [0, nv) or a non-finite corner.
+// k_tri_pairs      a lane per face: the (linear cell, face) pairs of that box in
+//                  x, y, z order at first[f] ...: fixed positions, no atomics.
+// k_nearest_tri    a lane per query: k_nearest's ring walk (point_grid.hip) over
+//                  records of three float4 per (cell, face) pair, sorted by cell
+//                  with faces ascending inside a cell: a cell's candidates are
+//                  contiguous 16-byte loads and no index is chased.  A face
+//                  registered in several cells is evaluated more than once; the
+//                  result is a minimum over a set and does not change.
+//
+// The closest point of a face (Ericson's regions on the triangle moved so that
+// the query is the origin) is evaluated without a branch: the region picks a
+// numerator and a denominator, one division follows, the region picks (v, w).
+// In every region that is the definition's expression on the definition's
+// operands (the interior's den = 1 / sum is the same division).
+//
+// Why the cut is safe (docs/DESIGN_NOTEBOOK.md, section NT): a face none of
+// whose cells was visited has all three corners beyond one cut wall (monotone
+// cell assignment, as for points); its closest point is a combination of the
+// corners with weights v, w in [0, 1], w <= fl(1 - v), so it lies beyond the
+// wall too, up to thirteen and a half roundings of coordinates no larger than
+// |o| + |top| + |q| on that axis.  The gap is shortened by S = 2^-19 of that sum
+// (32 roundings) and its square compared with B * (1 + 2^-20).  A comparison with
+// a NaN is false: no cut, more walking, the same result.
+// Every loop is bounded by the grid's dims; offsets are clamped into
+// [0, n_pairs]; no atomics, no LDS, no waiting on another thread.
+#include "cell_grid.h"
+
+namespace {
+
+constexpr float TG_KS = 2.0f * PG_K;  // 2^-19
+
+struct Corners {
+  float ax, ay, az, bx, by, bz, cx, cy, cz;
+  bool ok;
+};
+
+__device__ __forceinline__ Corners tg_corners(const float* __restrict__ verts, uint32_t nv,
+                                              const int32_t* __restrict__ faces, uint32_t f) {
+  Corners c;
+  const uint32_t i0 = (uint32_t)faces[3ull * f], i1 = (uint32_t)faces[3ull * f + 1u],
+                 i2 = (uint32_t)faces[3ull * f + 2u];  // a negative index is >= 2^31 > nv
+  c.ok = i0 < nv && i1 < nv && i2 < nv;
+  if (c.ok) {
+    c.ax = verts[3ull * i0]; c.ay = verts[3ull * i0 + 1u]; c.az = verts[3ull * i0 + 2u];
+    c.bx = verts[3ull * i1]; c.by = verts[3ull * i1 + 1u]; c.bz = verts[3ull * i1 + 2u];
+    c.cx = verts[3ull * i2]; c.cy = verts[3ull * i2 + 1u]; c.cz = verts[3ull * i2 + 2u];
+    c.ok = pg_finite3(c.ax, c.ay, c.az) && pg_finite3(c.bx, c.by, c.bz) &&
+           pg_finite3(c.cx, c.cy, c.cz);
+  }
+  return c;
+}
+
+// the face's box of cells on one axis (finite corners)
+__device__ __forceinline__ void tg_range(float a, float b, float c, float o, float cell,
+                                         uint32_t dim, uint32_t& c0, uint32_t& c1) {
+  const float mn = fminf(fminf(a, b), c), mx = fmaxf(fmaxf(a, b), c);
+  c0 = pg_cell((mn - o) / cell, dim);
+  c1 = pg_cell((mx - o) / cell, dim);
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_tri_counts(const float* __restrict__ verts,
+                                                           uint32_t nv,
+                                                           const int32_t* __restrict__ faces,
+                                                           uint32_t nf, GridArgs g,
+                                                           int32_t* __restrict__ counts) {
+  const uint32_t f = blockIdx.x * PG_THREADS + threadIdx.x;
+  if (f >= nf) return;
+  const Corners c = tg_corners(verts, nv, faces, f);
+  uint32_t n = 0;
+  if (c.ok) {
+    uint32_t x0, x1, y0, y1, z0, z1;
+    tg_range(c.ax, c.bx, c.cx, g.o[0], g.cell, g.d[0], x0, x1);
+    tg_range(c.ay, c.by, c.cy, g.o[1], g.cell, g.d[1], y0, y1);
+    tg_range(c.az, c.bz, c.cz, g.o[2], g.cell, g.d[2], z0, z1);
+    n = (x1 - x0 + 1u) * (y1 - y0 + 1u) * (z1 - z0 + 1u);  // <= cells <= 2^24
+  }
+  counts[f] = (int32_t)n;
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_tri_pairs(const float* __restrict__ verts,
+                                                          uint32_t nv,
+                                                          const int32_t* __restrict__ faces,
+                                                          uint32_t nf, GridArgs g,
+                                                          const int32_t* __restrict__ first,
+                                                          uint32_t n_pairs,
+                                                          int32_t* __restrict__ keys,
+                                                          int32_t* __restrict__ pair_face) {
+  const uint32_t f = blockIdx.x * PG_THREADS + threadIdx.x;
+  if (f >= nf) return;
+  const Corners c = tg_corners(verts, nv, faces, f);
+  if (!c.ok) return;
+  const int32_t at = first[f];
+  if (at < 0) return;
+  uint32_t x0, x1, y0, y1, z0, z1;
+  tg_range(c.ax, c.bx, c.cx, g.o[0], g.cell, g.d[0], x0, x1);
+  tg_range(c.ay, c.by, c.cy, g.o[1], g.cell, g.d[1], y0, y1);
+  tg_range(c.az, c.bz, c.cz, g.o[2], g.cell, g.d[2], z0, z1);
+  uint32_t k = (uint32_t)at;  // at most 2^24 steps from at < 2^31: no wrap
+  for (uint32_t x = x0; x <= x1; ++x)
+    for (uint32_t y = y0; y <= y1; ++y)
+      for (uint32_t z = z0; z <= z1; ++z, ++k) {
+        if (k >= n_pairs) return;  // a `first` that is not the scan of the counts
+        keys[k] = (int32_t)((x * g.d[1] + y) * g.d[2] + z);
+        pair_face[k] = (int32_t)f;
+      }
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_tri_no_match(uint32_t nq,
+                                                             int32_t* __restrict__ face,
+                                                             float* __restrict__ dist2,
+                                                             float* __restrict__ bary) {
+  const uint32_t i = blockIdx.x * PG_THREADS + threadIdx.x;
+  if (i >= nq) return;
+  face[i] = -1;
+  dist2[i] = INFINITY;
+  bary[3ull * i] = 0.0f;
+  bary[3ull * i + 1u] = 0.0f;
+  bary[3ull * i + 2u] = 0.0f;
+}
+
+struct Walk {
+  float qx, qy, qz;
+  float best;     // B = min(best dist2, max_dist^2)
+  float v, w;     // the best face's weights of its second and third corner
+  uint32_t bidx;  // PG_NONE: no match yet
+};
+
+__device__ __forceinline__ float tg_dot(float x0, float x1, float x2, float y0, float y1, float y2) {
+  return (x0 * y0 + x1 * y1) + x2 * y2;
+}
+
+// the closest point of one face to the query: (v, w) and its squared distance
+__device__ __forceinline__ void tg_closest(const float4 A, const float4 B, const float4 C,
+                                           const Walk& q, float& v, float& w, float& dist2) {
+  const float ax = A.x - q.qx, ay = A.y - q.qy, az = A.z - q.qz;
+  const float bx = B.x - q.qx, by = B.y - q.qy, bz = B.z - q.qz;
+  const float cx = C.x - q.qx, cy = C.y - q.qy, cz = C.z - q.qz;
+  const float abx = bx - ax, aby = by - ay, abz = bz - az;
+  const float acx = cx - ax, acy = cy - ay, acz = cz - az;
+  const float d1 = tg_dot(abx, aby, abz, -ax, -ay, -az), d2 = tg_dot(acx, acy, acz, -ax, -ay, -az);
+  const float d3 = tg_dot(abx, aby, abz, -bx, -by, -bz), d4 = tg_dot(acx, acy, acz, -bx, -by, -bz);
+  const float d5 = tg_dot(abx, aby, abz, -cx, -cy, -cz), d6 = tg_dot(acx, acy, acz, -cx, -cy, -cz);
+  const float vc = d1 * d4 - d3 * d2;
+  const float vb = d5 * d2 - d1 * d6;
+  const float va = d3 * d6 - d5 * d4;
+  const float e43 = d4 - d3, e56 = d5 - d6;
+  // the regions in the definition's order; the last assignment that holds is the first true
+  int region = 6;
+  region = (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f) ? 5 : region;
+  region = (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) ? 4 : region;
+  region = (d6 >= 0.0f && d5 <= d6) ? 3 : region;
+  region = (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) ? 2 : region;
+  region = (d3 >= 0.0f && d4 <= d3) ? 1 : region;
+  region = (d1 <= 0.0f && d2 <= 0.0f) ? 0 : region;
+  float num = 1.0f, den = (va + vb) + vc;
+  num = region == 5 ? e43 : num;  den = region == 5 ? e43 + e56 : den;
+  num = region == 4 ? d2 : num;   den = region == 4 ? d2 - d6 : den;
+  num = region == 2 ? d1 : num;   den = region == 2 ? d1 - d3 : den;
+  const float r = num / den;  // unused in the corner regions
+  // the interior: clamps are selects, so that a NaN stays a NaN
+  float vi = vb * r, wi = vc * r;
+  vi = vi < 0.0f ? 0.0f : vi;
+  vi = vi > 1.0f ? 1.0f : vi;
+  const float t = 1.0f - vi;
+  wi = wi < 0.0f ? 0.0f : wi;
+  wi = wi > t ? t : wi;
+  v = vi; w = wi;
+  v = region == 5 ? 1.0f - r : v;  w = region == 5 ? r : w;
+  v = region == 4 ? 0.0f : v;      w = region == 4 ? r : w;
+  v = region == 3 ? 0.0f : v;      w = region == 3 ? 1.0f : w;
+  v = region == 2 ? r : v;         w = region == 2 ? 0.0f : w;
+  v = region == 1 ? 1.0f : v;      w = region == 1 ? 0.0f : w;
+  v = region == 0 ? 0.0f : v;      w = region == 0 ? 0.0f : w;
+  const float px = (ax + abx * v) + acx * w;
+  const float py = (ay + aby * v) + acy * w;
+  const float pz = (az + abz * v) + acz * w;
+  dist2 = (px * px + py * py) + pz * pz;
+}
+
+// the candidates of the cells lin0 .. lin1 of one row (consecutive in the sorted order)
+__device__ __forceinline__ void tg_run(const float4* __restrict__ rec,
+                                       const int32_t* __restrict__ offsets, uint32_t n,
+                                       uint32_t lin0, uint32_t lin1, Walk& w) {
+  int32_t b = offsets[lin0], e = offsets[lin1 + 1u];
+  b = b < 0 ? 0 : b;
+  e = e > (int32_t)n ? (int32_t)n : e;
+  for (int32_t k = b; k < e; ++k) {  // 0 <= k < n
+    const float4 A = rec[3ull * (uint32_t)k], B = rec[3ull * (uint32_t)k + 1u],
+                 C = rec[3ull * (uint32_t)k + 2u];
+    float v, ww, d2;
+    tg_closest(A, B, C, w, v, ww, d2);
+    const uint32_t j = __float_as_uint(A.w);
+    if (d2 < w.best || (d2 == w.best && j < w.bidx)) {
+      w.best = d2;
+      w.bidx = j;
+      w.v = v;
+      w.w = ww;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_nearest_tri(const float4* __restrict__ rec,
+                                                            const int32_t* __restrict__ offsets,
+                                                            uint32_t n, GridArgs g,
+                                                            const float* __restrict__ queries,
+                                                            const int32_t* __restrict__ q_order,
+                                                            uint32_t nq, float limit2,
+                                                            int32_t* __restrict__ face,
+                                                            float* __restrict__ dist2,
+                                                            float* __restrict__ bary) {
+  const uint32_t t = blockIdx.x * PG_THREADS + threadIdx.x;
+  if (t >= nq) return;
+  const uint32_t qi = q_order ? (uint32_t)q_order[t] : t;
+  if (qi >= nq) return;  // a malformed order writes nothing outside the outputs
+  Walk w;
+  w.qx = queries[3ull * qi];
+  w.qy = queries[3ull * qi + 1u];
+  w.qz = queries[3ull * qi + 2u];
+  w.best = limit2;
+  w.bidx = PG_NONE;
+  w.v = 0.0f;
+  w.w = 0.0f;
+  const int32_t nx = (int32_t)g.d[0], ny = (int32_t)g.d[1], nz = (int32_t)g.d[2];
+  const float h = g.cell;
+  // the box's far corner and the slack of every wall distance, per axis
+  const float topx = g.o[0] + (float)g.d[0] * h, topy = g.o[1] + (float)g.d[1] * h,
+              topz = g.o[2] + (float)g.d[2] * h;
+  const float Sx = TG_KS * ((fabsf(g.o[0]) + fabsf(topx)) + fabsf(w.qx));
+  const float Sy = TG_KS * ((fabsf(g.o[1]) + fabsf(topy)) + fabsf(w.qy));
+  const float Sz = TG_KS * ((fabsf(g.o[2]) + fabsf(topz)) + fabsf(w.qz));
+  bool walk = pg_finite3(w.qx, w.qy, w.qz);
+  if (walk) {
+    // farther than max_dist from the box that holds the faces: no ring at all
+    const float ex = fmaxf(fmaxf(g.o[0] - w.qx, w.qx - topx) - Sx, 0.0f);
+    const float ey = fmaxf(fmaxf(g.o[1] - w.qy, w.qy - topy) - Sy, 0.0f);
+    const float ez = fmaxf(fmaxf(g.o[2] - w.qz, w.qz - topz) - Sz, 0.0f);
+    const float out2 = (ex * ex + ey * ey) + ez * ez;
+    walk = !(out2 > limit2 * PG_ONE_PLUS_K);
+  }
+  if (walk) {
+    const int32_t cx = (int32_t)pg_cell((w.qx - g.o[0]) / h, g.d[0]);
+    const int32_t cy = (int32_t)pg_cell((w.qy - g.o[1]) / h, g.d[1]);
+    const int32_t cz = (int32_t)pg_cell((w.qz - g.o[2]) / h, g.d[2]);
+    int32_t lox = 0, loy = 0, loz = 0, hix = nx - 1, hiy = ny - 1, hiz = nz - 1;
+    // r grows by one per pass and a slab exists only while cx + r + 1 <= hix or
+    // cx - r - 1 >= lox (and so on): at most max(nx, ny, nz) passes
+    for (int32_t r = 0;; ++r) {
+      const int32_t x0 = max(cx - r, lox), x1 = min(cx + r, hix);
+      const int32_t y0 = max(cy - r, loy), y1 = min(cy + r, hiy);
+      const int32_t z0 = max(cz - r, loz), z1 = min(cz + r, hiz);
+      for (int32_t x = x0; x <= x1; ++x) {
+        const bool xedge = x == cx - r || x == cx + r;
+        for (int32_t y = y0; y <= y1; ++y) {
+          const uint32_t row = (uint32_t)(x * ny + y) * (uint32_t)nz;
+          if (xedge || y == cy - r || y == cy + r) {
+            if (z0 <= z1) tg_run(rec, offsets, n, row + (uint32_t)z0, row + (uint32_t)z1, w);
+          } else {  // r >= 1 here: the two caps of the column
+            if (cz - r >= loz) tg_run(rec, offsets, n, row + (uint32_t)(cz - r), row + (uint32_t)(cz - r), w);
+            if (cz + r <= hiz) tg_run(rec, offsets, n, row + (uint32_t)(cz + r), row + (uint32_t)(cz + r), w);
+          }
+        }
+      }
+      const float bk = w.best * PG_ONE_PLUS_K;
+      bool left = false;
+      if (cx + r + 1 <= hix) {
+        if (pg_cut(g.o[0], h, w.qx, Sx, bk, cx + r + 1, true)) hix = cx + r; else left = true;
+      }
+      if (cx - r - 1 >= lox) {
+        if (pg_cut(g.o[0], h, w.qx, Sx, bk, cx - r, false)) lox = cx - r; else left = true;
+      }
+      if (cy + r + 1 <= hiy) {
+        if (pg_cut(g.o[1], h, w.qy, Sy, bk, cy + r + 1, true)) hiy = cy + r; else left = true;
+      }
+      if (cy - r - 1 >= loy) {
+        if (pg_cut(g.o[1], h, w.qy, Sy, bk, cy - r, false)) loy = cy - r; else left = true;
+      }
+      if (cz + r + 1 <= hiz) {
+        if (pg_cut(g.o[2], h, w.qz, Sz, bk, cz + r + 1, true)) hiz = cz + r; else left = true;
+      }
+      if (cz - r - 1 >= loz) {
+        if (pg_cut(g.o[2], h, w.qz, Sz, bk, cz - r, false)) loz = cz - r; else left = true;
+      }
+      if (!left) break;
+    }
+  }
+  const bool hit = w.bidx != PG_NONE;
+  face[qi] = hit ? (int32_t)w.bidx : -1;
+  dist2[qi] = hit ? w.best : INFINITY;
+  bary[3ull * qi] = hit ? (1.0f - w.v) - w.w : 0.0f;
+  bary[3ull * qi + 1u] = hit ? w.v : 0.0f;
+  bary[3ull * qi + 2u] = hit ? w.w : 0.0f;
+}
+
+// the arguments the two build kernels share: -> 0 or the offending argument's index + 1
+int tg_mesh_args(uint32_t nv, uint32_t nf, const float* origin, float cell, const uint32_t* dims,
+                 GridArgs& g) {
+  if (nv > 0x7FFFFFFFu) return 2;
+  if (nf > 0x7FFFFFFFu) return 4;
+  const int bad = pg_grid_args(origin, cell, dims, g);
+  return bad ? 4 + bad : 0;  // origin 4, cell 5, dims 6
+}
+
+}  // namespace
+
+extern "C" int32_t ucsa_triangle_cell_counts(const float* verts, uint32_t nv, const int32_t* faces,
+                                             uint32_t nf, const float* origin, float cell,
+                                             const uint32_t* dims, int32_t* counts, void* stream) {
+  GridArgs g;
+  const int bad = tg_mesh_args(nv, nf, origin, cell, dims, g);
+  UCSA_CHECK_ARG(bad == 0, bad - 1);
+  if (nf == 0) return 0;
+  UCSA_CHECK_ARG(nv == 0 || verts, 0);
+  UCSA_CHECK_ARG(faces, 2);
+  UCSA_CHECK_ARG(counts, 7);
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_tri_counts, dim3(ucsa_div_up(nf, PG_THREADS)), dim3(PG_THREADS), 0,
+                     (hipStream_t)stream, verts, nv, faces, nf, g, counts);
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_triangle_cell_pairs(const float* verts, uint32_t nv, const int32_t* faces,
+                                            uint32_t nf, const float* origin, float cell,
+                                            const uint32_t* dims, const int32_t* first,
+                                            uint32_t n_pairs, int32_t* keys, int32_t* pair_face,
+                                            void* stream) {
+  GridArgs g;
+  const int bad = tg_mesh_args(nv, nf, origin, cell, dims, g);
+  UCSA_CHECK_ARG(bad == 0, bad - 1);
+  UCSA_CHECK_ARG(n_pairs <= 0x7FFFFFFFu, 8);
+  if (nf == 0 || n_pairs == 0) return 0;
+  UCSA_CHECK_ARG(nv == 0 || verts, 0);
+  UCSA_CHECK_ARG(faces, 2);
+  UCSA_CHECK_ARG(first, 7);
+  UCSA_CHECK_ARG(keys, 9);
+  UCSA_CHECK_ARG(pair_face, 10);
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_tri_pairs, dim3(ucsa_div_up(nf, PG_THREADS)), dim3(PG_THREADS), 0,
+                     (hipStream_t)stream, verts, nv, faces, nf, g, first, n_pairs, keys, pair_face);
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_nearest_triangle(const float* records, const int32_t* offsets,
+                                         uint32_t n_pairs, const float* origin, float cell,
+                                         const uint32_t* dims, const float* queries,
+                                         const int32_t* q_order, uint32_t nq, float max_dist,
+                                         int32_t* face, float* dist2, float* bary, void* stream) {
+  UCSA_CHECK_ARG(n_pairs <= 0x7FFFFFFFu, 2);
+  GridArgs g;
+  const int bad = pg_grid_args(origin, cell, dims, g);
+  UCSA_CHECK_ARG(bad != 1, 3);
+  UCSA_CHECK_ARG(bad != 2, 4);
+  UCSA_CHECK_ARG(bad != 3, 5);
+  UCSA_CHECK_ARG(nq <= 0x7FFFFFFFu, 8);
+  const float limit2 = max_dist * max_dist;
+  UCSA_CHECK_ARG(max_dist > 0.0f && pg_host_finite(max_dist) && pg_host_finite(limit2), 9);
+  if (nq == 0) return 0;
+  UCSA_CHECK_ARG(queries, 6);
+  UCSA_CHECK_ARG(face, 10);
+  UCSA_CHECK_ARG(dist2, 11);
+  UCSA_CHECK_ARG(bary, 12);
+  UCSA_CHECK_ARG(n_pairs == 0 || records, 0);
+  UCSA_CHECK_ARG(n_pairs == 0 || offsets, 1);
+  UCSA_CHECK_ARG(n_pairs == 0 || ((uintptr_t)records & 15u) == 0, 0);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(ucsa_div_up(nq, PG_THREADS));
+  UCSA_CLEAR_ERR();
+  if (n_pairs == 0)
+    hipLaunchKernelGGL(k_tri_no_match, grid, dim3(PG_THREADS), 0, s, nq, face, dist2, bary);
+  else
+    hipLaunchKernelGGL(k_nearest_tri, grid, dim3(PG_THREADS), 0, s, (const float4*)records,
+                       offsets, n_pairs, g, queries, q_order, nq, limit2, face, dist2, bary);
+  return ucsa_launch_status();
+}

@@ -2482,3 +2482,144 @@ def nearest_point(grid, queries, max_dist: float, sort_queries: bool = True):
                                    cell, dm, _ptr(q), _ptr(q_order), nq, max_dist, _ptr(index),
                                    _ptr(dist2), _stream()), "ucsa_nearest_point")
     return index, dist2
+
+
+TRIANGLE_GRID_MAX_PAIRS = 0x7FFFFFFF
+
+
+def triangle_grid(verts, faces, cell=None):
+    """A uniform cell grid over the faces of a triangle mesh (``verts`` [V,3]
+    float32, ``faces`` [F,3] int32, on the GPU) for ``nearest_triangle`` -> dict:
+    ``origin`` (3 floats) and ``dims`` (3 ints) from the finite vertices'
+    bounding box, ``cell``, ``offsets`` int32 [cells+1], ``records`` float32
+    [P,12] (per (cell, face) pair, by cell and faces ascending inside a cell:
+    A.xyz and the bits of the face index, B.xyz and 0, C.xyz and 0),
+    ``n_pairs`` = P, ``n_faces``.  A face is registered in every cell of the box
+    between its corners' cells; a face with a corner index outside [0, V) or a
+    non-finite corner is registered nowhere.  The default cell is the (lower)
+    median over the valid faces of the longest side of the face's box, at least
+    1/1024 of the largest extent; it is raised by a quarter while the grid has
+    more than min(2^24, max(4096, 64 F)) cells or more than max(65536, 32 F)
+    pairs, and an explicit ``cell`` is raised the same way.  The cell changes
+    time only, never a result.  Counts and pairs are kernels
+    (ucsa_triangle_cell_counts, ucsa_triangle_cell_pairs); scan, sort and
+    packing are torch on the device."""
+    v = _points3(verts, "verts")
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.dtype == torch.int32 and faces.device == v.device):
+        raise _lib.UcsaError("faces must be an int32 [F,3] tensor on the GPU of verts: the HIP "
+                             "path has no CPU fallback")
+    f = faces.contiguous()
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    if nf > 0x7FFFFFFF:
+        raise _lib.UcsaError("faces must have at most 2^31-1 rows")
+    if cell is not None and not (float(cell) > 0 and math.isfinite(float(cell))):
+        raise _lib.UcsaError(f"cell must be positive and finite, got {cell!r}")
+    dev = v.device
+    fin = torch.isfinite(v).all(1)
+    if nv and bool(fin.any()):
+        good = v[fin]
+        lo, hi = good.min(0).values.tolist(), good.max(0).values.tolist()
+    else:
+        lo = hi = [0.0, 0.0, 0.0]
+    ext = [float(b) - float(a) for a, b in zip(lo, hi)]
+    big = max(ext)
+    if cell is None:
+        ok = ((f >= 0) & (f < nv)).all(1) if nv else torch.zeros(nf, dtype=torch.bool, device=dev)
+        if nv and nf:
+            ok &= fin[f.clamp(0, nv - 1).long()].all(1)
+        if nf and bool(ok.any()):
+            corners = v[f[ok].long()]                                   # [F',3,3]
+            side = (corners.max(1).values - corners.min(1).values).max(1).values
+            cell = float(torch.sort(side).values[(side.numel() - 1) // 2])
+        else:
+            cell = big
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
+    cell = f32(max(float(cell), big / 1024.0, 1e-30))
+    cell_cap = min(POINT_GRID_MAX_CELLS, max(4096, 64 * nf))
+    pair_cap = max(65536, 32 * nf)
+    org = fvec(lo)
+    counts = torch.empty(nf, dtype=torch.int32, device=dev)
+    while True:
+        dims = tuple(int(math.floor(e / cell)) + 1 for e in ext)
+        if dims[0] * dims[1] * dims[2] <= cell_cap:
+            dm = (C.c_uint32 * 3)(*dims)
+            check(lib().ucsa_triangle_cell_counts(_ptr(v), nv, _ptr(f), nf, org, cell, dm,
+                                                  _ptr(counts), _stream()),
+                  "ucsa_triangle_cell_counts")
+            n_pairs = int(counts.sum(dtype=torch.int64)) if nf else 0
+            if n_pairs <= pair_cap:
+                break
+        cell = f32(cell * 1.25)
+    if n_pairs > TRIANGLE_GRID_MAX_PAIRS:
+        raise _lib.UcsaError(f"{n_pairs} (cell, face) pairs: at most 2^31-1")
+    ncells = dims[0] * dims[1] * dims[2]
+    first = (torch.cumsum(counts, 0, dtype=torch.int64) - counts).to(torch.int32)
+    keys = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+    pair_face = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+    check(lib().ucsa_triangle_cell_pairs(_ptr(v), nv, _ptr(f), nf, org, cell, dm, _ptr(first),
+                                         n_pairs, _ptr(keys), _ptr(pair_face), _stream()),
+          "ucsa_triangle_cell_pairs")
+    order = torch.sort(keys, stable=True).indices
+    offsets = torch.searchsorted(keys[order].contiguous(),
+                                 torch.arange(ncells + 1, dtype=torch.int32, device=dev)
+                                 ).to(torch.int32)
+    sf = pair_face[order]
+    rec = torch.zeros((n_pairs, 12), dtype=torch.int32, device=dev)
+    if n_pairs:
+        tri = f[sf.long()].long()
+        for c in range(3):
+            rec[:, 4 * c:4 * c + 3] = v[tri[:, c]].view(torch.int32)
+        rec[:, 3] = sf
+    return {"origin": tuple(float(x) for x in lo), "cell": cell, "dims": dims,
+            "offsets": offsets, "records": rec.view(torch.float32), "n_pairs": n_pairs,
+            "n_faces": nf}
+
+
+def nearest_triangle(grid, queries, max_dist: float, sort_queries: bool = True):
+    """For each of ``queries`` [Q,3] (float32 on the GPU) the nearest point on the
+    faces of ``grid`` (``triangle_grid``'s dict) within ``max_dist`` -> (``face``
+    int32 [Q], ``dist2`` float32 [Q], ``bary`` float32 [Q,3]) on the device: the
+    face, the squared distance to its closest point and that point's
+    barycentric weights of the face's three corners; -1, +inf and a zero row
+    where no face lies within ``max_dist`` (inclusive).  Among equally near
+    faces the smallest index wins; an invalid face or a non-finite query matches
+    nothing.  ``max_dist`` is required and finite, as in ``nearest_point``, and
+    costs the same: a query with nothing near walks every cell within it.
+    ``sort_queries`` hands the queries to the kernel in cell order; it changes
+    time only.  Contract of ucsa_nearest_triangle (include/ucsa_hip.h)."""
+    q = _points3(queries, "queries")
+    try:
+        rec, offsets = grid["records"], grid["offsets"]
+        origin, cell, dims = grid["origin"], float(grid["cell"]), grid["dims"]
+        n = int(grid["n_pairs"])
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("grid must be the dict of ops.triangle_grid")
+    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if not (torch.is_tensor(rec) and rec.is_cuda and rec.dtype == torch.float32
+            and rec.is_contiguous() and tuple(rec.shape) == (n, 12) and torch.is_tensor(offsets)
+            and offsets.dtype == torch.int32 and offsets.is_contiguous()
+            and offsets.device == rec.device and offsets.numel() == ncells + 1):
+        raise _lib.UcsaError("grid: records must be float32 [n_pairs,12] and offsets int32 "
+                             "[cells+1], contiguous, on one GPU")
+    if rec.device != q.device:
+        raise _lib.UcsaError(f"the grid is on {rec.device}, the queries on {q.device}")
+    max_dist = float(max_dist)
+    if not (max_dist > 0 and math.isfinite(max_dist)):
+        raise _lib.UcsaError(f"max_dist must be positive and finite, got {max_dist!r}")
+    nq = int(q.shape[0])
+    org, dm = fvec(origin), (C.c_uint32 * 3)(*[int(d) for d in dims])
+    q_order = None
+    if sort_queries and nq and n:
+        keys = torch.empty(nq, dtype=torch.int32, device=q.device)
+        check(lib().ucsa_point_cell_keys(_ptr(q), nq, org, cell, dm, 0, _ptr(keys), _stream()),
+              "ucsa_point_cell_keys")
+        q_order = torch.sort(keys, stable=True).indices.to(torch.int32)
+    face = torch.empty(nq, dtype=torch.int32, device=q.device)
+    dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+    bary = torch.empty((nq, 3), dtype=torch.float32, device=q.device)
+    check(lib().ucsa_nearest_triangle(_ptr(rec) if n else None, _ptr(offsets) if n else None, n,
+                                      org, cell, dm, _ptr(q), _ptr(q_order), nq, max_dist,
+                                      _ptr(face), _ptr(dist2), _ptr(bary), _stream()),
+          "ucsa_nearest_triangle")
+    return face, dist2, bary

@@ -9,7 +9,13 @@ Meshes come as ``utils.mesh_render.load_mesh`` returns them, both in one frame
 (numpy or tensors; labels are NYU40 ids: class + 1, 0 = unknown).  Finding the
 rigid motion between two frames is not done here.  ``max_dist`` is required: a
 vertex with nothing within it is unmatched, and a query with nothing near costs
-the walk over every cell within ``max_dist``."""
+the walk over every cell within ``max_dist``.
+
+Vertex to vertex is right only when both meshes are tessellated about equally
+finely.  Where the target's faces are given (``src_faces``, ``pred_faces``,
+``gt_faces``) the search is for the nearest point on its surface instead
+(``ops.triangle_grid`` + ``ops.nearest_triangle``): a vertex in the middle of a
+large ground-truth triangle is then at distance 0, not half an edge away."""
 from __future__ import annotations
 
 import numpy as np
@@ -31,14 +37,38 @@ def _labels(l, n, device):
     return t.to(device=device, dtype=torch.int32)
 
 
-def transfer_labels(src_verts, src_labels, dst_verts, max_dist, return_match=False):
+def _faces(f, device):
+    t = torch.as_tensor(np.asarray(f) if not torch.is_tensor(f) else f)
+    return t.to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def transfer_labels(src_verts, src_labels, dst_verts, max_dist, return_match=False,
+                    src_faces=None):
     """The label of the nearest ``src`` vertex within ``max_dist`` at every ``dst``
     vertex -> int32 [D] on the device; 0 where there is none.  Among equally near
     source vertices the smallest index decides.  ``return_match``: also the
-    ``index`` (-1 = none) and ``dist2`` of ``ops.nearest_point``."""
+    ``index`` (-1 = none) and ``dist2`` of ``ops.nearest_point``.
+
+    With ``src_faces`` [F,3] the nearest point of the source's surface decides:
+    every ``dst`` vertex takes the label of the corner with the largest
+    barycentric weight of its nearest face (the first such corner on a tie), and
+    ``return_match`` gives (labels, ``index`` of that corner's vertex, ``dist2``,
+    ``face``, ``bary``) of ``ops.nearest_triangle``."""
     src = _verts(src_verts)
     dst = _verts(dst_verts, src.device)
     lab = _labels(src_labels, src.shape[0], src.device)
+    if src_faces is not None:
+        faces = _faces(src_faces, src.device)
+        face, dist2, bary = ops.nearest_triangle(ops.triangle_grid(src, faces), dst, max_dist)
+        hit = face >= 0
+        out = torch.zeros(dst.shape[0], dtype=torch.int32, device=src.device)
+        index = torch.full_like(face, -1)
+        if faces.shape[0] and lab.numel():
+            corner = bary.argmax(1, keepdim=True)                   # the first maximum
+            vert = faces[face.clamp_min(0).long()].gather(1, corner)[:, 0]
+            index = torch.where(hit, vert, index)
+            out = torch.where(hit, lab[vert.clamp(0, src.shape[0] - 1).long()], out)
+        return (out, index, dist2, face, bary) if return_match else out
     index, dist2 = ops.nearest_point(ops.point_grid(src), dst, max_dist)
     hit = index >= 0
     out = torch.zeros(dst.shape[0], dtype=torch.int32, device=src.device)
@@ -60,15 +90,17 @@ def _score(pred, index, gt_labels, C):
             "unmatched": float(((index < 0) & scored).sum()) / n if n else float("nan")}
 
 
-def score_labels_3d(pred_verts, pred_labels, gt_verts, gt_labels, max_dist, C=40):
+def score_labels_3d(pred_verts, pred_labels, gt_verts, gt_labels, max_dist, C=40,
+                    pred_faces=None):
     """The predicted labels at the ground-truth vertices (``transfer_labels``)
     scored through ``score_label_maps``: ground truth 0 or above ``C`` is ignored;
     a prediction of 0, or no predicted vertex within ``max_dist``, counts as
     wrong, exactly as the 2D score treats it.  -> {"mIoU", "total_acc",
     "mean_acc", "vertices" (scored), "unmatched" (the share of scored vertices
-    without a match)}."""
-    pred, index, _ = transfer_labels(pred_verts, pred_labels, gt_verts, max_dist,
-                                     return_match=True)
+    without a match)}.  ``pred_faces``: the labels come from the nearest point of
+    the predicted surface (``transfer_labels`` with ``src_faces``)."""
+    pred, index = transfer_labels(pred_verts, pred_labels, gt_verts, max_dist,
+                                  return_match=True, src_faces=pred_faces)[:2]
     return _score(pred, index, gt_labels, C)
 
 
@@ -95,32 +127,44 @@ def score_voxel_labels_3d(volume, voxel_labels, gt_verts, gt_labels, max_dist, C
     return score_labels_3d(centres, lab, gt_verts, gt_labels, max_dist, C)
 
 
-def mesh_distance(pred_verts, gt_verts, threshold, max_dist):
+def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt_faces=None):
     """Vertex-to-vertex distances both ways -> {"accuracy": mean pred -> gt,
     "completeness": mean gt -> pred, "chamfer": their mean, "precision": the share
     of pred vertices within ``threshold`` of gt, "recall": the share of gt
     vertices within ``threshold`` of pred, "fscore": their harmonic mean (0 when
     both are 0)}.  Distances are ``sqrt(dist2)`` in float64 on the device; a
     vertex with nothing within ``max_dist`` counts as ``max_dist`` (and is not
-    within the threshold).  An empty set gives nan for its direction."""
+    within the threshold).  An empty set gives nan for its direction.
+
+    A direction whose target has faces measures vertex to surface: ``gt_faces``
+    [F,3] the pred -> gt direction (accuracy, precision), ``pred_faces`` the
+    gt -> pred direction (completeness, recall).  With either given the dict
+    also holds "surface": (pred -> gt is to the surface, gt -> pred is)."""
     pred = _verts(pred_verts)
     gt = _verts(gt_verts, pred.device)
 
-    def one_way(a, b):
+    def one_way(a, b, b_faces):
         if a.shape[0] == 0:
             return float("nan"), float("nan")
-        index, dist2 = ops.nearest_point(ops.point_grid(b), a, max_dist)
+        if b_faces is not None:
+            grid = ops.triangle_grid(b, _faces(b_faces, b.device))
+            index, dist2, _ = ops.nearest_triangle(grid, a, max_dist)
+        else:
+            index, dist2 = ops.nearest_point(ops.point_grid(b), a, max_dist)
         d = torch.where(index >= 0, dist2.double().sqrt(),
                         torch.full_like(dist2, float(max_dist), dtype=torch.float64))
         return float(d.mean()), float(((index >= 0) & (d <= float(threshold))).double().mean())
 
-    acc, prec = one_way(pred, gt)
-    comp, rec = one_way(gt, pred)
+    acc, prec = one_way(pred, gt, gt_faces)
+    comp, rec = one_way(gt, pred, pred_faces)
     if not prec + rec >= 0:                         # an empty set: nan
         f = float("nan")
     elif prec + rec == 0:
         f = 0.0
     else:
         f = 2.0 * prec * rec / (prec + rec)
-    return {"accuracy": acc, "completeness": comp, "chamfer": 0.5 * (acc + comp),
-            "precision": prec, "recall": rec, "fscore": f}
+    out = {"accuracy": acc, "completeness": comp, "chamfer": 0.5 * (acc + comp),
+           "precision": prec, "recall": rec, "fscore": f}
+    if pred_faces is not None or gt_faces is not None:
+        out["surface"] = (gt_faces is not None, pred_faces is not None)
+    return out
