@@ -1892,6 +1892,77 @@ int32_t ucsa_nearest_triangle(const float* records, const int32_t* offsets, uint
                               float max_dist, int32_t* face, float* dist2, float* bary,
                               void* stream);
 
+/* ---- mesh simplification by vertex clustering (not in the reference) ----
+ * Rossignac-Borrel: the vertices of one cell of a uniform grid become one
+ * vertex, faces follow their corners, faces that collapse are dropped.  It
+ * carries what this project's meshes carry per vertex: label, colour, normal.
+ * One sort, no atomics, no data-dependent iteration: tests/simplify_numpy.py
+ * restates the three contracts in plain loops and the outputs match it byte
+ * for byte.  The inputs are never modified.  The grid is cells of edge `cell`
+ * from `origin`, dims[0] x dims[1] x dims[2] of them; origin[3] and dims[3] are
+ * host arrays.  The stable sort of the keys, the cluster boundaries, the face
+ * de-duplication and the compaction are torch on the device (ops.simplify_mesh).
+ *
+ * ucsa_vertex_cluster_keys: verts [n][3] float32, labels [n] uint8 or NULL ->
+ *   keys [n] int64.  One lane per vertex.  The cell of a coordinate is that of
+ *   ucsa_point_cell_keys: t = (p - origin) / cell in float32 (the division
+ *   correctly rounded), clamped as a float into [0, dim - 1], then floored.
+ *   keys[i] = (((ix << 18 | iy) << 18 | iz) << 8) | label, label = labels[i] or
+ *   0 without labels; a vertex with a non-finite coordinate gets INT64_MAX,
+ *   which sorts last and belongs to no cluster.  Ascending keys are x-major
+ *   cell order, then label.
+ *   Limits: n <= 2^31-1 (argument 1), origin finite (2), cell > 0 and finite
+ *   with a finite far corner (3), 1 <= dims <= 2^18 each (4; there is no
+ *   per-cell table, so the 2^24-cell limit of the point grid does not apply).
+ *   n == 0: returns 0, launches nothing.
+ * ucsa_cluster_reduce: one lane per cluster.  order [n] int32 is the stable
+ *   sort of the keys, first [K+1] int32 the clusters' offsets into it: the
+ *   members of cluster c are order[first[c] .. first[c+1]), ordered by label,
+ *   then by original index.  Per cluster, over its members in that order:
+ *   position  x0 = the first member's position; s = 0; s = s + (x - x0) per
+ *             member and axis, in float32; out = x0 + s / (float)count.
+ *             Offsets from a member keep the error independent of where the
+ *             scene sits.  A cluster of one returns its vertex's bits.
+ *   normal    (normals [n][3] float32 or NULL) s = 0; s = s + n per member and
+ *             axis; len = sqrtf((x*x + y*y) + z*z); out = len > 0 ? s / len : 0
+ *             (the expression of the marching-cubes normals).
+ *   colour    (rgb [n][3] uint8 or NULL) 64-bit integer sums per channel;
+ *             out = (2*sum + count) / (2*count) in integers: rounds half up.
+ *   label     (labels [n] uint8 or NULL) the most frequent label among the
+ *             members with label > 0: the members are sorted by label, so this
+ *             is the longest run, and the first longest run wins (the smallest
+ *             such label); 0 if no member has a label.
+ *   count     int32, the number of members.
+ *   A sequential float sum is the definition: a long cluster is one lane's
+ *   loop and is not split across lanes, so a call that puts every vertex into
+ *   one cell costs one lane walking all of them.  The loop is bounded by n.
+ *   Offsets are clamped into [0, n] and a decreasing pair is an empty cluster;
+ *   an entry of order outside [0, n) is no member; a cluster without members
+ *   writes zeros.  A lane writes row c of the outputs and nothing else.
+ *   Limits: n <= 2^31-1 (argument 4), K <= n (7); out_normals, out_rgb and
+ *   out_labels are required where their input is given (9..11) and untouched
+ *   where it is not.  K == 0: returns 0, launches nothing.
+ * ucsa_cluster_faces: faces [nf][3] int32, vertex_map [nv] int32 (the cluster of
+ *   every vertex, -1 for a dropped one) -> tri [nf][3] int32, keep [nf] uint8.
+ *   One lane per face.  A face with a corner index outside [0, nv), with a
+ *   corner mapped to a negative value, or with two corners on one cluster is
+ *   dropped: keep 0 and the row -1 -1 -1.  Otherwise keep is 1 and the row is
+ *   the mapped triple rotated so that its smallest index comes first; the
+ *   cyclic order, and so the orientation, is preserved.
+ *   Limits: nf, nv <= 2^31-1 (arguments 1, 3).  nf == 0: returns 0, launches
+ *   nothing; nv == 0: every face is dropped (vertex_map may be NULL).
+ * An argument error comes before any launch and nothing is written. */
+int32_t ucsa_vertex_cluster_keys(const float* verts, uint32_t n, const float* origin, float cell,
+                                 const uint32_t* dims, const uint8_t* labels, int64_t* keys,
+                                 void* stream);
+int32_t ucsa_cluster_reduce(const float* verts, const float* normals, const uint8_t* rgb,
+                            const uint8_t* labels, uint32_t n, const int32_t* order,
+                            const int32_t* first, uint32_t K, float* out_verts,
+                            float* out_normals, uint8_t* out_rgb, uint8_t* out_labels,
+                            int32_t* out_count, void* stream);
+int32_t ucsa_cluster_faces(const int32_t* faces, uint32_t nf, const int32_t* vertex_map,
+                           uint32_t nv, int32_t* tri, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ sibling of ``scripts/render_mesh_labels.py``, which goes the other way.
         [--pose_frame] --labels {seg_label,nerf_label,label_40,<dir>} [--exp_name E] \\
         [--depth_tol METRES] [--min_votes K] [--every N] --out FUSED.ply \\
         [--render] [--score] [--scores {seg_evidence,<dir>} [--min_margin M]] \\
-        [--smooth N] [--min_component N] [--gt_mesh G.ply [--gt_max_dist M]]
+        [--smooth N] [--min_component N] [--gt_mesh G.ply [--gt_max_dist M]] \\
+        [--simplify CELL [--simplify_split_labels]]
 
 ``--labels``: ``label_40`` is ``<scene>/label_40``; ``seg_label`` / ``nerf_label``
 are ``<scene>/<exp_name>/...`` (the predict pass's output); anything else is a
@@ -50,7 +51,16 @@ changes nothing.
 every labelled vertex of G, read in the frame ``--mesh`` is read in, takes the
 label of the nearest fused vertex within ``--gt_max_dist`` scene units (default
 0.2), and one ``3d: {...}`` line is printed.  Without the flag the output is
-unchanged."""
+unchanged.
+``--simplify CELL`` simplifies the mesh by vertex clustering on a grid of edge
+CELL, in the units of the mesh file (metres with ``--pose_frame``, else scene
+units), after ``--min_component`` and before the views are fused
+(``utils.mesh_fusion.simplify_mesh``): the votes land on the coarse vertices,
+each of which stands for a patch of about CELL across, and the written mesh is
+the coarse one with its averaged colours and normals.  With
+``--simplify_split_labels`` vertices that carry different labels in the mesh
+file are never merged.  One ``simplify:`` line of statistics is printed;
+without the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -62,10 +72,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from ucsa_neural_rendering_amd.utils.mesh_fusion import (  # noqa: E402
-    filter_mesh_components, fuse_views)
+    filter_mesh_components, fuse_views, simplify_mesh)
 from ucsa_neural_rendering_amd.utils.mesh_render import (  # noqa: E402
     load_mesh, read_frames, render_views, score_label_maps)
 from ucsa_neural_rendering_amd.utils.ply import read_ply, write_ply  # noqa: E402
+from ucsa_neural_rendering_amd.utils.semantic_mesh import pose_frame_to_ngp  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -92,6 +103,11 @@ def parse_args(argv=None):
                    help="score the fused labels in 3D at this labelled mesh's vertices (.ply)")
     p.add_argument("--gt_max_dist", type=float, default=0.2,
                    help="with --gt_mesh: search radius, scene units")
+    p.add_argument("--simplify", type=float, default=None,
+                   help="cluster the mesh's vertices on a grid of this edge before fusing, "
+                        "units of the mesh file (default: off)")
+    p.add_argument("--simplify_split_labels", action="store_true",
+                   help="with --simplify: never merge vertices whose labels in the file differ")
     p.add_argument("--exp_name", default=None)
     p.add_argument("--depth_tol", type=float, default=None, help="metres")
     p.add_argument("--min_votes", type=int, default=1,
@@ -151,6 +167,10 @@ def main(argv=None):
         raise SystemExit("--smooth must be >= 0")
     if a.min_component < 0:
         raise SystemExit("--min_component must be >= 0")
+    if a.simplify is not None and not a.simplify > 0:
+        raise SystemExit("--simplify must be > 0")
+    if a.simplify_split_labels and a.simplify is None:
+        raise SystemExit("--simplify_split_labels goes with --simplify")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -166,6 +186,23 @@ def main(argv=None):
         raw = {**raw, "faces": mesh["faces"],
                **{k: raw[k][vi] for k in ("verts", "normals", "rgb") if raw.get(k) is not None}}
         print("components: " + json.dumps(components))
+    simplified = None
+    if a.simplify is not None:
+        # in the file's frame, on the file's own attributes; the fused mesh is
+        # then what load_mesh makes of the coarse one
+        fine = {"verts": raw["verts"], "faces": raw["faces"], "normals": raw.get("normals"),
+                "rgb": raw.get("rgb"), "labels": mesh["labels"]}
+        coarse, simplified = simplify_mesh(fine, a.simplify,
+                                           split_labels=a.simplify_split_labels)
+        raw = {**raw, **{k: coarse[k] for k in ("verts", "faces", "normals", "rgb")
+                         if coarse.get(k) is not None}}
+        verts = pose_frame_to_ngp(coarse["verts"], uom) if a.pose_frame else coarse["verts"]
+        rgb = coarse.get("rgb")
+        mesh = {"verts": np.ascontiguousarray(verts, np.float32),
+                "faces": np.ascontiguousarray(coarse["faces"], np.int32),
+                "labels": coarse["labels"],
+                "rgb": None if rgb is None else rgb.astype(np.float32) / np.float32(255.0)}
+        print("simplify: " + json.dumps(simplified))
     src = None if a.labels is None else label_dir(a)
     ssrc = None if a.scores is None else score_dir(a)
 
@@ -202,6 +239,8 @@ def main(argv=None):
         rec["smooth"] = a.smooth
     if components is not None:
         rec["components"] = components
+    if simplified is not None:
+        rec["simplify"] = simplified
     if a.gt_mesh is not None:
         from ucsa_neural_rendering_amd.utils.mesh_eval import score_labels_3d
         gt = load_mesh(a.gt_mesh, pose_frame=a.pose_frame, one_m_to_scene_uom=uom)

@@ -7,7 +7,7 @@ first stage of the mapping-based pseudo-label baseline.
     python scripts/fuse_tsdf_mesh.py --scene_root <root>/<scene> --out M.ply \\
         [--voxel METRES] [--trunc METRES] [--aabb X0 Y0 Z0 X1 Y1 Z1] [--every N] \\
         [--min_weight K] [--no_color] [--pose_frame] \\
-        [--min_component N] [--component_connectivity {6,26}]
+        [--min_component N] [--component_connectivity {6,26}] [--simplify CELL]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
 ``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement; scene units as
@@ -22,7 +22,12 @@ vertex colours; no labels.  ``--min_component N`` returns the connected
 components of the truncation band with fewer than N voxels to the unobserved
 state before the mesh is extracted (``remove_small_components``: the floaters
 that a few bad depth pixels leave in free space) and prints their statistics;
-0, the default, changes nothing.  Prints one JSON line last."""
+0, the default, changes nothing.  ``--simplify CELL`` (metres, as ``--voxel``)
+simplifies the extracted mesh by vertex clustering on a grid of that edge
+(``utils.mesh_fusion.simplify_mesh``: normals and colours are carried) after
+``--min_component`` has judged the floaters at full resolution, and prints one
+``simplify:`` line of statistics; without the flag nothing changes.  Prints one
+JSON line last."""
 import argparse
 import json
 import os
@@ -57,6 +62,9 @@ def parse_args(argv=None):
     p.add_argument("--min_component", type=int, default=0,
                    help="drop band components with fewer voxels than this (default 0: off)")
     p.add_argument("--component_connectivity", type=int, choices=(6, 26), default=26)
+    p.add_argument("--simplify", type=float, default=None,
+                   help="cluster the mesh's vertices on a grid of this edge, metres "
+                        "(default: off)")
     return p.parse_args(argv)
 
 
@@ -67,6 +75,8 @@ def main(argv=None):
         raise SystemExit("--every, --min_weight and --batch must be >= 1")
     if a.min_component < 0:
         raise SystemExit("--min_component must be >= 0")
+    if a.simplify is not None and not a.simplify > 0:
+        raise SystemExit("--simplify must be > 0")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -90,6 +100,11 @@ def main(argv=None):
                             min_weight=a.min_weight, batch=a.batch,
                             min_component=a.min_component,
                             component_connectivity=a.component_connectivity)
+    simplified = None
+    if a.simplify is not None:
+        from ucsa_neural_rendering_amd.utils.mesh_fusion import simplify_mesh
+        mesh, simplified = simplify_mesh(mesh, a.simplify * uom)
+        print("simplify: " + json.dumps(simplified))
     verts = mesh["verts"]
     normals = mesh["normals"]
     if a.pose_frame:
@@ -107,6 +122,8 @@ def main(argv=None):
     if "components" in mesh:
         rec["components"] = mesh["components"]
         print("components: " + json.dumps(mesh["components"]))
+    if simplified is not None:
+        rec["simplify"] = simplified
     print(json.dumps(rec))
     return rec
 

@@ -359,6 +359,12 @@ SIGNATURES = {
                                              C.POINTER(_u32), _p, _u32, _p, _p, _p]),
     "ucsa_nearest_triangle": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p,
                                           _p, _u32, _f, _p, _p, _p, _p]),
+    # ---- mesh simplification by vertex clustering ----
+    "ucsa_vertex_cluster_keys": (C.c_int32, [_p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _p,
+                                             _p]),
+    "ucsa_cluster_reduce": (C.c_int32, [_p, _p, _p, _p, _u32, _p, _p, _u32, _p, _p, _p, _p, _p,
+                                        _p]),
+    "ucsa_cluster_faces": (C.c_int32, [_p, _u32, _p, _u32, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

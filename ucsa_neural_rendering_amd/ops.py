@@ -2623,3 +2623,151 @@ def nearest_triangle(grid, queries, max_dist: float, sort_queries: bool = True):
                                       _ptr(face), _ptr(dist2), _ptr(bary), _stream()),
           "ucsa_nearest_triangle")
     return face, dist2, bary
+
+
+# ---------------------------------------------------------------------------
+# mesh simplification by vertex clustering
+# ---------------------------------------------------------------------------
+SIMPLIFY_MAX_DIM = 1 << 18
+_NO_CLUSTER = 0x7FFFFFFFFFFFFFFF
+
+
+def _vertex_rows(t, name, dtype, shape, dev):
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == dtype
+            and tuple(t.shape) == shape):
+        raise _lib.UcsaError(f"{name} must be a {dtype} tensor of shape {list(shape)} on the "
+                             "vertices' GPU")
+    return t.contiguous()
+
+
+def simplify_mesh(verts, faces, cell, normals=None, rgb=None, labels=None,
+                  split_labels: bool = False, origin=None):
+    """Simplify a triangle mesh by vertex clustering (Rossignac-Borrel): the
+    vertices of one cell of a uniform grid of edge ``cell`` become one vertex.
+    ``verts`` float32 [V,3] and ``faces`` int32 [F,3] on the GPU; per vertex and
+    optional ``normals`` float32 [V,3], ``rgb`` uint8 [V,3], ``labels`` an
+    integer tensor [V] with values 0..255 (0 = none).  A cluster is a cell; with
+    ``split_labels`` it is a (cell, label) pair, so vertices of different
+    classes in one cell are never merged and class borders keep their place.
+    ``origin`` (3 floats) defaults to the minimum corner of the finite vertices;
+    dims = floor(extent / cell) + 1 per axis, at most 2^18.  -> dict:
+    ``verts`` float32 [K,3] (the members' mean, summed as offsets from the first
+    member), ``count`` int32 [K] and, for the inputs given, ``normals`` (the
+    normalised sum), ``rgb`` uint8 (the mean, half up), ``labels`` uint8 (the
+    most frequent label > 0, ties to the smallest; 0 if none): one row per
+    cluster, in ascending key order (x-major cell order, then label when
+    split); ``faces`` int32 [F',3]: every face through the clusters of its
+    corners, rotated to start at its smallest index, without the degenerate
+    ones (two corners on one cluster, a corner outside [0, V) or on a
+    non-finite vertex) and without repeated triples (the lowest input face is
+    kept; a reversed copy is another triple and stays), in their former
+    relative order; ``face_index`` int32 [F'] (the input face of each);
+    ``vertex_map`` int32 [V] (the cluster of every input vertex, -1 for a
+    non-finite one); ``origin``, ``cell``, ``dims``; ``degenerate`` and
+    ``duplicate`` (how many faces went each way).  V = 0 and F = 0 are valid;
+    the inputs are not modified.  One lane walks a cluster's members in order:
+    a call that puts every vertex into one cell costs one lane walking all of
+    them.  The keys, the per-cluster reduction and the face mapping are kernels
+    (ucsa_vertex_cluster_keys, ucsa_cluster_reduce, ucsa_cluster_faces in
+    include/ucsa_hip.h); the sort, the cluster boundaries, the de-duplication
+    and the compaction are torch on the device."""
+    pts = _points3(verts, "verts")
+    dev = pts.device
+    n = int(pts.shape[0])
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.device == dev
+            and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3):
+        raise _lib.UcsaError("faces must be an int32 [F,3] tensor on the vertices' GPU")
+    if faces.shape[0] > 0x7FFFFFFF:
+        raise _lib.UcsaError("faces must have at most 2^31-1 rows")
+    fc = faces.contiguous()
+    nf = int(fc.shape[0])
+    nrm = _vertex_rows(normals, "normals", torch.float32, (n, 3), dev)
+    col = _vertex_rows(rgb, "rgb", torch.uint8, (n, 3), dev)
+    lab = None
+    if labels is not None:
+        if not (torch.is_tensor(labels) and labels.is_cuda and labels.device == dev
+                and not labels.dtype.is_floating_point and not labels.dtype.is_complex
+                and labels.dtype != torch.bool and tuple(labels.shape) == (n,)):
+            raise _lib.UcsaError(f"labels must be an integer tensor of shape [{n}] on the "
+                                 "vertices' GPU")
+        if n and (int(labels.min()) < 0 or int(labels.max()) > 255):
+            raise _lib.UcsaError("labels must be in 0..255")
+        lab = labels.to(torch.uint8).contiguous()
+    f32 = lambda v: float(torch.tensor(float(v), dtype=torch.float32))
+    try:
+        cell = f32(cell)
+    except (TypeError, ValueError):
+        raise _lib.UcsaError(f"cell must be a number, got {cell!r}")
+    if not (cell > 0 and math.isfinite(cell)):
+        raise _lib.UcsaError(f"cell must be positive and finite in float32, got {cell!r}")
+    ok = torch.isfinite(pts).all(1)
+    if n and bool(ok.any()):
+        good = pts[ok]
+        lo, hi = good.min(0).values.tolist(), good.max(0).values.tolist()
+    else:
+        lo = hi = [0.0, 0.0, 0.0]
+    if origin is not None:
+        try:
+            lo = [f32(v) for v in origin]
+        except (TypeError, ValueError):
+            raise _lib.UcsaError("origin must be three numbers")
+        if len(lo) != 3 or not all(math.isfinite(v) for v in lo):
+            raise _lib.UcsaError(f"origin must be three finite numbers, got {origin!r}")
+    dims = tuple(int(math.floor(max(float(b) - float(a), 0.0) / cell)) + 1
+                 for a, b in zip(lo, hi))
+    if max(dims) > SIMPLIFY_MAX_DIM:
+        raise _lib.UcsaError(f"cell {cell!r} needs {max(dims)} cells along an axis, more than "
+                             f"2^18: raise cell")
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    check(lib().ucsa_vertex_cluster_keys(_ptr(pts), n, fvec(lo), cell, (C.c_uint32 * 3)(*dims),
+                                         _ptr(lab), _ptr(keys), _stream()),
+          "ucsa_vertex_cluster_keys")
+    skeys, order64 = torch.sort(keys, stable=True)
+    order = order64.to(torch.int32)
+    n_fin = int((skeys != _NO_CLUSTER).sum()) if n else 0
+    ident = skeys[:n_fin] if split_labels else skeys[:n_fin] >> 8
+    _, inverse, counts = torch.unique_consecutive(ident, return_inverse=True, return_counts=True)
+    K = int(counts.numel())
+    first = torch.zeros(K + 1, dtype=torch.int32, device=dev)
+    first[1:] = torch.cumsum(counts, 0)
+    vertex_map = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    vertex_map[order64[:n_fin]] = inverse.to(torch.int32)
+    out = {"verts": torch.empty((K, 3), dtype=torch.float32, device=dev),
+           "count": torch.empty(K, dtype=torch.int32, device=dev)}
+    if nrm is not None:
+        out["normals"] = torch.empty((K, 3), dtype=torch.float32, device=dev)
+    if col is not None:
+        out["rgb"] = torch.empty((K, 3), dtype=torch.uint8, device=dev)
+    if lab is not None:
+        out["labels"] = torch.empty(K, dtype=torch.uint8, device=dev)
+    check(lib().ucsa_cluster_reduce(_ptr(pts), _ptr(nrm), _ptr(col), _ptr(lab), n, _ptr(order),
+                                    _ptr(first), K, _ptr(out["verts"]), _ptr(out.get("normals")),
+                                    _ptr(out.get("rgb")), _ptr(out.get("labels")),
+                                    _ptr(out["count"]), _stream()), "ucsa_cluster_reduce")
+    tri = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    keep = torch.empty(nf, dtype=torch.uint8, device=dev)
+    check(lib().ucsa_cluster_faces(_ptr(fc), nf, _ptr(vertex_map) if n else None, n, _ptr(tri),
+                                   _ptr(keep), _stream()), "ucsa_cluster_faces")
+    kept = torch.nonzero(keep).view(-1)
+    n_kept = int(kept.numel())
+    if n_kept:
+        # equal triples, two columns at a time so that a key stays below 2^62
+        t = tri[kept].long()
+        ab = torch.unique(t[:, 0] * K + t[:, 1], return_inverse=True)[1]
+        abc = torch.unique(ab * K + t[:, 2], return_inverse=True)[1]
+        # a stable sort puts the lowest input face first in each group
+        sg, pos = torch.sort(abc, stable=True)
+        head = torch.ones_like(sg, dtype=torch.bool)
+        head[1:] = sg[1:] != sg[:-1]
+        face_index = kept[torch.sort(pos[head]).values]
+    else:
+        face_index = kept
+    out["faces"] = tri[face_index].reshape(-1, 3)
+    out["face_index"] = face_index.to(torch.int32)
+    out["vertex_map"] = vertex_map
+    out["origin"], out["cell"], out["dims"] = tuple(float(v) for v in lo), cell, dims
+    out["degenerate"] = nf - n_kept
+    out["duplicate"] = n_kept - int(face_index.numel())
+    return out

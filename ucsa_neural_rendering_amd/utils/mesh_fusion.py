@@ -13,7 +13,9 @@ majority.  With ``score_maps`` (rows of evidence codes per pixel,
 (``ops.fuse_label_evidence``, same table) and the majority becomes the MAP
 class.  With ``smooth`` the table is pooled over each vertex's edge neighbours
 before it is resolved (``ops.smooth_label_table``), which also fills unobserved
-vertices from their neighbours.  Out of scope: float probabilities on the
+vertices from their neighbours.  ``simplify_mesh`` makes a mesh coarser by
+vertex clustering before (or after) fusing, and ``pool_label_table`` carries a
+table fused on the fine mesh to the coarse one.  Out of scope: float probabilities on the
 device, priors, registering a
 mesh to the poses' frame (``load_mesh(..., pose_frame=True)`` covers the one
 rigid motion the project records), anything in the training loop."""
@@ -203,3 +205,81 @@ def filter_mesh_components(mesh, min_vertices=0, keep_largest=None, device="cuda
              "removed_vertices": int(root_sizes[gone].sum()),
              "largest": int(root_sizes.max()) if roots.numel() else 0}
     return out, stats
+
+
+def simplify_mesh(mesh, cell, split_labels=False, device="cuda"):
+    """Simplify a mesh by vertex clustering (``ops.simplify_mesh``): the vertices
+    of one cell of a grid of edge ``cell`` become one vertex, so the mesh comes
+    out about as fine as ``cell``.  ``mesh`` is a dict as ``load_mesh`` gives it
+    (numpy: verts [V,3], faces [F,3] int32, optional normals / rgb / labels per
+    vertex; rgb uint8, or float in [0,1], which is rounded to 0..255 for the
+    averaging and returned as float again; labels 0..255).  With
+    ``split_labels`` vertices of different labels are never merged.  -> (new
+    dict, statistics): verts, faces, normals, rgb and labels replaced (dtypes
+    kept), ``face_classes`` [F], if present, indexed by ``face_index``, every
+    other entry passed on, plus ``vertex_map`` (int32 [V]: the output vertex of
+    every input vertex, -1 for a non-finite one) and ``face_index`` (int32: the
+    input face of every output face); {"vertices": [in, out], "faces": [in,
+    out], "degenerate": k, "duplicate": d, "largest_cluster": m}."""
+    dev = torch.device(device)
+    put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+    verts = put(np.asarray(mesh["verts"]).reshape(-1, 3), np.float32)
+    faces = put(np.asarray(mesh["faces"]).reshape(-1, 3), np.int32)
+    normals = rgb = labels = None
+    if mesh.get("normals") is not None:
+        normals = put(np.asarray(mesh["normals"]).reshape(-1, 3), np.float32)
+    if mesh.get("rgb") is not None:
+        c = np.asarray(mesh["rgb"]).reshape(-1, 3)
+        if c.dtype != np.uint8:      # write_ply's rounding
+            c = np.round(np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+        rgb = put(c, np.uint8)
+    if mesh.get("labels") is not None:
+        labels = put(np.asarray(mesh["labels"]).reshape(-1), np.int64)
+    res = ops.simplify_mesh(verts, faces, cell, normals=normals, rgb=rgb, labels=labels,
+                            split_labels=split_labels)
+    out = dict(mesh)
+    out["verts"] = res["verts"].cpu().numpy()
+    out["faces"] = res["faces"].cpu().numpy().reshape(-1, 3)
+    if normals is not None:
+        out["normals"] = res["normals"].cpu().numpy().astype(np.asarray(mesh["normals"]).dtype)
+    if rgb is not None:
+        c = res["rgb"].cpu().numpy()
+        src = np.asarray(mesh["rgb"])
+        out["rgb"] = c if src.dtype == np.uint8 else \
+            (c.astype(np.float32) / np.float32(255.0)).astype(src.dtype)
+    if labels is not None:
+        out["labels"] = res["labels"].cpu().numpy().astype(np.asarray(mesh["labels"]).dtype)
+    out["vertex_map"] = res["vertex_map"].cpu().numpy()
+    out["face_index"] = res["face_index"].cpu().numpy()
+    if mesh.get("face_classes") is not None:
+        out["face_classes"] = np.asarray(mesh["face_classes"])[out["face_index"]]
+    count = res["count"]
+    stats = {"vertices": [int(verts.shape[0]), int(count.numel())],
+             "faces": [int(faces.shape[0]), int(out["faces"].shape[0])],
+             "degenerate": int(res["degenerate"]), "duplicate": int(res["duplicate"]),
+             "largest_cluster": int(count.max()) if count.numel() else 0}
+    return out, stats
+
+
+def pool_label_table(votes, vertex_map, n_out):
+    """Carry a vote or evidence table from a fine mesh to its simplified one:
+    ``votes`` [V, C+1] int64 on the GPU (the bits of the uint64 table of
+    ``ops.fuse_label_votes`` / ``ops.fuse_label_evidence``), ``vertex_map`` [V]
+    (``simplify_mesh``'s: the coarse vertex of every fine one, -1 = none) -> a
+    NEW [n_out, C+1] int64 table: row k is the sum of the rows mapped to k,
+    exact modulo 2^64 (integer adds, so the order does not matter); -1 rows are
+    skipped.  ``ops.resolve_label_votes`` reads the result as it is.  The table
+    is not modified.  ``index_add_`` on the device: plumbing, not a kernel."""
+    if not (torch.is_tensor(votes) and votes.dtype == torch.int64 and votes.dim() == 2):
+        raise ValueError("votes must be an int64 [V, C+1] tensor")
+    vm = torch.as_tensor(np.asarray(vertex_map) if not torch.is_tensor(vertex_map)
+                         else vertex_map).to(votes.device).long().view(-1)
+    if vm.numel() != votes.shape[0]:
+        raise ValueError(f"vertex_map has {vm.numel()} entries, the table {votes.shape[0]} rows")
+    n_out = int(n_out)
+    if vm.numel() and (int(vm.min()) < -1 or int(vm.max()) >= n_out):
+        raise ValueError(f"vertex_map must lie in -1..{n_out - 1}")
+    out = torch.zeros((n_out, votes.shape[1]), dtype=torch.int64, device=votes.device)
+    keep = vm >= 0
+    out.index_add_(0, vm[keep], votes[keep])
+    return out
