@@ -1963,6 +1963,77 @@ int32_t ucsa_cluster_reduce(const float* verts, const float* normals, const uint
 int32_t ucsa_cluster_faces(const int32_t* faces, uint32_t nf, const int32_t* vertex_map,
                            uint32_t nv, int32_t* tri, uint8_t* keep, void* stream);
 
+/* ---- area-uniform sample points on a triangle mesh (not in the reference) ----
+ * A deterministic, low-discrepancy point set on the surface of a mesh, with a
+ * density of `density` points per unit area: the query points of 3D scores that
+ * weigh a surface by its area and not by its tessellation.  A sample is a
+ * function of (seed, face index, index inside the face) and the face's corners
+ * alone: raising the density keeps every earlier sample of a face and appends
+ * new ones, and editing one face changes no sample of another.  No atomics, no
+ * LDS; tests/sample_numpy.py restates both contracts in plain loops and the
+ * outputs match it byte for byte.  The inputs are never modified.  All float
+ * arithmetic is float32 in the order written, without fused multiply-add, with
+ * sqrt and divide correctly rounded; all integer arithmetic is uint32, wrapping.
+ *
+ * Hash   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+ *        x ^= x >> 16.  Per face f: h0 = mix(seed ^ mix(f + 0x9e3779b9)),
+ *        hc = mix(h0 ^ 0x3c6ef372), h1 = mix(h0 ^ 0x68bc21eb),
+ *        h2 = mix(h0 ^ 0x02e5be93).
+ *
+ * ucsa_face_sample_counts: verts [nv][3] float32, faces [nf][3] int32 ->
+ *   area [nf] float32, count [nf] int32.  One lane per face with corners A, B, C:
+ *   e1 = B - A, e2 = C - A, c = e1 x e2 with each component a*b - c*d,
+ *   area = 0.5f * sqrtf((cx*cx + cy*cy) + cz*cz), expect = area * density,
+ *   count = (int)floorf(expect + (float)(hc >> 8) * 2^-24), at most 2^24: the
+ *   offset is uniform in [0, 1), so the rounding has no bias and a face smaller
+ *   than 1 / density gets a sample at the right rate.  A face with a corner
+ *   index outside [0, nv), a non-finite corner or a non-finite area gets area 0
+ *   and count 0.
+ *   Limits: nv, nf <= 2^31-1 (arguments 1, 3), density > 0 and finite (4).
+ *   nf == 0: returns 0, launches nothing.
+ * ucsa_mesh_surface_samples: first [nf+1] int32 is the exclusive prefix sum of
+ *   the counts and n_samples = first[nf] (torch on the device in
+ *   ops.sample_mesh_surface).  One lane per sample s:
+ *   face    the f with first[f] <= s < first[f+1]: the smallest k in [0, nf)
+ *           with first[k+1] > s, by a binary search of at most 32 steps over
+ *           lo = 0, hi = nf (mid = (lo + hi) >> 1; first[mid+1] > s ? hi = mid :
+ *           lo = mid + 1), then f = min(lo, nf - 1).  Every read of `first` is
+ *           at an index in [1, nf] whatever its entries hold.  j = s - first[f]
+ *           (as a uint32).
+ *   bary    a = (j * 0xC13FA9A9 + h1) >> 8, b = (j * 0x91E10DA5 + h2) >> 8: the
+ *           R2 sequence (Roberts; the plastic number's powers) in 32-bit fixed
+ *           point with a per-face offset, 24 bits each.  Folded in integers: if
+ *           a + b > 2^24 then a = 2^24 - a, b = 2^24 - b; c = 2^24 - a - b;
+ *           bary = (c, a, b) * 2^-24, exact, non-negative, summing to 1.
+ *   point   per axis A + (bary[1] * e1 + bary[2] * e2): offsets from A, so the
+ *           error does not grow with the scene's distance from the origin.
+ *   labels  (labels [nv] uint8 or NULL) the label of the corner with the largest
+ *           weight, the first such corner on a tie.
+ *   rgb     (rgb [nv][3] uint8 or NULL) per channel
+ *           floorf(((w0*r0 + w1*r1) + w2*r2) + 0.5f).
+ *   normals (normals [nv][3] float32 or NULL) n = (w0*n0 + w1*n1) + w2*n2 per
+ *           axis, len = sqrtf((x*x + y*y) + z*z), out = len > 0 ? n / len : 0.
+ *   -> points [n_samples][3] float32, face [n_samples] int32, bary
+ *   [n_samples][3] float32, and out_normals, out_rgb, out_labels (rows per
+ *   sample) where their input is given.  Only a malformed `first` can lead to a
+ *   face with a corner index outside [0, nv): its samples get the face and the
+ *   weights as above, a zero point and zero attributes.  A lane writes row s
+ *   of the outputs and nothing else.
+ *   Limits: nv, nf <= 2^31-1 (arguments 1, 3), n_samples <= 2^31-1 (5), nf > 0
+ *   where n_samples > 0 (3); out_normals, out_rgb and out_labels are required
+ *   where their input is given (13..15) and untouched where it is not.
+ *   n_samples == 0: returns 0, launches nothing.
+ * An argument error comes before any launch and nothing is written. */
+int32_t ucsa_face_sample_counts(const float* verts, uint32_t nv, const int32_t* faces,
+                                uint32_t nf, float density, uint32_t seed, float* area,
+                                int32_t* count, void* stream);
+int32_t ucsa_mesh_surface_samples(const float* verts, uint32_t nv, const int32_t* faces,
+                                  uint32_t nf, const int32_t* first, uint32_t n_samples,
+                                  uint32_t seed, const float* normals, const uint8_t* rgb,
+                                  const uint8_t* labels, float* points, int32_t* face,
+                                  float* bary, float* out_normals, uint8_t* out_rgb,
+                                  uint8_t* out_labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

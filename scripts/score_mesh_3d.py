@@ -6,7 +6,8 @@ and the geometry as accuracy, completeness, chamfer and F-score.
 
     python scripts/score_mesh_3d.py --pred P.ply --gt G.ply [--max_dist M] \\
         [--threshold T] [--pred_pose_frame] [--gt_pose_frame] [--one_m_to_scene_uom U] \\
-        [--gt_transform T.txt] [--num_classes C] [--surface]
+        [--gt_transform T.txt] [--num_classes C] [--surface] \\
+        [--sample_density D [--sample_seed S]]
 
 Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
 read a mesh in the frame of the JSON poses in metres (what the export and fusion
@@ -21,6 +22,18 @@ with nothing within it is unmatched (its label counts as wrong, its distance as
 surface and every distance is from a vertex to the other mesh's surface, which
 is what a coarsely tessellated ground truth needs; both lines then carry a
 ``"surface"`` entry (``true`` in ``3d:``, ``[true, true]`` in ``geometry:``).
+``--sample_density D`` (points per unit area; needs faces in both meshes) takes
+the query points from the surfaces and not from the vertices
+(``ops.sample_mesh_surface``, deterministic for ``--sample_seed``), the protocol
+of reconstruction benchmarks: the labels are scored at samples of the
+ground-truth surface, each with the label of its face's nearest corner, and the
+geometry between the two sampled point sets, so that every surface weighs by its
+area and a hole in the predicted mesh costs recall.  With ``--surface`` the
+samples are measured to the other mesh's surface instead of to its samples
+(point to point, two sets of spacing about ``1 / sqrt(D)`` are that far apart
+even on one surface: keep ``--threshold`` above it, or use ``--surface``).
+Both lines then carry a ``"sampled"`` entry: the number of ground-truth samples
+in ``3d:``, ``[n_pred, n_gt]`` in ``geometry:``.
 Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
 import argparse
 import json
@@ -33,7 +46,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from ucsa_neural_rendering_amd.utils.mesh_eval import (  # noqa: E402
-    mesh_distance, score_labels_3d)
+    mesh_distance, sample_surface, score_labels_3d)
 from ucsa_neural_rendering_amd.utils.mesh_render import load_mesh  # noqa: E402
 
 
@@ -50,6 +63,9 @@ def parse_args(argv=None):
     p.add_argument("--num_classes", type=int, default=40)
     p.add_argument("--surface", action="store_true",
                    help="measure to the nearest point on the other mesh's faces, not its vertices")
+    p.add_argument("--sample_density", type=float, default=None,
+                   help="query points sampled from the surfaces, so many per unit area")
+    p.add_argument("--sample_seed", type=int, default=0)
     return p.parse_args(argv)
 
 
@@ -67,14 +83,31 @@ def main(argv=None):
     pf, gf = (pred["faces"], gt["faces"]) if a.surface else (None, None)
     if a.surface and (pf is None or gf is None or not len(pf) or not len(gf)):
         raise SystemExit("--surface needs faces in both meshes")
+    dens = a.sample_density
+    if dens is not None:
+        if not dens > 0:
+            raise SystemExit("--sample_density must be > 0")
+        if any(m["faces"] is None or not len(m["faces"]) for m in (pred, gt)):
+            raise SystemExit("--sample_density needs faces in both meshes")
     if pred["labels"] is not None and gt["labels"] is not None:
+        more = {} if dens is None else {"gt_faces": gt["faces"], "sample_density": dens,
+                                        "seed": a.sample_seed}
         rec["3d"] = score_labels_3d(pred["verts"], pred["labels"], gv, gt["labels"], a.max_dist,
-                                    a.num_classes, pred_faces=pf)
+                                    a.num_classes, pred_faces=pf, **more)
         if a.surface:
             rec["3d"]["surface"] = True
         print("3d: " + json.dumps(rec["3d"]))
-    rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist, pred_faces=pf,
-                                    gt_faces=gf)
+    if dens is None:
+        rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist, pred_faces=pf,
+                                        gt_faces=gf)
+    elif a.surface:
+        rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist, pred_faces=pf,
+                                        gt_faces=gf, sample_density=dens, seed=a.sample_seed)
+    else:                                           # the two sampled point sets, point to point
+        ps, _, pres = sample_surface(pred["verts"], pred["faces"], dens, a.sample_seed)
+        gs, _, gres = sample_surface(gv, gt["faces"], dens, a.sample_seed)
+        rec["geometry"] = mesh_distance(ps, gs, a.threshold, a.max_dist)
+        rec["geometry"]["sampled"] = [pres["n_samples"], gres["n_samples"]]
     print("geometry: " + json.dumps(rec["geometry"]))
     return rec
 

@@ -365,6 +365,10 @@ SIGNATURES = {
     "ucsa_cluster_reduce": (C.c_int32, [_p, _p, _p, _p, _u32, _p, _p, _u32, _p, _p, _p, _p, _p,
                                         _p]),
     "ucsa_cluster_faces": (C.c_int32, [_p, _u32, _p, _u32, _p, _p, _p]),
+    # ---- area-uniform sample points on a triangle mesh ----
+    "ucsa_face_sample_counts": (C.c_int32, [_p, _u32, _p, _u32, _f, _u32, _p, _p, _p]),
+    "ucsa_mesh_surface_samples": (C.c_int32, [_p, _u32, _p, _u32, _p, _u32, _u32, _p, _p, _p, _p,
+                                              _p, _p, _p, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 import os
 import threading
 from typing import Optional, Tuple
@@ -2770,4 +2771,106 @@ def simplify_mesh(verts, faces, cell, normals=None, rgb=None, labels=None,
     out["origin"], out["cell"], out["dims"] = tuple(float(v) for v in lo), cell, dims
     out["degenerate"] = nf - n_kept
     out["duplicate"] = n_kept - int(face_index.numel())
+    return out
+
+
+# ---------------------------------------------------------------------------
+# area-uniform sample points on a triangle mesh
+# ---------------------------------------------------------------------------
+SAMPLE_MAX_SAMPLES = 0x7FFFFFFF
+
+
+def sample_mesh_surface(verts, faces, density, seed: int = 0, normals=None, rgb=None,
+                        labels=None, max_samples: int = 1 << 26):
+    """A deterministic, area-uniform, low-discrepancy point set on the surface of
+    a triangle mesh, ``density`` points per unit area: the query points of 3D
+    scores that weigh a surface by its area and not by its tessellation.
+    ``verts`` float32 [V,3] and ``faces`` int32 [F,3] on the GPU; per vertex and
+    optional ``normals`` float32 [V,3], ``rgb`` uint8 [V,3], ``labels`` an
+    integer tensor [V] with values 0..255.  ``seed`` is a uint32.  -> dict:
+    ``points`` float32 [S,3], ``face`` int32 [S] (ascending), ``bary`` float32
+    [S,3] (multiples of 2^-24, non-negative, summing to exactly 1) and, for the
+    inputs given, ``normals`` (the blend, normalised; zero where it vanishes),
+    ``rgb`` uint8 (the blend, half up), ``labels`` uint8 (of the corner with the
+    largest weight, the first on a tie, as ``transfer_labels`` decides); per
+    face ``area`` float32 [F], ``count`` int32 [F] (area * density, rounded
+    down after adding a hashed offset in [0, 1): no bias, so faces far smaller
+    than 1 / density are sampled at the right rate) and ``first`` int32 [F+1]
+    (the samples of face f are rows first[f] .. first[f+1]); ``n_samples`` = S
+    and ``density`` (as rounded to float32).  A face with a corner index outside
+    [0, V), a non-finite corner or a non-finite area has area 0 and no sample.
+    A sample depends on (seed, face index, index inside the face) and the
+    face's corners alone: a higher density keeps every earlier sample of a face
+    and appends new ones, and editing one face moves no sample of another.
+    More than ``max_samples`` (at most 2^31-1) samples is an error raised before
+    anything of that size is allocated.  F = 0, V = 0 and S = 0 are valid; the
+    inputs are not modified.  The counts and the samples are kernels
+    (ucsa_face_sample_counts, ucsa_mesh_surface_samples in include/ucsa_hip.h);
+    the prefix sum is torch on the device, in int64."""
+    pts = _points3(verts, "verts")
+    dev = pts.device
+    n = int(pts.shape[0])
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.device == dev
+            and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3):
+        raise _lib.UcsaError("faces must be an int32 [F,3] tensor on the vertices' GPU: the HIP "
+                             "path has no CPU fallback")
+    if faces.shape[0] > 0x7FFFFFFF:
+        raise _lib.UcsaError("faces must have at most 2^31-1 rows")
+    fc = faces.contiguous()
+    nf = int(fc.shape[0])
+    nrm = _vertex_rows(normals, "normals", torch.float32, (n, 3), dev)
+    col = _vertex_rows(rgb, "rgb", torch.uint8, (n, 3), dev)
+    lab = None
+    if labels is not None:
+        if not (torch.is_tensor(labels) and labels.is_cuda and labels.device == dev
+                and not labels.dtype.is_floating_point and not labels.dtype.is_complex
+                and labels.dtype != torch.bool and tuple(labels.shape) == (n,)):
+            raise _lib.UcsaError(f"labels must be an integer tensor of shape [{n}] on the "
+                                 "vertices' GPU")
+        if n and (int(labels.min()) < 0 or int(labels.max()) > 255):
+            raise _lib.UcsaError("labels must be in 0..255")
+        lab = labels.to(torch.uint8).contiguous()
+    try:
+        density = float(torch.tensor(float(density), dtype=torch.float32))
+    except (TypeError, ValueError):
+        raise _lib.UcsaError(f"density must be a number, got {density!r}")
+    if not (density > 0 and math.isfinite(density)):
+        raise _lib.UcsaError(f"density must be positive and finite in float32, got {density!r}")
+    try:
+        seed, max_samples = operator.index(seed), operator.index(max_samples)
+    except TypeError:
+        raise _lib.UcsaError("seed and max_samples must be integers")
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise _lib.UcsaError(f"seed must be in 0..2^32-1, got {seed!r}")
+    if max_samples < 0:
+        raise _lib.UcsaError(f"max_samples must not be negative, got {max_samples!r}")
+    max_samples = min(max_samples, SAMPLE_MAX_SAMPLES)
+    area = torch.empty(nf, dtype=torch.float32, device=dev)
+    count = torch.empty(nf, dtype=torch.int32, device=dev)
+    check(lib().ucsa_face_sample_counts(_ptr(pts) if n else None, n, _ptr(fc), nf, density, seed,
+                                        _ptr(area), _ptr(count), _stream()),
+          "ucsa_face_sample_counts")
+    first64 = torch.zeros(nf + 1, dtype=torch.int64, device=dev)
+    first64[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+    S = int(first64[nf])
+    if S > max_samples:
+        raise _lib.UcsaError(f"density {density!r} gives {S} samples, more than max_samples = "
+                             f"{max_samples}: lower density")
+    first = first64.to(torch.int32)
+    out = {"points": torch.empty((S, 3), dtype=torch.float32, device=dev),
+           "face": torch.empty(S, dtype=torch.int32, device=dev),
+           "bary": torch.empty((S, 3), dtype=torch.float32, device=dev)}
+    if nrm is not None:
+        out["normals"] = torch.empty((S, 3), dtype=torch.float32, device=dev)
+    if col is not None:
+        out["rgb"] = torch.empty((S, 3), dtype=torch.uint8, device=dev)
+    if lab is not None:
+        out["labels"] = torch.empty(S, dtype=torch.uint8, device=dev)
+    check(lib().ucsa_mesh_surface_samples(_ptr(pts) if n else None, n, _ptr(fc), nf, _ptr(first), S,
+                                          seed, _ptr(nrm), _ptr(col), _ptr(lab),
+                                          _ptr(out["points"]), _ptr(out["face"]),
+                                          _ptr(out["bary"]), _ptr(out.get("normals")),
+                                          _ptr(out.get("rgb")), _ptr(out.get("labels")),
+                                          _stream()), "ucsa_mesh_surface_samples")
+    out.update(area=area, count=count, first=first, n_samples=S, density=density)
     return out

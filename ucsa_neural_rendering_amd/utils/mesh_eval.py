@@ -15,7 +15,13 @@ Vertex to vertex is right only when both meshes are tessellated about equally
 finely.  Where the target's faces are given (``src_faces``, ``pred_faces``,
 ``gt_faces``) the search is for the nearest point on its surface instead
 (``ops.triangle_grid`` + ``ops.nearest_triangle``): a vertex in the middle of a
-large ground-truth triangle is then at distance 0, not half an edge away."""
+large ground-truth triangle is then at distance 0, not half an edge away.
+
+That settles the target.  The query points are a mesh's vertices unless
+``sample_density`` is given: then they are drawn from the mesh's surface
+(``ops.sample_mesh_surface``: so many points per unit area, deterministic for a
+``seed``), so that a wall of two triangles weighs by its area and not by its
+four corners, and a hole in the middle of it costs what it covers."""
 from __future__ import annotations
 
 import numpy as np
@@ -40,6 +46,29 @@ def _labels(l, n, device):
 def _faces(f, device):
     t = torch.as_tensor(np.asarray(f) if not torch.is_tensor(f) else f)
     return t.to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def sample_surface(verts, faces, density, seed=0, labels=None, samples=None):
+    """Query points on a mesh's surface (``ops.sample_mesh_surface``) -> (points
+    float32 [S,3] on the device, labels int32 [S] or None, the op's dict).
+    ``labels`` [V] (0..255) are carried to the samples: each takes the label of
+    its face's corner with the largest weight.  ``samples=N`` instead of a
+    density asks for about N points: density = N / sum(area), the sum taken in
+    float64 on the host from the op's ``area`` array."""
+    v = _verts(verts)
+    f = _faces(faces, v.device)
+    lab = None if labels is None else _labels(labels, v.shape[0], v.device)
+    if (density is None) == (samples is None):
+        raise ValueError("give one of density and samples")
+    if density is None:
+        area = ops.sample_mesh_surface(v, f, 1.0, seed, max_samples=1 << 31)["area"]
+        total = float(np.sum(area.cpu().numpy(), dtype=np.float64))
+        if not total > 0:
+            raise ValueError("the mesh has no area to put samples on")
+        density = float(samples) / total
+    res = ops.sample_mesh_surface(v, f, density, seed, labels=lab)
+    got = None if lab is None else res["labels"].to(torch.int32)
+    return res["points"], got, res
 
 
 def transfer_labels(src_verts, src_labels, dst_verts, max_dist, return_match=False,
@@ -91,17 +120,32 @@ def _score(pred, index, gt_labels, C):
 
 
 def score_labels_3d(pred_verts, pred_labels, gt_verts, gt_labels, max_dist, C=40,
-                    pred_faces=None):
+                    pred_faces=None, gt_faces=None, sample_density=None, seed=0):
     """The predicted labels at the ground-truth vertices (``transfer_labels``)
     scored through ``score_label_maps``: ground truth 0 or above ``C`` is ignored;
     a prediction of 0, or no predicted vertex within ``max_dist``, counts as
     wrong, exactly as the 2D score treats it.  -> {"mIoU", "total_acc",
     "mean_acc", "vertices" (scored), "unmatched" (the share of scored vertices
     without a match)}.  ``pred_faces``: the labels come from the nearest point of
-    the predicted surface (``transfer_labels`` with ``src_faces``)."""
-    pred, index = transfer_labels(pred_verts, pred_labels, gt_verts, max_dist,
+    the predicted surface (``transfer_labels`` with ``src_faces``).
+
+    ``gt_faces`` with ``sample_density``: the score is taken at points sampled
+    from the ground-truth surface (``sample_surface``, ``seed``), each carrying
+    the label of its face's nearest corner, and so weighs every class by its
+    area; "vertices" is then the number of scored samples and "sampled" the
+    number of samples."""
+    if sample_density is None:
+        pred, index = transfer_labels(pred_verts, pred_labels, gt_verts, max_dist,
+                                      return_match=True, src_faces=pred_faces)[:2]
+        return _score(pred, index, gt_labels, C)
+    if gt_faces is None:
+        raise ValueError("sample_density needs gt_faces")
+    points, labels, res = sample_surface(gt_verts, gt_faces, sample_density, seed, gt_labels)
+    pred, index = transfer_labels(pred_verts, pred_labels, points, max_dist,
                                   return_match=True, src_faces=pred_faces)[:2]
-    return _score(pred, index, gt_labels, C)
+    out = _score(pred, index, labels, C)
+    out["sampled"] = res["n_samples"]
+    return out
 
 
 def voxel_centres(volume, voxel_labels):
@@ -119,15 +163,18 @@ def voxel_centres(volume, voxel_labels):
     return centres, lab[ijk[:, 0], ijk[:, 1], ijk[:, 2]].to(torch.int32)
 
 
-def score_voxel_labels_3d(volume, voxel_labels, gt_verts, gt_labels, max_dist, C=40):
+def score_voxel_labels_3d(volume, voxel_labels, gt_verts, gt_labels, max_dist, C=40,
+                          gt_faces=None, sample_density=None, seed=0):
     """``score_labels_3d`` with the centres of the labelled voxels of a voxel map
     (``utils.voxel_map``: the volume and its resolved labels) as the predicted
-    point set."""
+    point set; ``gt_faces``, ``sample_density`` and ``seed`` as there."""
     centres, lab = voxel_centres(volume, voxel_labels)
-    return score_labels_3d(centres, lab, gt_verts, gt_labels, max_dist, C)
+    return score_labels_3d(centres, lab, gt_verts, gt_labels, max_dist, C, gt_faces=gt_faces,
+                           sample_density=sample_density, seed=seed)
 
 
-def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt_faces=None):
+def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt_faces=None,
+                  sample_density=None, seed=0):
     """Vertex-to-vertex distances both ways -> {"accuracy": mean pred -> gt,
     "completeness": mean gt -> pred, "chamfer": their mean, "precision": the share
     of pred vertices within ``threshold`` of gt, "recall": the share of gt
@@ -139,9 +186,25 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
     A direction whose target has faces measures vertex to surface: ``gt_faces``
     [F,3] the pred -> gt direction (accuracy, precision), ``pred_faces`` the
     gt -> pred direction (completeness, recall).  With either given the dict
-    also holds "surface": (pred -> gt is to the surface, gt -> pred is)."""
+    also holds "surface": (pred -> gt is to the surface, gt -> pred is).
+
+    ``sample_density``: a side that has faces is measured from points sampled on
+    its surface at that density (``sample_surface``, ``seed``) instead of from
+    its vertices: pred -> gt from the samples of ``pred_faces``, gt -> pred from
+    those of ``gt_faces``.  Recall then falls by the share of the ground-truth
+    area that the predicted mesh leaves uncovered.  The dict also holds
+    "sampled": [n_pred, n_gt], the number of samples on each side (0 for a side
+    without faces, which is measured from its vertices)."""
     pred = _verts(pred_verts)
     gt = _verts(gt_verts, pred.device)
+    pred_from, gt_from, sampled = pred, gt, [0, 0]
+    if sample_density is not None:
+        if pred_faces is not None:
+            pred_from, _, res = sample_surface(pred, pred_faces, sample_density, seed)
+            sampled[0] = res["n_samples"]
+        if gt_faces is not None:
+            gt_from, _, res = sample_surface(gt, gt_faces, sample_density, seed)
+            sampled[1] = res["n_samples"]
 
     def one_way(a, b, b_faces):
         if a.shape[0] == 0:
@@ -155,8 +218,8 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
                         torch.full_like(dist2, float(max_dist), dtype=torch.float64))
         return float(d.mean()), float(((index >= 0) & (d <= float(threshold))).double().mean())
 
-    acc, prec = one_way(pred, gt, gt_faces)
-    comp, rec = one_way(gt, pred, pred_faces)
+    acc, prec = one_way(pred_from, gt, gt_faces)
+    comp, rec = one_way(gt_from, pred, pred_faces)
     if not prec + rec >= 0:                         # an empty set: nan
         f = float("nan")
     elif prec + rec == 0:
@@ -167,4 +230,6 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
            "precision": prec, "recall": rec, "fscore": f}
     if pred_faces is not None or gt_faces is not None:
         out["surface"] = (gt_faces is not None, pred_faces is not None)
+    if sample_density is not None:
+        out["sampled"] = sampled
     return out
