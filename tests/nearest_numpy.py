@@ -7,7 +7,8 @@ cannot depend on the cell size, the grid's origin or the order of the queries.
 
 ``nearest_point_grid`` is a model of the kernel's traversal: the same cell
 arithmetic, the same rings, the same stop rule with the same margins, in the
-same float32 expressions.  tests/test_nearest_cpu.py holds it to the brute
+same float32 expressions.  The traversal itself is ``ring_walk``, which
+tests/surface_numpy.py calls too, as both kernels call pg_walk.  tests/test_nearest_cpu.py holds it to the brute
 force byte for byte, which proves the pruning before any GPU run.  Inside a
 ring the kernel takes candidates one by one and the model takes them all at
 once; the best candidate is the minimum of (d2, index) over the visited set,
@@ -142,19 +143,20 @@ def point_grid(points, cell=None, origin=None):
             "sorted_points": sp.view(F), "n": n}
 
 
-def nearest_point_grid(points, queries, max_dist, cell=None, origin=None, stats=None):
-    """The kernel's traversal.  Per query: rings r = 0, 1, ... of cells around
-    the query's clamped cell, clipped to per-axis limits that start at the grid
-    and close in as slabs of cells are proven too far; a ring's candidates
-    compete by (d2, index); the walk ends when no slab is left."""
-    g = point_grid(points, cell, origin)
-    Q = _f32(queries)
-    lim2 = limit2_of(max_dist)
-    nq, n = Q.shape[0], g["n"]
-    o, h, dims = g["origin"], g["cell"], g["dims"]
+def ring_walk(origin, cell, dims, offsets, n, Q, lim2, ks, candidate):
+    """The kernels' traversal (pg_walk in csrc/cell_grid.h), once for both
+    searches -> (best float32 [Q], bidx uint32 [Q], cells visited).  Per query:
+    rings r = 0, 1, ... of cells around the query's clamped cell, clipped to
+    per-axis limits that start at the grid and close in as slabs of cells are
+    proven too far; a ring's candidates compete by (d2, index); the walk ends
+    when no slab is left.  ``n`` is the number of sorted candidates, ``ks`` the
+    slack of a wall distance (K for points, KS for faces) and ``candidate(qi, k)``
+    -> (d2 float32, j uint32) scores the candidates at sorted positions ``k``
+    for the queries ``qi``."""
+    o, h = origin, cell
+    nq = Q.shape[0]
     dm = np.asarray(dims, np.int64)
-    sp, offsets = g["sorted_points"], g["offsets"].astype(np.int64)
-    sidx = sp[:, 3].view(np.uint32) if n else np.zeros(0, np.uint32)
+    offsets = offsets.astype(np.int64)
     best = np.full(nq, lim2, F)                  # B = min(best d2, limit2)
     bidx = np.full(nq, NONE, np.uint32)
     visited = 0
@@ -162,7 +164,7 @@ def nearest_point_grid(points, queries, max_dist, cell=None, origin=None, stats=
         with np.errstate(all="ignore"):
             cq, finite, _ = cell_coords(Q, o, h, dims)
             top = o + dm.astype(F) * h                               # the box's far corner
-            S = K * ((np.abs(o) + np.abs(top))[None, :] + np.abs(Q))  # slack per query and axis
+            S = ks * ((np.abs(o) + np.abs(top))[None, :] + np.abs(Q))  # slack per query and axis
             e = np.maximum(np.maximum(o[None, :] - Q, Q - top[None, :]) - S, F(0))
             out2 = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
             far = out2 > lim2 * ONE_PLUS_K
@@ -200,11 +202,7 @@ def nearest_point_grid(points, queries, max_dist, cell=None, origin=None, stats=
                 qi = np.repeat(qs, cnt)
                 k = np.repeat(bs - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()))
                 with np.errstate(all="ignore"):
-                    dx = Q[qi, 0] - sp[k, 0]
-                    dy = Q[qi, 1] - sp[k, 1]
-                    dz = Q[qi, 2] - sp[k, 2]
-                    d2 = (dx * dx + dy * dy) + dz * dz
-                    j = sidx[k]
+                    d2, j = candidate(qi, k)
                     take = (d2 < best[qi]) | ((d2 == best[qi]) & (j < bidx[qi]))
                 qi, d2, j = qi[take], d2[take], j[take]
                 low = np.full(nq, np.inf, F)                      # each query's least d2 first:
@@ -237,11 +235,34 @@ def nearest_point_grid(points, queries, max_dist, cell=None, origin=None, stats=
                     left |= has & ~cut
             active[A[~left]] = False
             r += 1
+    return best, bidx, visited
+
+
+def _search_result(best, bidx, dims, visited, stats):
+    """(index int32, dist2 float32) of a walk's (best, bidx), and the stats"""
     if stats is not None:
         stats["cells_visited"] = visited
         stats["cells"] = int(np.prod(dims))
     hit = bidx != NONE
     index = np.where(hit, bidx, 0).astype(np.int64).astype(np.int32)
     index[~hit] = -1
-    dist2 = np.where(hit, best, F(np.inf)).astype(F)
-    return index, dist2
+    return index, np.where(hit, best, F(np.inf)).astype(F)
+
+
+def nearest_point_grid(points, queries, max_dist, cell=None, origin=None, stats=None):
+    """ucsa_nearest_point's traversal: ``ring_walk`` over ``point_grid``'s sorted
+    points with the point search's candidate test and slack K."""
+    g = point_grid(points, cell, origin)
+    Q = _f32(queries)
+    sp = g["sorted_points"]
+    sidx = sp[:, 3].view(np.uint32)
+
+    def candidate(qi, k):
+        dx = Q[qi, 0] - sp[k, 0]
+        dy = Q[qi, 1] - sp[k, 1]
+        dz = Q[qi, 2] - sp[k, 2]
+        return (dx * dx + dy * dy) + dz * dz, sidx[k]
+
+    best, bidx, visited = ring_walk(g["origin"], g["cell"], g["dims"], g["offsets"], g["n"], Q,
+                                    limit2_of(max_dist), K, candidate)
+    return _search_result(best, bidx, g["dims"], visited, stats)

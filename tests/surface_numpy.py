@@ -9,8 +9,9 @@ the queries.
 
 ``nearest_triangle_grid`` is a model of the kernel's traversal: the same cell
 arithmetic, the same registration of a face in the box of cells between its
-corners' cells, the same rings, the same stop rule with the same margins, in the
-same float32 expressions.  tests/test_surface_cpu.py holds it to the brute force
+corners' cells, and the rings and the stop rule of tests/nearest_numpy.py's
+``ring_walk`` with this search's candidate test and margin, in the same float32
+expressions.  tests/test_surface_cpu.py holds it to the brute force
 byte for byte, which proves the pruning before any GPU run.  Inside a ring the
 kernel takes candidates one by one and the model takes them all at once; the
 best candidate is the minimum of (dist2, face) over the visited set, which no
@@ -19,8 +20,8 @@ import math
 
 import numpy as np
 
-from tests.nearest_numpy import (F, K, MAX_CELLS, NONE, ONE_PLUS_K, _f32, cell_coords,
-                                 limit2_of)
+from tests.nearest_numpy import (F, K, MAX_CELLS, _f32, _search_result, cell_coords, limit2_of,
+                                 ring_walk)
 
 # The slack of a wall distance is twice the point grid's (docs/DESIGN_NOTEBOOK.md,
 # section NT): the closest point of a face is seven and a half roundings away
@@ -219,106 +220,22 @@ def triangle_grid(verts, faces, cell=None, origin=None):
 
 
 def nearest_triangle_grid(verts, faces, queries, max_dist, cell=None, origin=None, stats=None):
-    """The kernel's traversal.  Per query: rings r = 0, 1, ... of cells around
-    the query's clamped cell, clipped to per-axis limits that start at the grid
-    and close in as slabs of cells are proven too far; a ring's candidates
-    compete by (dist2, face); the walk ends when no slab is left."""
+    """ucsa_nearest_triangle's traversal: ``ring_walk`` over ``triangle_grid``'s
+    records with the face search's candidate test and slack KS."""
     g = triangle_grid(verts, faces, cell, origin)
     Q = _f32(queries)
-    lim2 = limit2_of(max_dist)
-    nq, n = Q.shape[0], g["n_pairs"]
-    o, h, dims = g["origin"], g["cell"], g["dims"]
-    dm = np.asarray(dims, np.int64)
-    rec, offsets = g["records"], g["offsets"].astype(np.int64)
-    sidx = np.ascontiguousarray(rec[:, 3]).view(np.uint32) if n else np.zeros(0, np.uint32)
-    best = np.full(nq, lim2, F)                  # B = min(best dist2, limit2)
-    bidx = np.full(nq, NONE, np.uint32)
-    visited = 0
-    if nq and n:
-        with np.errstate(all="ignore"):
-            cq, finite, _ = cell_coords(Q, o, h, dims)
-            top = o + dm.astype(F) * h                                # the box's far corner
-            S = KS * ((np.abs(o) + np.abs(top))[None, :] + np.abs(Q))  # slack per query and axis
-            e = np.maximum(np.maximum(o[None, :] - Q, Q - top[None, :]) - S, F(0))
-            out2 = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
-            far = out2 > lim2 * ONE_PLUS_K
-        active = finite & ~far
-        lo = np.zeros((nq, 3), np.int64)
-        hi = np.broadcast_to(dm - 1, (nq, 3)).copy()
-        r = 0
-        while active.any():
-            A = np.nonzero(active)[0]
-            d = np.arange(-r, r + 1)
-            DX, DY = [a.reshape(-1) for a in np.meshgrid(d, d, indexing="ij")]
-            edge = (np.abs(DX) == r) | (np.abs(DY) == r)
-            x = cq[A, 0, None] + DX[None, :]
-            y = cq[A, 1, None] + DY[None, :]
-            inxy = ((x >= lo[A, 0, None]) & (x <= hi[A, 0, None]) &
-                    (y >= lo[A, 1, None]) & (y <= hi[A, 1, None]))
-            zc, zl, zh = cq[A, 2, None], lo[A, 2, None], hi[A, 2, None]
-            runs = []                                               # (mask, z0, z1) per column
-            runs.append((inxy & edge[None, :], np.maximum(zc - r, zl) + 0 * x,
-                         np.minimum(zc + r, zh) + 0 * x))
-            if r > 0:
-                runs.append((inxy & ~edge[None, :] & (zc - r >= zl), zc - r + 0 * x, zc - r + 0 * x))
-                runs.append((inxy & ~edge[None, :] & (zc + r <= zh), zc + r + 0 * x, zc + r + 0 * x))
-            qs, bs, es = [], [], []
-            for m, z0, z1 in runs:
-                m = m & (z0 <= z1)
-                row = (x[m] * dims[1] + y[m]) * dims[2]
-                qs.append(np.broadcast_to(A[:, None], m.shape)[m])
-                bs.append(np.clip(offsets[row + z0[m]], 0, n))
-                es.append(np.clip(offsets[row + z1[m] + 1], 0, n))
-                visited += int((z1[m] - z0[m] + 1).sum())
-            qs, bs, es = np.concatenate(qs), np.concatenate(bs), np.concatenate(es)
-            cnt = np.maximum(es - bs, 0)
-            if cnt.sum():
-                qi = np.repeat(qs, cnt)
-                k = np.repeat(bs - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()))
-                with np.errstate(all="ignore"):
-                    a, b, c = (tuple(rec[k, 4 * s + t] - Q[qi, t] for t in range(3))
-                               for s in range(3))
-                    _, _, d2 = closest(a, b, c)
-                    j = sidx[k]
-                    take = (d2 < best[qi]) | ((d2 == best[qi]) & (j < bidx[qi]))
-                qi, d2, j = qi[take], d2[take], j[take]
-                low = np.full(nq, np.inf, F)                      # each query's least dist2 first:
-                np.minimum.at(low, qi, d2)                        # few candidates reach the sort
-                take = d2 == low[qi]
-                qi, d2, j = qi[take], d2[take], j[take]
-                first = np.lexsort((j, d2, qi))
-                qi, d2, j = qi[first], d2[first], j[first]
-                head = np.ones(qi.size, bool)
-                head[1:] = qi[1:] != qi[:-1]
-                best[qi[head]] = d2[head]
-                bidx[qi[head]] = j[head]
-            # the stop rule: a slab of unvisited cells beyond a wall is dropped once
-            # the wall is provably farther than B, strictly and with the margins
-            left = np.zeros(A.size, bool)
-            with np.errstate(all="ignore"):
-                bk = best[A] * ONE_PLUS_K
-                for ax in range(3):
-                    m_hi = cq[A, ax] + r + 1                         # first cell of the far slab
-                    has = m_hi <= hi[A, ax]
-                    gap = ((o[ax] + m_hi.astype(F) * h) - Q[A, ax]) - S[A, ax]
-                    cut = has & (gap > 0) & (gap * gap > bk)
-                    hi[A, ax] = np.where(cut, cq[A, ax] + r, hi[A, ax])
-                    left |= has & ~cut
-                    m_lo = cq[A, ax] - r - 1                         # last cell of the near slab
-                    has = m_lo >= lo[A, ax]
-                    gap = (Q[A, ax] - (o[ax] + (m_lo + 1).astype(F) * h)) - S[A, ax]
-                    cut = has & (gap > 0) & (gap * gap > bk)
-                    lo[A, ax] = np.where(cut, cq[A, ax] - r, lo[A, ax])
-                    left |= has & ~cut
-            active[A[~left]] = False
-            r += 1
-    if stats is not None:
-        stats["cells_visited"] = visited
-        stats["cells"] = int(np.prod(dims))
-    hit = bidx != NONE
-    face = np.where(hit, bidx, 0).astype(np.int64).astype(np.int32)
-    face[~hit] = -1
-    dist2 = np.where(hit, best, F(np.inf)).astype(F)
+    rec = g["records"]
+    sidx = np.ascontiguousarray(rec[:, 3]).view(np.uint32)
+
+    def candidate(qi, k):
+        a, b, c = (tuple(rec[k, 4 * s + t] - Q[qi, t] for t in range(3)) for s in range(3))
+        return closest(a, b, c)[2], sidx[k]
+
+    best, bidx, visited = ring_walk(g["origin"], g["cell"], g["dims"], g["offsets"],
+                                    g["n_pairs"], Q, limit2_of(max_dist), KS, candidate)
+    face, dist2 = _search_result(best, bidx, g["dims"], visited, stats)
+    hit = face >= 0
+    nq = Q.shape[0]
     bary = np.zeros((nq, 3), F)
     if hit.any():
         # the winner's weights: the same expressions on the same operands as in the walk

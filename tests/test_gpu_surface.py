@@ -51,6 +51,40 @@ def test_bytes_equal_the_definition_at_three_cell_sizes_and_both_query_orders(na
             assert grid[k].cpu().numpy().tobytes() == g[k].tobytes(), (name, cell, k)
 
 
+def test_the_two_searches_agree_on_faces_that_are_points():
+    """The two instantiations of the one ring walk (pg_walk in csrc/cell_grid.h)
+    against each other: over the faces [i, i, i] the face search is the point
+    search.  A degenerate face lands in the first corner region, bary (1, 0, 0),
+    and its dist2 is the point search's expression on negated differences."""
+    ops = _ops()
+    rng = np.random.default_rng(17)
+    pts = rng.uniform(-1.0, 1.0, (200, 3)).astype(F)
+    pts[17] = pts[3]                                             # a tie: the smaller index wins
+    pts[40, 1] = np.nan                                          # matches nothing in either search
+    faces = np.repeat(np.arange(200, dtype=np.int32)[:, None], 3, axis=1)
+    q = np.concatenate([rng.uniform(-1.3, 1.3, (300, 3)).astype(F), pts[:20]])
+    P, Fc, Q = _cu(pts).view(-1, 3), _cu(faces).view(-1, 3), _cu(q).view(-1, 3)
+    misses = 0
+    for md in (0.05, 0.3, 5.0):
+        ref_p = NN.nearest_point(pts, q, md)
+        ref_t = SN.nearest_triangle(pts, faces, q, md)
+        hit = ref_p[0] >= 0
+        assert hit.any()
+        misses += int((~hit).sum())                              # none at 5.0: every query matches
+        for cell in (None, 0.07, 1.5):
+            pgrid, tgrid = ops.point_grid(P, cell), ops.triangle_grid(P, Fc, cell)
+            for sort_queries in (True, False):
+                index, d2p = (t.cpu().numpy() for t in
+                              ops.nearest_point(pgrid, Q, md, sort_queries=sort_queries))
+                face, d2t, bary = gpu_nearest(tgrid, q, md, sort_queries)
+                where = (md, cell, sort_queries)
+                assert face.tobytes() == index.tobytes() and d2t.tobytes() == d2p.tobytes(), where
+                assert (bary[hit] == np.array([1, 0, 0], F)).all() and (bary[~hit] == 0).all(), where
+                assert index.tobytes() == ref_p[0].tobytes() and d2p.tobytes() == ref_p[1].tobytes(), where
+                assert same((face, d2t, bary), ref_t), where
+    assert misses > 0
+
+
 def raw_call(l, grid, queries, max_dist, out_face, out_dist2, out_bary, q_order=None, **over):
     """ucsa_nearest_triangle with the grid's arguments; ``over`` replaces any of them by name"""
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())

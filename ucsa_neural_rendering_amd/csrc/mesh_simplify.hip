@@ -138,23 +138,6 @@ __global__ void __launch_bounds__(PG_THREADS) k_cluster_faces(const int32_t* __r
   keep[f] = ok ? 1u : 0u;
 }
 
-// origin finite, cell > 0 and finite, dims in 1..2^18 each (there is no per-cell
-// table, so PG_MAX_CELLS does not apply), the box's far corner finite: -> 0, or
-// the index (1..3) of the offending one
-inline int vc_grid_args(const float* origin, float cell, const uint32_t* dims, GridArgs& g) {
-  if (!origin || !(pg_host_finite(origin[0]) && pg_host_finite(origin[1]) && pg_host_finite(origin[2]))) return 1;
-  if (!(cell > 0.0f) || !pg_host_finite(cell)) return 2;
-  if (!dims) return 3;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] == 0 || dims[a] > VC_MAX_DIM) return 3;
-    g.o[a] = origin[a];
-    g.d[a] = dims[a];
-    if (!pg_host_finite(origin[a] + (float)dims[a] * cell)) return 2;
-  }
-  g.cell = cell;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int32_t ucsa_vertex_cluster_keys(const float* verts, uint32_t n, const float* origin,
@@ -162,7 +145,8 @@ extern "C" int32_t ucsa_vertex_cluster_keys(const float* verts, uint32_t n, cons
                                             const uint8_t* labels, int64_t* keys, void* stream) {
   UCSA_CHECK_ARG(n <= 0x7FFFFFFFu, 1);
   GridArgs g;
-  const int bad = vc_grid_args(origin, cell, dims, g);
+  // dims of at most 2^18 each; there is no per-cell table, so no cap on their product
+  const int bad = pg_grid_args(origin, cell, dims, g, VC_MAX_DIM, ~0ull);
   UCSA_CHECK_ARG(bad != 1, 2);
   UCSA_CHECK_ARG(bad != 2, 3);
   UCSA_CHECK_ARG(bad != 3, 4);

@@ -12,7 +12,7 @@
 //                  [0, nv) or a non-finite corner.
 // k_tri_pairs      a lane per face: the (linear cell, face) pairs of that box in
 //                  x, y, z order at first[f] ...: fixed positions, no atomics.
-// k_nearest_tri    a lane per query: k_nearest's ring walk (point_grid.hip) over
+// k_nearest_tri    a lane per query: the ring walk of cell_grid.h (pg_walk) over
 //                  records of three float4 per (cell, face) pair, sorted by cell
 //                  with faces ascending inside a cell: a cell's candidates are
 //                  contiguous 16-byte loads and no index is chased.  A face
@@ -31,10 +31,9 @@
 // corners with weights v, w in [0, 1], w <= fl(1 - v), so it lies beyond the
 // wall too, up to thirteen and a half roundings of coordinates no larger than
 // |o| + |top| + |q| on that axis.  The gap is shortened by S = 2^-19 of that sum
-// (32 roundings) and its square compared with B * (1 + 2^-20).  A comparison with
-// a NaN is false: no cut, more walking, the same result.
-// Every loop is bounded by the grid's dims; offsets are clamped into
-// [0, n_pairs]; no atomics, no LDS, no waiting on another thread.
+// (32 roundings) and its square compared with B * (1 + 2^-20).
+// k_tri_pairs' loops are bounded by the grid's dims and by n_pairs; no atomics,
+// no LDS, no waiting on another thread.
 #include "cell_grid.h"
 
 namespace {
@@ -130,23 +129,17 @@ __global__ void __launch_bounds__(PG_THREADS) k_tri_no_match(uint32_t nq,
   bary[3ull * i + 2u] = 0.0f;
 }
 
-struct Walk {
-  float qx, qy, qz;
-  float best;     // B = min(best dist2, max_dist^2)
-  float v, w;     // the best face's weights of its second and third corner
-  uint32_t bidx;  // PG_NONE: no match yet
-};
-
 __device__ __forceinline__ float tg_dot(float x0, float x1, float x2, float y0, float y1, float y2) {
   return (x0 * y0 + x1 * y1) + x2 * y2;
 }
 
 // the closest point of one face to the query: (v, w) and its squared distance
 __device__ __forceinline__ void tg_closest(const float4 A, const float4 B, const float4 C,
-                                           const Walk& q, float& v, float& w, float& dist2) {
-  const float ax = A.x - q.qx, ay = A.y - q.qy, az = A.z - q.qz;
-  const float bx = B.x - q.qx, by = B.y - q.qy, bz = B.z - q.qz;
-  const float cx = C.x - q.qx, cy = C.y - q.qy, cz = C.z - q.qz;
+                                           float qx, float qy, float qz, float& v, float& w,
+                                           float& dist2) {
+  const float ax = A.x - qx, ay = A.y - qy, az = A.z - qz;
+  const float bx = B.x - qx, by = B.y - qy, bz = B.z - qz;
+  const float cx = C.x - qx, cy = C.y - qy, cz = C.z - qz;
   const float abx = bx - ax, aby = by - ay, abz = bz - az;
   const float acx = cx - ax, acy = cy - ay, acz = cz - az;
   const float d1 = tg_dot(abx, aby, abz, -ax, -ay, -az), d2 = tg_dot(acx, acy, acz, -ax, -ay, -az);
@@ -189,27 +182,26 @@ __device__ __forceinline__ void tg_closest(const float4 A, const float4 B, const
   dist2 = (px * px + py * py) + pz * pz;
 }
 
-// the candidates of the cells lin0 .. lin1 of one row (consecutive in the sorted order)
-__device__ __forceinline__ void tg_run(const float4* __restrict__ rec,
-                                       const int32_t* __restrict__ offsets, uint32_t n,
-                                       uint32_t lin0, uint32_t lin1, Walk& w) {
-  int32_t b = offsets[lin0], e = offsets[lin1 + 1u];
-  b = b < 0 ? 0 : b;
-  e = e > (int32_t)n ? (int32_t)n : e;
-  for (int32_t k = b; k < e; ++k) {  // 0 <= k < n
-    const float4 A = rec[3ull * (uint32_t)k], B = rec[3ull * (uint32_t)k + 1u],
-                 C = rec[3ull * (uint32_t)k + 2u];
-    float v, ww, d2;
-    tg_closest(A, B, C, w, v, ww, d2);
+// the state of one query's walk (cell_grid.h)
+struct FaceWalk {
+  const float4* __restrict__ rec;
+  float qx, qy, qz;
+  float best;     // B = min(best dist2, max_dist^2)
+  float v, w;     // the best face's weights of its second and third corner
+  uint32_t bidx;  // PG_NONE: no match yet
+  __device__ __forceinline__ void score(uint32_t k) {
+    const float4 A = rec[3ull * k], B = rec[3ull * k + 1u], C = rec[3ull * k + 2u];
+    float fv, fw, d2;
+    tg_closest(A, B, C, qx, qy, qz, fv, fw, d2);
     const uint32_t j = __float_as_uint(A.w);
-    if (d2 < w.best || (d2 == w.best && j < w.bidx)) {
-      w.best = d2;
-      w.bidx = j;
-      w.v = v;
-      w.w = ww;
+    if (d2 < best || (d2 == best && j < bidx)) {
+      best = d2;
+      bidx = j;
+      v = fv;
+      w = fw;
     }
   }
-}
+};
 
 __global__ void __launch_bounds__(PG_THREADS) k_nearest_tri(const float4* __restrict__ rec,
                                                             const int32_t* __restrict__ offsets,
@@ -224,7 +216,8 @@ __global__ void __launch_bounds__(PG_THREADS) k_nearest_tri(const float4* __rest
   if (t >= nq) return;
   const uint32_t qi = q_order ? (uint32_t)q_order[t] : t;
   if (qi >= nq) return;  // a malformed order writes nothing outside the outputs
-  Walk w;
+  FaceWalk w;
+  w.rec = rec;
   w.qx = queries[3ull * qi];
   w.qy = queries[3ull * qi + 1u];
   w.qz = queries[3ull * qi + 2u];
@@ -232,69 +225,7 @@ __global__ void __launch_bounds__(PG_THREADS) k_nearest_tri(const float4* __rest
   w.bidx = PG_NONE;
   w.v = 0.0f;
   w.w = 0.0f;
-  const int32_t nx = (int32_t)g.d[0], ny = (int32_t)g.d[1], nz = (int32_t)g.d[2];
-  const float h = g.cell;
-  // the box's far corner and the slack of every wall distance, per axis
-  const float topx = g.o[0] + (float)g.d[0] * h, topy = g.o[1] + (float)g.d[1] * h,
-              topz = g.o[2] + (float)g.d[2] * h;
-  const float Sx = TG_KS * ((fabsf(g.o[0]) + fabsf(topx)) + fabsf(w.qx));
-  const float Sy = TG_KS * ((fabsf(g.o[1]) + fabsf(topy)) + fabsf(w.qy));
-  const float Sz = TG_KS * ((fabsf(g.o[2]) + fabsf(topz)) + fabsf(w.qz));
-  bool walk = pg_finite3(w.qx, w.qy, w.qz);
-  if (walk) {
-    // farther than max_dist from the box that holds the faces: no ring at all
-    const float ex = fmaxf(fmaxf(g.o[0] - w.qx, w.qx - topx) - Sx, 0.0f);
-    const float ey = fmaxf(fmaxf(g.o[1] - w.qy, w.qy - topy) - Sy, 0.0f);
-    const float ez = fmaxf(fmaxf(g.o[2] - w.qz, w.qz - topz) - Sz, 0.0f);
-    const float out2 = (ex * ex + ey * ey) + ez * ez;
-    walk = !(out2 > limit2 * PG_ONE_PLUS_K);
-  }
-  if (walk) {
-    const int32_t cx = (int32_t)pg_cell((w.qx - g.o[0]) / h, g.d[0]);
-    const int32_t cy = (int32_t)pg_cell((w.qy - g.o[1]) / h, g.d[1]);
-    const int32_t cz = (int32_t)pg_cell((w.qz - g.o[2]) / h, g.d[2]);
-    int32_t lox = 0, loy = 0, loz = 0, hix = nx - 1, hiy = ny - 1, hiz = nz - 1;
-    // r grows by one per pass and a slab exists only while cx + r + 1 <= hix or
-    // cx - r - 1 >= lox (and so on): at most max(nx, ny, nz) passes
-    for (int32_t r = 0;; ++r) {
-      const int32_t x0 = max(cx - r, lox), x1 = min(cx + r, hix);
-      const int32_t y0 = max(cy - r, loy), y1 = min(cy + r, hiy);
-      const int32_t z0 = max(cz - r, loz), z1 = min(cz + r, hiz);
-      for (int32_t x = x0; x <= x1; ++x) {
-        const bool xedge = x == cx - r || x == cx + r;
-        for (int32_t y = y0; y <= y1; ++y) {
-          const uint32_t row = (uint32_t)(x * ny + y) * (uint32_t)nz;
-          if (xedge || y == cy - r || y == cy + r) {
-            if (z0 <= z1) tg_run(rec, offsets, n, row + (uint32_t)z0, row + (uint32_t)z1, w);
-          } else {  // r >= 1 here: the two caps of the column
-            if (cz - r >= loz) tg_run(rec, offsets, n, row + (uint32_t)(cz - r), row + (uint32_t)(cz - r), w);
-            if (cz + r <= hiz) tg_run(rec, offsets, n, row + (uint32_t)(cz + r), row + (uint32_t)(cz + r), w);
-          }
-        }
-      }
-      const float bk = w.best * PG_ONE_PLUS_K;
-      bool left = false;
-      if (cx + r + 1 <= hix) {
-        if (pg_cut(g.o[0], h, w.qx, Sx, bk, cx + r + 1, true)) hix = cx + r; else left = true;
-      }
-      if (cx - r - 1 >= lox) {
-        if (pg_cut(g.o[0], h, w.qx, Sx, bk, cx - r, false)) lox = cx - r; else left = true;
-      }
-      if (cy + r + 1 <= hiy) {
-        if (pg_cut(g.o[1], h, w.qy, Sy, bk, cy + r + 1, true)) hiy = cy + r; else left = true;
-      }
-      if (cy - r - 1 >= loy) {
-        if (pg_cut(g.o[1], h, w.qy, Sy, bk, cy - r, false)) loy = cy - r; else left = true;
-      }
-      if (cz + r + 1 <= hiz) {
-        if (pg_cut(g.o[2], h, w.qz, Sz, bk, cz + r + 1, true)) hiz = cz + r; else left = true;
-      }
-      if (cz - r - 1 >= loz) {
-        if (pg_cut(g.o[2], h, w.qz, Sz, bk, cz - r, false)) loz = cz - r; else left = true;
-      }
-      if (!left) break;
-    }
-  }
+  pg_walk(offsets, n, g, TG_KS, limit2, w);
   const bool hit = w.bidx != PG_NONE;
   face[qi] = hit ? (int32_t)w.bidx : -1;
   dist2[qi] = hit ? w.best : INFINITY;
@@ -356,23 +287,12 @@ extern "C" int32_t ucsa_nearest_triangle(const float* records, const int32_t* of
                                          const uint32_t* dims, const float* queries,
                                          const int32_t* q_order, uint32_t nq, float max_dist,
                                          int32_t* face, float* dist2, float* bary, void* stream) {
-  UCSA_CHECK_ARG(n_pairs <= 0x7FFFFFFFu, 2);
   GridArgs g;
-  const int bad = pg_grid_args(origin, cell, dims, g);
-  UCSA_CHECK_ARG(bad != 1, 3);
-  UCSA_CHECK_ARG(bad != 2, 4);
-  UCSA_CHECK_ARG(bad != 3, 5);
-  UCSA_CHECK_ARG(nq <= 0x7FFFFFFFu, 8);
-  const float limit2 = max_dist * max_dist;
-  UCSA_CHECK_ARG(max_dist > 0.0f && pg_host_finite(max_dist) && pg_host_finite(limit2), 9);
-  if (nq == 0) return 0;
-  UCSA_CHECK_ARG(queries, 6);
-  UCSA_CHECK_ARG(face, 10);
-  UCSA_CHECK_ARG(dist2, 11);
-  UCSA_CHECK_ARG(bary, 12);
-  UCSA_CHECK_ARG(n_pairs == 0 || records, 0);
-  UCSA_CHECK_ARG(n_pairs == 0 || offsets, 1);
-  UCSA_CHECK_ARG(n_pairs == 0 || ((uintptr_t)records & 15u) == 0, 0);
+  float limit2;
+  const void* outs[] = {face, dist2, bary};
+  const int32_t st = pg_search_args(records, offsets, n_pairs, origin, cell, dims, queries, nq,
+                                    max_dist, outs, 3, g, limit2);
+  if (st != 0 || nq == 0) return st;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(ucsa_div_up(nq, PG_THREADS));
   UCSA_CLEAR_ERR();

@@ -2379,6 +2379,61 @@ def _points3(t, name):
     return _f32(t, name)
 
 
+def _finite_box(pts, ok):
+    """the bounding box of the rows of ``pts`` [N,3] that ``ok`` marks (the finite
+    ones) -> (lo, hi), three Python floats each; zeros when there is none"""
+    if pts.shape[0] and bool(ok.any()):
+        good = pts[ok]
+        return good.min(0).values.tolist(), good.max(0).values.tolist()
+    return [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+
+
+def _cell_sort(keys, ncells: int):
+    """int32 cell ``keys`` -> (``order`` int64: by key, ties by position;
+    ``offsets`` int32 [ncells+1]: where each cell starts in that order)"""
+    order = torch.sort(keys, stable=True).indices
+    offsets = torch.searchsorted(keys[order].contiguous(),
+                                 torch.arange(ncells + 1, dtype=torch.int32, device=keys.device)
+                                 ).to(torch.int32)
+    return order, offsets
+
+
+def _search_args(grid, maker: str, payload: str, count: str, cols: int, queries, max_dist,
+                 sort_queries: bool):
+    """What ``nearest_point`` and ``nearest_triangle`` do before their library
+    call: the queries, the grid dict of ops.``maker`` (its ``payload`` float32
+    [grid[``count``], ``cols``]) and ``max_dist`` checked, and the queries' cell
+    order -> (q, payload, offsets, n, origin, cell, dims, q_order, nq, max_dist)
+    as the library takes them."""
+    q = _points3(queries, "queries")
+    try:
+        pay, offsets = grid[payload], grid["offsets"]
+        origin, cell, dims, n = grid["origin"], float(grid["cell"]), grid["dims"], int(grid[count])
+    except (TypeError, KeyError):
+        raise _lib.UcsaError(f"grid must be the dict of ops.{maker}")
+    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if not (torch.is_tensor(pay) and pay.is_cuda and pay.dtype == torch.float32
+            and pay.is_contiguous() and tuple(pay.shape) == (n, cols) and torch.is_tensor(offsets)
+            and offsets.dtype == torch.int32 and offsets.is_contiguous()
+            and offsets.device == pay.device and offsets.numel() == ncells + 1):
+        raise _lib.UcsaError(f"grid: {payload} must be float32 [{count},{cols}] and offsets int32 "
+                             "[cells+1], contiguous, on one GPU")
+    if pay.device != q.device:
+        raise _lib.UcsaError(f"the grid is on {pay.device}, the queries on {q.device}")
+    max_dist = float(max_dist)
+    if not (max_dist > 0 and math.isfinite(max_dist)):
+        raise _lib.UcsaError(f"max_dist must be positive and finite, got {max_dist!r}")
+    nq = int(q.shape[0])
+    org, dm = fvec(origin), (C.c_uint32 * 3)(*[int(d) for d in dims])
+    q_order = None
+    if sort_queries and nq and n:
+        keys = torch.empty(nq, dtype=torch.int32, device=q.device)
+        check(lib().ucsa_point_cell_keys(_ptr(q), nq, org, cell, dm, 0, _ptr(keys), _stream()),
+              "ucsa_point_cell_keys")
+        q_order = torch.sort(keys, stable=True).indices.to(torch.int32)
+    return q, pay, offsets, n, org, cell, dm, q_order, nq, max_dist
+
+
 def _grid_shape(lo, hi, n, cell):
     """origin, cell and dims from the finite points' box: host arithmetic in
     float64 on float32 corners.  The choice changes time only, never a result."""
@@ -2415,23 +2470,15 @@ def point_grid(points, cell=None):
     pts = _points3(points, "points")
     n = int(pts.shape[0])
     dev = pts.device
-    ok = torch.isfinite(pts).all(1)
-    if n and bool(ok.any()):
-        good = pts[ok]
-        lo, hi = good.min(0).values.tolist(), good.max(0).values.tolist()
-    else:
-        lo = hi = [0.0, 0.0, 0.0]
+    lo, hi = _finite_box(pts, torch.isfinite(pts).all(1))
     cell, dims = _grid_shape(lo, hi, n, cell)
-    ncells = dims[0] * dims[1] * dims[2]
     keys = torch.empty(n, dtype=torch.int32, device=dev)
     check(lib().ucsa_point_cell_keys(_ptr(pts), n, fvec(lo), cell, (C.c_uint32 * 3)(*dims), 1,
                                      _ptr(keys), _stream()), "ucsa_point_cell_keys")
-    order = torch.sort(keys, stable=True).indices.to(torch.int32)
-    offsets = torch.searchsorted(keys[order.long()].contiguous(),
-                                 torch.arange(ncells + 1, dtype=torch.int32, device=dev)
-                                 ).to(torch.int32)
+    order64, offsets = _cell_sort(keys, dims[0] * dims[1] * dims[2])
+    order = order64.to(torch.int32)
     packed = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    packed[:, :3] = pts[order.long()].view(torch.int32)
+    packed[:, :3] = pts[order64].view(torch.int32)
     packed[:, 3] = order
     return {"origin": tuple(float(v) for v in lo), "cell": cell, "dims": dims,
             "offsets": offsets, "order": order, "sorted_points": packed.view(torch.float32),
@@ -2451,32 +2498,8 @@ def nearest_point(grid, queries, max_dist: float, sort_queries: bool = True):
     hands the queries to the kernel in cell order, so that a wave's lanes walk
     the same cells; it changes time only.  Contract of ucsa_nearest_point
     (include/ucsa_hip.h)."""
-    q = _points3(queries, "queries")
-    try:
-        sp, offsets = grid["sorted_points"], grid["offsets"]
-        origin, cell, dims, n = grid["origin"], float(grid["cell"]), grid["dims"], int(grid["n"])
-    except (TypeError, KeyError):
-        raise _lib.UcsaError("grid must be the dict of ops.point_grid")
-    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
-    if not (torch.is_tensor(sp) and sp.is_cuda and sp.dtype == torch.float32 and sp.is_contiguous()
-            and tuple(sp.shape) == (n, 4) and torch.is_tensor(offsets)
-            and offsets.dtype == torch.int32 and offsets.is_contiguous()
-            and offsets.device == sp.device and offsets.numel() == ncells + 1):
-        raise _lib.UcsaError("grid: sorted_points must be float32 [n,4] and offsets int32 "
-                             "[cells+1], contiguous, on one GPU")
-    if sp.device != q.device:
-        raise _lib.UcsaError(f"the grid is on {sp.device}, the queries on {q.device}")
-    max_dist = float(max_dist)
-    if not (max_dist > 0 and math.isfinite(max_dist)):
-        raise _lib.UcsaError(f"max_dist must be positive and finite, got {max_dist!r}")
-    nq = int(q.shape[0])
-    org, dm = fvec(origin), (C.c_uint32 * 3)(*[int(d) for d in dims])
-    q_order = None
-    if sort_queries and nq and n:
-        keys = torch.empty(nq, dtype=torch.int32, device=q.device)
-        check(lib().ucsa_point_cell_keys(_ptr(q), nq, org, cell, dm, 0, _ptr(keys), _stream()),
-              "ucsa_point_cell_keys")
-        q_order = torch.sort(keys, stable=True).indices.to(torch.int32)
+    q, sp, offsets, n, org, cell, dm, q_order, nq, max_dist = _search_args(
+        grid, "point_grid", "sorted_points", "n", 4, queries, max_dist, sort_queries)
     index = torch.empty(nq, dtype=torch.int32, device=q.device)
     dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
     check(lib().ucsa_nearest_point(_ptr(sp) if n else None, _ptr(offsets) if n else None, n, org,
@@ -2518,11 +2541,7 @@ def triangle_grid(verts, faces, cell=None):
         raise _lib.UcsaError(f"cell must be positive and finite, got {cell!r}")
     dev = v.device
     fin = torch.isfinite(v).all(1)
-    if nv and bool(fin.any()):
-        good = v[fin]
-        lo, hi = good.min(0).values.tolist(), good.max(0).values.tolist()
-    else:
-        lo = hi = [0.0, 0.0, 0.0]
+    lo, hi = _finite_box(v, fin)
     ext = [float(b) - float(a) for a, b in zip(lo, hi)]
     big = max(ext)
     if cell is None:
@@ -2554,17 +2573,13 @@ def triangle_grid(verts, faces, cell=None):
         cell = f32(cell * 1.25)
     if n_pairs > TRIANGLE_GRID_MAX_PAIRS:
         raise _lib.UcsaError(f"{n_pairs} (cell, face) pairs: at most 2^31-1")
-    ncells = dims[0] * dims[1] * dims[2]
     first = (torch.cumsum(counts, 0, dtype=torch.int64) - counts).to(torch.int32)
     keys = torch.empty(n_pairs, dtype=torch.int32, device=dev)
     pair_face = torch.empty(n_pairs, dtype=torch.int32, device=dev)
     check(lib().ucsa_triangle_cell_pairs(_ptr(v), nv, _ptr(f), nf, org, cell, dm, _ptr(first),
                                          n_pairs, _ptr(keys), _ptr(pair_face), _stream()),
           "ucsa_triangle_cell_pairs")
-    order = torch.sort(keys, stable=True).indices
-    offsets = torch.searchsorted(keys[order].contiguous(),
-                                 torch.arange(ncells + 1, dtype=torch.int32, device=dev)
-                                 ).to(torch.int32)
+    order, offsets = _cell_sort(keys, dims[0] * dims[1] * dims[2])
     sf = pair_face[order]
     rec = torch.zeros((n_pairs, 12), dtype=torch.int32, device=dev)
     if n_pairs:
@@ -2589,33 +2604,8 @@ def nearest_triangle(grid, queries, max_dist: float, sort_queries: bool = True):
     costs the same: a query with nothing near walks every cell within it.
     ``sort_queries`` hands the queries to the kernel in cell order; it changes
     time only.  Contract of ucsa_nearest_triangle (include/ucsa_hip.h)."""
-    q = _points3(queries, "queries")
-    try:
-        rec, offsets = grid["records"], grid["offsets"]
-        origin, cell, dims = grid["origin"], float(grid["cell"]), grid["dims"]
-        n = int(grid["n_pairs"])
-    except (TypeError, KeyError):
-        raise _lib.UcsaError("grid must be the dict of ops.triangle_grid")
-    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
-    if not (torch.is_tensor(rec) and rec.is_cuda and rec.dtype == torch.float32
-            and rec.is_contiguous() and tuple(rec.shape) == (n, 12) and torch.is_tensor(offsets)
-            and offsets.dtype == torch.int32 and offsets.is_contiguous()
-            and offsets.device == rec.device and offsets.numel() == ncells + 1):
-        raise _lib.UcsaError("grid: records must be float32 [n_pairs,12] and offsets int32 "
-                             "[cells+1], contiguous, on one GPU")
-    if rec.device != q.device:
-        raise _lib.UcsaError(f"the grid is on {rec.device}, the queries on {q.device}")
-    max_dist = float(max_dist)
-    if not (max_dist > 0 and math.isfinite(max_dist)):
-        raise _lib.UcsaError(f"max_dist must be positive and finite, got {max_dist!r}")
-    nq = int(q.shape[0])
-    org, dm = fvec(origin), (C.c_uint32 * 3)(*[int(d) for d in dims])
-    q_order = None
-    if sort_queries and nq and n:
-        keys = torch.empty(nq, dtype=torch.int32, device=q.device)
-        check(lib().ucsa_point_cell_keys(_ptr(q), nq, org, cell, dm, 0, _ptr(keys), _stream()),
-              "ucsa_point_cell_keys")
-        q_order = torch.sort(keys, stable=True).indices.to(torch.int32)
+    q, rec, offsets, n, org, cell, dm, q_order, nq, max_dist = _search_args(
+        grid, "triangle_grid", "records", "n_pairs", 12, queries, max_dist, sort_queries)
     face = torch.empty(nq, dtype=torch.int32, device=q.device)
     dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
     bary = torch.empty((nq, 3), dtype=torch.float32, device=q.device)
@@ -2703,12 +2693,7 @@ def simplify_mesh(verts, faces, cell, normals=None, rgb=None, labels=None,
         raise _lib.UcsaError(f"cell must be a number, got {cell!r}")
     if not (cell > 0 and math.isfinite(cell)):
         raise _lib.UcsaError(f"cell must be positive and finite in float32, got {cell!r}")
-    ok = torch.isfinite(pts).all(1)
-    if n and bool(ok.any()):
-        good = pts[ok]
-        lo, hi = good.min(0).values.tolist(), good.max(0).values.tolist()
-    else:
-        lo = hi = [0.0, 0.0, 0.0]
+    lo, hi = _finite_box(pts, torch.isfinite(pts).all(1))
     if origin is not None:
         try:
             lo = [f32(v) for v in origin]
