@@ -90,6 +90,9 @@ def test_render_gradients_match_oracle_autograd(N, T, t, perturb, inside):
     # sample's contribution to one hidden neuron flips (observed: one row of
     # one matrix off by 4e-3 of the largest entry, everything else 1e-5).
     # Hence a tight bound in the L2 sense and a looser bound entrywise.
+    # (The per-sample outputs of the stage -- G, d_h rows, dW -- are held to
+    # derived per-element bounds, with the gates pinned in the inputs, in
+    # tests/test_gpu_shade_reference.py.)
     for got, ref_g in ((net.color_net.params.grad, fld.color_params.grad),
                        (net.semantics_net.params.grad, fld.sem_params.grad),
                        (net.sigma_net.params.grad, fld.sigma_params.grad),
@@ -538,7 +541,9 @@ def test_sigma_mlp_backward_bf16x2_matches_autograd(ops):
     recompute's 1e-5 of zero, within 2e-5 of the maximum as well.  At 70 001
     samples x 64 units a handful do: their ReLU gate is decided by the 2^-16
     recompute, the gradient of THAT sample takes the other (equally valid)
-    subgradient, and the maximum error is O(0.1) on ~1e-5 of the samples."""
+    subgradient, and the maximum error is O(0.1) on ~1e-5 of the samples.
+    (tests/test_gpu_shade_reference.py::test_sigma_backward compares per
+    element on inputs without such samples.)"""
     from ucsa_neural_rendering_amd import _lib
     fld = lively_oracle_field()
     g = torch.Generator().manual_seed(1)

@@ -775,14 +775,12 @@ static void shade_bwd_geometry(uint32_t N, uint32_t& rpw, uint32_t& blocks,
 }
 
 // fp32 kernel as a per-net pair (NET = 1 then 2, two waves per SIMD each):
-// UCSA_SHADE_BWD_SPLIT=0 keeps the single kernel (one wave per SIMD).
+// UCSA_SHADE_BWD_SPLIT=0 keeps the single kernel (one wave per SIMD).  Read
+// from the env table on every call (no cache of its own), so the switch
+// follows ucsa_env_reload() like the table's other switches.
 static bool shade_bwd_split() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = ucsa_getenv("UCSA_SHADE_BWD_SPLIT");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  const char* e = ucsa_getenv("UCSA_SHADE_BWD_SPLIT");
+  return !(e && e[0] == '0');
 }
 
 // number of per-wave partial slots the caller must provide
