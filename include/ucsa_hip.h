@@ -1439,6 +1439,63 @@ int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx,
                             uint32_t W, float trunc, float max_weight, float depth_min,
                             float depth_max, void* stream);
 
+/* ---- occupancy prior: a TSDF volume carves the marcher's cascade grid (not in
+ * the reference; its parent code base had mark_untrained_grid) ---------------
+ * ucsa_tsdf_occupancy: the volume (tsdf, weight [nx,ny,nz] fp32, origin3 /
+ * spacing3 HOST float[3]: the state and lattice of ucsa_tsdf_integrate) ->
+ * mask uint8 [cascade,H,H,H], 1 = the cell may hold matter (keep), 0 = the
+ * sensor saw it to be empty, in density_grid's linear layout
+ * ((cas*H + ix)*H + iy)*H + iz.  SemanticNeRFRenderer.set_occupancy_prior
+ * writes -1 into the 0 cells; ucsa_density_grid_update never touches a negative
+ * cell and the marcher's grid > thresh never enters one.
+ * Contract (fp32, every operation as written and rounded on its own, no
+ * contraction, correctly rounded division; tests/occupancy_numpy.py restates it
+ * and the masks match byte for byte).  Per axis a, with n = the dim:
+ *   voxel i: centre p(i) = origin_a + (float)i * spacing_a (the lattice point of
+ *     ucsa_tsdf_integrate), box [p(i) - h, p(i) + h] with h = 0.5f * spacing_a;
+ *   cell j of cascade c: b = min(2^c, bound),
+ *     lo = b * ((float)(2j) / (float)H - 1) - dilate,
+ *     hi = b * ((float)(2j + 2) / (float)H - 1) + dilate
+ *     (the cells of ucsa_density_grid_points and of the marcher's lookup, grown
+ *     by dilate on every side);
+ *   voxel i meets cell j iff p(i) + h >= lo && p(i) - h <= hi: closed
+ *     intervals, the conservative choice.
+ * A voxel overlaps a cell iff it meets it on all three axes.  p(i) is
+ * non-decreasing in i (spacing > 0; every rounding is monotone), so per axis the
+ * overlapping voxels are one index interval and the overlap set is a box; an
+ * implementation may find the interval any way it likes but its ends are
+ * settled by the predicate above, never by a floor of its own.
+ * A voxel is FREE iff weight >= min_weight && tsdf >= free_tsdf (NaN in either:
+ * not free).  With free_tsdf = 1 that is "every view that saw it saw it more
+ * than trunc in front of its surface": integrate gives such a voxel exactly 1.
+ * With unknown_keeps = 0 a voxel with !(weight >= min_weight) is free as well,
+ * and so is all space outside the volume.
+ * A cell is KEPT (1) iff
+ *   some overlapping voxel is not free, or
+ *   unknown_keeps != 0 and on some axis lo < p(0) - h or hi > p(n-1) + h (the
+ *     dilated cell reaches outside the volume).
+ * A pure OR over a box: no order, no atomics, two runs give the same bytes.
+ * Two launches whatever the data: the "not free" bits are packed along z into
+ * `workspace` (ucsa_tsdf_occupancy_workspace_bytes = 8*nx*ny*ceil(nz/64),
+ * checked against workspace_bytes), then one lane per cell walks its box over
+ * the packed words (csrc/occupancy_prior.hip states the work per lane).  No
+ * host read-back.
+ * Limits, ERR_ARG - argument index: tsdf, weight, origin3, spacing3, mask,
+ * workspace not NULL; dims >= 1 each (nx*ny*nz <= 2^31-1: argument 2); origin
+ * finite; spacing > 0 and finite; min_weight, free_tsdf not NaN; unknown_keeps
+ * 0 or 1; bound > 0 and finite; 1 <= cascade <= 31; 2 <= H <= 1024; dilate >= 0
+ * and finite; mask_capacity (bytes) >= cascade*H^3.  An argument error comes
+ * before any launch; nothing outside mask[0 .. cascade*H^3) and the workspace is
+ * written. */
+uint64_t ucsa_tsdf_occupancy_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int32_t ucsa_tsdf_occupancy(const float* tsdf, const float* weight, uint32_t nx,
+                            uint32_t ny, uint32_t nz, const float* origin3,
+                            const float* spacing3, float min_weight, float free_tsdf,
+                            uint32_t unknown_keeps, float bound, uint32_t cascade,
+                            uint32_t H, float dilate, uint8_t* mask,
+                            uint64_t mask_capacity, void* workspace,
+                            uint64_t workspace_bytes, void* stream);
+
 /* ---- voxel map: per-voxel class votes and a ray-caster over the TSDF volume
  * (not in the reference) ----------------------------------------------------
  * The voxel route of the mapping baseline (utils/voxel_map.py,

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""Make the marcher's occupancy prior from a scene's posed depth frames: TSDF
+fusion on the GPU, then ``ops.tsdf_occupancy`` (``utils/occupancy_prior.py``).
+
+    python scripts/occupancy_prior.py --scene_root <root>/<scene> --out prior.npz \\
+        [--bound 4] [--voxel METRES] [--trunc METRES] [--dilate METRES] \\
+        [--unknown {keep,empty}] [--every N]
+
+Reads the frames of transforms_train.json (every ``--every``-th) as
+``scripts/fuse_tsdf_mesh.py`` does: the poses in the field's (NGP) frame and
+``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement).  ``--voxel``,
+``--trunc`` (default: 4 voxels) and ``--dilate`` (default: one voxel) are
+metres; ``--bound`` is the renderer's.  ``--unknown keep`` (default) carves only
+the space the sensor saw to be empty; ``empty`` also carves what no view
+observed and everything outside the volume.  Writes the mask and its parameters
+(``utils.occupancy_prior.save_prior``); ``nerf: {cuda_ray: true,
+occupancy_prior: prior.npz}`` in an experiment YAML makes the training loop load
+it.  Prints one ``occupancy_prior:`` line of statistics."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ucsa_neural_rendering_amd.utils.mesh_render import read_frames  # noqa: E402
+from ucsa_neural_rendering_amd.utils.occupancy_prior import (  # noqa: E402
+    prior_from_depth_views, save_prior)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--scene_root", required=True, help="<root>/<scene>")
+    p.add_argument("--out", required=True, help="the prior to write (.npz)")
+    p.add_argument("--bound", type=float, default=4.0, help="the renderer's bound")
+    p.add_argument("--voxel", type=float, default=0.05, help="metres")
+    p.add_argument("--trunc", type=float, default=None, help="metres (default: 4 voxels)")
+    p.add_argument("--dilate", type=float, default=None, help="metres (default: one voxel)")
+    p.add_argument("--unknown", choices=("keep", "empty"), default="keep")
+    p.add_argument("--every", type=int, default=1, help="use every N-th frame")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    from PIL import Image
+    a = parse_args(argv)
+    if a.every < 1:
+        raise SystemExit("--every must be >= 1")
+    fr = read_frames(a.scene_root)
+    uom = fr["one_m_to_scene_uom"]
+    keep = list(range(0, len(fr["stems"]), a.every))
+    stems = [fr["stems"][i] for i in keep]
+    poses = fr["poses"][keep]
+
+    def depth(i):
+        mm = np.asarray(Image.open(os.path.join(a.scene_root, "depth", stems[i] + ".png")))
+        return (mm.astype(np.float32) / np.float32(1000.0)) * np.float32(uom)
+
+    voxel = a.voxel * uom
+    dilate = None if a.dilate is None else a.dilate * uom
+    mask, st = prior_from_depth_views(poses, fr["intrinsics"], fr["H"], fr["W"], depth, a.bound,
+                                      voxel=voxel,
+                                      trunc=None if a.trunc is None else a.trunc * uom,
+                                      dilate=dilate, unknown=a.unknown)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    save_prior(a.out, mask, a.bound, voxel=np.float32(voxel), trunc=np.float32(st["trunc"]),
+               dilate=np.float32(voxel if dilate is None else dilate), unknown=a.unknown,
+               origin=np.asarray(st["origin"], np.float32), dims=np.asarray(st["dims"], np.int64))
+    rec = {"out": a.out, "frames": len(stems), "bound": a.bound, "unknown": a.unknown,
+           "cascade": int(mask.shape[0]), "H": int(mask.shape[1]),
+           "kept": [round(v, 4) for v in st["kept"]], "dims": list(st["dims"]),
+           "observed": round(st["observed"], 4), "band": round(st["band"], 4),
+           "free": round(st["free"], 4), "integrate_ms": round(st["integrate_ms"], 3),
+           "occupancy_ms": round(st["occupancy_ms"], 3)}
+    print("occupancy_prior: " + json.dumps(rec))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

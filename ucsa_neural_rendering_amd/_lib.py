@@ -320,6 +320,11 @@ SIGNATURES = {
     "ucsa_tsdf_integrate": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, C.POINTER(_f),
                                         C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f,
                                         _u32, _u32, _f, _f, _f, _f, _p]),
+    # ---- occupancy prior (a TSDF volume carves the marcher's cascade grid) ----
+    "ucsa_tsdf_occupancy_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32]),
+    "ucsa_tsdf_occupancy": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                        C.POINTER(_f), _f, _f, _u32, _f, _u32, _u32, _f,
+                                        _p, C.c_uint64, _p, C.c_uint64, _p]),
     # ---- voxel map (per-voxel class votes, ray-caster over the TSDF volume) ----
     "ucsa_tsdf_vote": (C.c_int32, [_p, C.c_uint64, _u32, _u32, _u32, _u32, C.POINTER(_f),
                                    C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f, _u32,

@@ -63,6 +63,21 @@ class JointTrainLightningNet(nn.Module):
             density_scale=1, num_semantic_classes=self.num_classes,
             seed=exp.get("nerf_seed"))
         self.nerf_model.march_training = self.cuda_ray
+        # `nerf: {cuda_ray: true, occupancy_prior: <prior.npz>}`: the mask of
+        # scripts/occupancy_prior.py (measured free space) carves the density
+        # grid before the first NeRF step; the marcher never samples those
+        # cells.  Without the key nothing changes.
+        self.occupancy_prior_path = nerf_cfg.get("occupancy_prior")
+        if self.occupancy_prior_path:
+            if not self.cuda_ray:
+                raise ValueError("nerf.occupancy_prior needs nerf.cuda_ray: true")
+            from ..utils.occupancy_prior import load_prior
+            mask, params = load_prior(self.occupancy_prior_path)
+            if float(params["bound"]) != float(self.nerf_model.bound):
+                raise ValueError(f"{self.occupancy_prior_path} was made for bound "
+                                 f"{float(params['bound'])}, the field has "
+                                 f"{float(self.nerf_model.bound)}")
+            self.nerf_model.set_occupancy_prior(mask)
         # `nerf: {precision: ...}`: arithmetic of the three MLPs in the no-grad
         # renders.  "f16x2" (default since round 4): fp32-grade on the f16 MFMA
         # pipe (two f16 terms per operand, the second scaled by 2^11, three

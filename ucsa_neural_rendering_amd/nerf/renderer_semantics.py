@@ -134,11 +134,56 @@ class SemanticNeRFRenderer(nn.Module):
         if not self.cuda_ray:
             return
         self.density_grid.zero_()
+        if getattr(self, "occupancy_prior", None) is not None:
+            self.density_grid[self.occupancy_prior == 0] = -1.0
         self.mean_density = 0
         self.iter_density = 0
         self.step_counter.zero_()
         self.mean_count = 0
         self.local_step = 0
+
+    # -- occupancy prior: measured free space, carved for good ----------------
+    # ucsa_density_grid_update leaves a negative cell alone and counts it as 0 in
+    # the mean, and the marcher's grid > thresh never enters one: a cell set to
+    # -1 here stays empty whatever the field says there.  ops.tsdf_occupancy /
+    # utils/occupancy_prior.py make the mask from the scene's depth frames.
+    @torch.no_grad()
+    def set_occupancy_prior(self, mask):
+        """``mask`` [cascade,H,H,H] (uint8 / bool, 1 = may hold matter) in
+        density_grid's layout: every 0 cell becomes -1 in density_grid, for
+        good (update_extra_state never touches it, the marcher never samples
+        it); a 1 cell that was negative (an earlier prior) goes back to 0 and is
+        learned from the field as usual.  The mask is kept as a non-persistent
+        buffer (it follows ``.to()``, the state_dict keys do not change) and
+        reset_extra_state re-applies it.  mean_density stays the mean over ALL
+        cells with the carved ones counted as 0, as in the parent code base:
+        under a tight prior it is smaller, so the marcher's threshold
+        min(0.01, mean_density) can only become more permissive."""
+        if not self.cuda_ray:
+            raise ValueError("set_occupancy_prior needs cuda_ray=True: only the marcher "
+                             "reads density_grid")
+        mask = torch.as_tensor(mask)
+        if tuple(mask.shape) != tuple(self.density_grid.shape):
+            raise ValueError(f"occupancy prior must be {tuple(self.density_grid.shape)} like "
+                             f"density_grid, got {tuple(mask.shape)}")
+        mask = (mask != 0).to(device=self.density_grid.device, dtype=torch.uint8).contiguous()
+        if "occupancy_prior" in self._buffers:
+            self.occupancy_prior = mask
+        else:
+            self.register_buffer("occupancy_prior", mask, persistent=False)
+        keep = mask != 0
+        self.density_grid[~keep] = -1.0
+        self.density_grid[keep & (self.density_grid < 0)] = 0.0
+
+    @torch.no_grad()
+    def clear_occupancy_prior(self):
+        """Drop the prior: the carved cells go back to 0 and the next refreshes
+        learn them from the field."""
+        if "occupancy_prior" in self._buffers:
+            del self._buffers["occupancy_prior"]
+            self._non_persistent_buffers_set.discard("occupancy_prior")
+        if self.cuda_ray:
+            self.density_grid[self.density_grid < 0] = 0.0
 
     # -- occupancy-grid marching (SURVEY 8f rank 1) ---------------------------
     # The reference keeps the state above and the raymarching functions but no

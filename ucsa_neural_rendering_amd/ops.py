@@ -1913,6 +1913,56 @@ def integrate_tsdf(volume, depth, poses, intrinsics, trunc: float, color=None,
     return volume
 
 
+def tsdf_occupancy(volume, bound, cascade=None, H: int = 128, dilate=None,
+                   min_weight: float = 1.0, free_tsdf: float = 1.0, unknown: str = "keep"):
+    """Occupancy prior of a ``tsdf_volume`` for the marcher's cascade grid:
+    uint8 [cascade,H,H,H] on the volume's device, 1 = the cell may hold matter,
+    0 = every voxel its box meets was seen to be free space
+    (``weight >= min_weight and tsdf >= free_tsdf``).  ``cascade`` None is the
+    renderer's ``1 + ceil(log2(bound))``; ``dilate`` (scene units, grows every
+    cell's box on all sides) None is the largest of the three spacings: one
+    voxel, because the voxels that no view observed next to a surface hold no
+    evidence either way; ``unknown`` "keep" keeps every cell that touches an
+    unobserved voxel or reaches outside the volume, "empty" carves them.
+    ``SemanticNeRFRenderer.set_occupancy_prior`` takes the result.  Contract of
+    ucsa_tsdf_occupancy (include/ucsa_hip.h): a pure OR over a box of voxels,
+    the same bytes every run."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    if unknown not in ("keep", "empty"):
+        raise _lib.UcsaError(f"tsdf_occupancy: unknown must be 'keep' or 'empty', got {unknown!r}")
+    bound = float(bound)
+    if not (bound > 0 and math.isfinite(bound)):
+        raise _lib.UcsaError(f"tsdf_occupancy: bound must be > 0 and finite, got {bound}")
+    if cascade is None:
+        cascade = 1 + math.ceil(math.log2(bound))
+    cascade, H = int(cascade), int(H)
+    if not 1 <= cascade <= 31:
+        raise _lib.UcsaError(f"tsdf_occupancy: cascade must be in 1..31, got {cascade}")
+    if not 2 <= H <= 1024:
+        raise _lib.UcsaError(f"tsdf_occupancy: H must be in 2..1024, got {H}")
+    spacing = [float(v) for v in volume["spacing"]]
+    origin = [float(v) for v in volume["origin"]]
+    if len(origin) != 3 or len(spacing) != 3:
+        raise _lib.UcsaError("tsdf_occupancy: origin and spacing have 3 entries each")
+    if not all(v > 0 and math.isfinite(v) for v in spacing):
+        raise _lib.UcsaError(f"tsdf_occupancy: spacing must be > 0 and finite, got {spacing}")
+    if not all(math.isfinite(v) for v in origin):
+        raise _lib.UcsaError(f"tsdf_occupancy: origin must be finite, got {origin}")
+    dilate = max(spacing) if dilate is None else float(dilate)
+    if not (dilate >= 0 and math.isfinite(dilate)):
+        raise _lib.UcsaError(f"tsdf_occupancy: dilate must be >= 0 and finite, got {dilate}")
+    if math.isnan(float(min_weight)) or math.isnan(float(free_tsdf)):
+        raise _lib.UcsaError("tsdf_occupancy: min_weight and free_tsdf must not be NaN")
+    mask = torch.empty(cascade, H, H, H, dtype=torch.uint8, device=dev)
+    ws_bytes = int(lib().ucsa_tsdf_occupancy_workspace_bytes(nx, ny, nz))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    check(lib().ucsa_tsdf_occupancy(
+        _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
+        float(min_weight), float(free_tsdf), 1 if unknown == "keep" else 0, bound, cascade, H,
+        dilate, _ptr(mask), mask.numel(), _ptr(ws), ws_bytes, _stream()), "ucsa_tsdf_occupancy")
+    return mask
+
+
 # ---------------------------------------------------------------------------
 # voxel map (per-voxel class votes, ray-caster over the TSDF volume)
 # ---------------------------------------------------------------------------

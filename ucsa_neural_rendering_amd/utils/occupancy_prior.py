@@ -1,0 +1,109 @@
+"""An occupancy prior for the marcher from the scene's own depth frames: the
+mapping chain already knows which space the sensor saw to be empty, in the
+NeRF's frame, so the marcher need not learn it.
+
+    depth/ + poses --ops.integrate_tsdf--> volume --ops.tsdf_occupancy--> mask
+        --SemanticNeRFRenderer.set_occupancy_prior--> density_grid = -1 there
+
+A fresh field has sigma ~ 1 everywhere and the marcher walks the air densely
+until the grid has forgotten it (``refresh_due``); with the prior the measured
+free space is skipped from step 0 and stays skipped.  The volume is picked the
+way ``tsdf_fusion.fuse_depth_views`` picks it.  Out of scope: carving straight
+from depth views without a volume, camera-coverage marking without depth,
+sparse volumes."""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+import torch
+
+from .. import ops
+from .mesh_fusion import _batch
+from .tsdf_fusion import depth_points_aabb
+
+
+def volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel=0.05, trunc=None,
+                            aabb=None, batch=16, max_weight=65504.0, depth_min=1e-6,
+                            depth_max=3.0e38, device="cuda"):
+    """The TSDF volume (``ops.tsdf_volume``, no colour) of the views, chosen and
+    integrated as ``fuse_depth_views`` does -> (volume, trunc, integrate_ms)."""
+    dev = torch.device(device)
+    voxel = float(voxel)
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    if not (voxel > 0 and trunc > 0):
+        raise ValueError("voxel and trunc must be > 0")
+    poses = torch.as_tensor(np.asarray(poses, np.float32)).reshape(-1, 4, 4)
+    N = int(poses.shape[0])
+    if N == 0:
+        raise ValueError("no views")
+    if aabb is None:
+        box = depth_points_aabb(poses, intrinsics, depth_maps, H, W, batch, depth_min,
+                                depth_max, dev)
+        box = box + np.array([[-trunc], [trunc]], np.float32)
+    else:
+        box = np.asarray(aabb, np.float32).reshape(2, 3)
+    dims = [max(2, int(np.ceil(float(box[1, a] - box[0, a]) / voxel - 1e-6)) + 1)
+            for a in range(3)]
+    vol = ops.tsdf_volume(dims, box[0].tolist(), voxel, device=dev)
+    t_i = 0.0
+    for a in range(0, N, batch):
+        b = min(a + batch, N)
+        z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
+        P = poses[a:b].to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ops.integrate_tsdf(vol, z, P, intrinsics, trunc, max_weight=max_weight,
+                           depth_min=depth_min, depth_max=depth_max)
+        torch.cuda.synchronize()
+        t_i += time.perf_counter() - t0
+    return vol, trunc, 1e3 * t_i
+
+
+def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.05, trunc=None,
+                           aabb=None, batch=16, **occupancy_kw):
+    """``poses`` [N,4,4] camera-to-world (NGP frame), ``depth_maps`` a sequence
+    or callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), ``bound``
+    the renderer's; ``voxel`` / ``trunc`` (default 4 voxels) / ``aabb`` (None =
+    the box of the valid depth points padded by ``trunc``) as for
+    ``fuse_depth_views``; ``occupancy_kw`` goes to ``ops.tsdf_occupancy``
+    (cascade, H, dilate, min_weight, free_tsdf, unknown).  -> (mask uint8
+    [cascade,H,H,H] on the device, stats): ``kept`` the kept share per cascade,
+    ``observed`` / ``band`` / ``free`` the shares of the volume's voxels with
+    weight >= min_weight / observed and not free / observed and free, ``dims``,
+    ``origin``, ``spacing``, ``trunc`` and the wall time ``integrate_ms`` /
+    ``occupancy_ms`` (device-synchronised host clock)."""
+    vol, trunc, t_i = volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel, trunc,
+                                              aabb, batch)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mask = ops.tsdf_occupancy(vol, bound, **occupancy_kw)
+    torch.cuda.synchronize()
+    t_o = time.perf_counter() - t0
+    seen = vol["weight"] >= float(occupancy_kw.get("min_weight", 1.0))
+    free = seen & (vol["tsdf"] >= float(occupancy_kw.get("free_tsdf", 1.0)))
+    stats = {"kept": [float(v) for v in mask.float().mean((1, 2, 3)).tolist()],
+             "observed": float(seen.float().mean()), "band": float((seen & ~free).float().mean()),
+             "free": float(free.float().mean()), "dims": tuple(vol["tsdf"].shape),
+             "origin": vol["origin"], "spacing": vol["spacing"], "trunc": trunc,
+             "integrate_ms": t_i, "occupancy_ms": 1e3 * t_o}
+    return mask, stats
+
+
+def save_prior(path, mask, bound, **params):
+    """Write the mask (bit-packed: 128^3 x 3 cascades is 768 KiB) and its
+    parameters as an ``.npz`` that ``load_prior`` reads."""
+    m = np.ascontiguousarray(torch.as_tensor(mask).cpu().numpy() != 0)
+    extra = {k: np.asarray(v) for k, v in params.items() if v is not None}
+    np.savez_compressed(path, mask_bits=np.packbits(m.reshape(-1)),
+                        shape=np.asarray(m.shape, np.int64), bound=np.float32(bound), **extra)
+
+
+def load_prior(path):
+    """-> (mask uint8 [cascade,H,H,H] numpy, params dict) of ``save_prior``"""
+    with np.load(path) as z:
+        shape = tuple(int(v) for v in z["shape"])
+        n = int(np.prod(shape))
+        mask = np.unpackbits(z["mask_bits"])[:n].reshape(shape).astype(np.uint8)
+        params = {k: z[k] for k in z.files if k not in ("mask_bits", "shape")}
+    return mask, params
