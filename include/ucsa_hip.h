@@ -1496,6 +1496,114 @@ int32_t ucsa_tsdf_occupancy(const float* tsdf, const float* weight, uint32_t nx,
                             uint64_t mask_capacity, void* workspace,
                             uint64_t workspace_bytes, void* stream);
 
+/* ---- mesh voxelization: the cells a triangle mesh passes through (not in the
+ * reference) ------------------------------------------------------------------
+ * ucsa_mesh_voxelize_count / ucsa_mesh_voxelize_fill: verts [V,3] fp32, faces
+ * [F,3] int32 (device) -> mask uint8, 1 = some face meets the cell's box.  Two
+ * families of axis-aligned boxes (fp32, every operation as written and rounded
+ * on its own, no contraction, correctly rounded division, as for
+ * ucsa_tsdf_occupancy; tests/voxelize_numpy.py restates all of it and the masks
+ * match byte for byte):
+ *   UCSA_VOXELIZE_LATTICE  the voxels of a tsdf_volume: nx, ny, nz, origin3 /
+ *     spacing3 HOST float[3]; voxel i on axis a has
+ *       p = origin_a + (float)i * spacing_a, h = 0.5f * spacing_a,
+ *       lo = (p - h) - dilate, hi = (p + h) + dilate;
+ *     mask [nx,ny,nz], linear (ix*ny + iy)*nz + iz; cascade must be 1, bound is
+ *     ignored.
+ *   UCSA_VOXELIZE_CASCADE  the marcher's cells: nx = ny = nz = H; cell j of
+ *     cascade c has, with b = min(2^c, bound),
+ *       lo = b * ((float)(2j) / (float)H - 1) - dilate,
+ *       hi = b * ((float)(2j + 2) / (float)H - 1) + dilate
+ *     (ucsa_tsdf_occupancy's formulas); mask [cascade,H,H,H] in density_grid's
+ *     layout ((c*H + ix)*H + iy)*H + iz; origin3 / spacing3 are ignored.
+ * meets(face, box), csrc/tri_box.h: the separating-axis test of a triangle
+ * against a box on 13 axes, closed, with a rounding slack.  Corners p0, p1, p2
+ * (the rows faces[f][0..2] of verts), per face and call:
+ *   S = the largest of |p_j.a| (9 numbers) and Bmax, the family's largest
+ *     absolute box bound: cascade min(2^(cascade-1), bound) + dilate; lattice
+ *     the largest of |lo(0)|, |hi(n-1)| over the three axes;
+ *   slack = 2^-20 * S  (K * 2^-24 with K = 16; docs/DESIGN_NOTEBOOK.md, VX);
+ *   mn_a / mx_a = the smallest / largest of p0.a, p1.a, p2.a;
+ *   e_0 = p1 - p0, e_1 = p2 - p1, e_2 = p0 - p2 (per component);
+ *   n_a = e_0.b * e_1.c - e_0.c * e_1.b, where (a, b, c) runs over (x, y, z),
+ *     (y, z, x), (z, x, y) here and below.
+ * Per box [lo, hi]:
+ *   box axes (3): mn_a <= hi_a + slack && mx_a >= lo_a - slack;
+ *   c_a = 0.5f * (lo_a + hi_a), g_a = 0.5f * (hi_a - lo_a) + slack,
+ *   v_j.a = p_j.a - c_a;
+ *   unit_a x e_i (9): q_j = e_i.b * v_j.c - e_i.c * v_j.b  for j = 0, 1, 2,
+ *     r = g_b * |e_i.c| + g_c * |e_i.b|;
+ *     the axis separates iff min(q_0, q_1, q_2) > r or max(q_0, q_1, q_2) < -r;
+ *   the normal (1): d_j = (n_x * v_j.x + n_y * v_j.y) + n_z * v_j.z,
+ *     r = (|n_x| * g_x + |n_y| * g_y) + |n_z| * g_z;
+ *     separates iff min(d_0, d_1, d_2) > r or max(d_0, d_1, d_2) < -r.  In exact
+ *     arithmetic the three d_j are equal and this is |n . v_0| <= |n| . g; in
+ *     fp32 they are not, and for a thin triangle they differ by more than the
+ *     slack covers, so all three are asked: whatever n came out as, it is an
+ *     axis, and an axis on which the projections overlap cannot lose a pair.
+ *   meets iff the three box axes hold and none of the ten separates.
+ * A face with an index outside [0, V) or a corner that is not finite or larger
+ * in magnitude than 2^40 (beyond it the products could overflow) meets nothing;
+ * the kernels test every index before use and are memory-safe on any faces.  A
+ * face of zero area (a segment, a point) takes the same test: n = 0 makes the
+ * normal axis pass and the other twelve decide.
+ * The guarantee, in exact arithmetic on the same fp32 inputs: a face and a box
+ * that intersect meet (never a touching pair lost: proven for every face, K >=
+ * 14 suffices), and a face that meets a box intersects that box grown by
+ * 2 * slack on every side (proven for the twelve box and cross axes; on the
+ * normal axis the rounded n tilts the plane, to first order by at most
+ * 24 * 2^-24 * L^2 / w at the far end of a face of longest edge L and width w,
+ * which 2 * slack covers for faces that are small beside the scene and not
+ * slivers; no pair outside the grown box was found among thousands built to
+ * graze, thin and scene-sized faces included).
+ * slack does not depend on the cell and lo, hi are non-decreasing in the cell
+ * index, so the box-axis test is monotone: per axis the cells that pass are one
+ * index interval.  An implementation may find it any way it likes but its ends
+ * are settled by the predicate above, never by a floor of its own, and it may
+ * skip a cell only where it can prove the predicate false.
+ * Result: mask[cell] = 1 iff some face meets the cell's box, else 0: a pure OR,
+ * stored as the constant 1 by plain byte stores, so no atomics, any face order
+ * and two runs give the same bytes.  With accumulate = 1 the mask is not
+ * cleared first: met cells are set to 1 and every other byte is left alone, so
+ * calls over any split of the face list give the bytes of one call.
+ * Two entries with the caller's prefix sum between them:
+ *   count: per item k = f * cascade + c the number count[k] (int32 [F*cascade])
+ *     of (x, y) columns of the index box of face f in cascade c, 0 when the
+ *     face meets nothing or an interval is empty; the index boxes go to
+ *     `workspace` (ucsa_mesh_voxelize_workspace_bytes = 24 * F * cascade);
+ *   the caller: first int64 [F*cascade + 1] = the exclusive prefix sum of count,
+ *     total = first[F*cascade], read back once;
+ *   fill: clears the mask (unless accumulate), then one lane per column walks
+ *     the column's z-run (csrc/mesh_voxelize.hip states the work per lane).
+ *     It takes the geometry arguments of the count call and its workspace.
+ * Neither entry allocates or reads anything back.
+ * Limits, ERR_ARG - argument index: verts / faces not NULL unless F = 0 (verts
+ * also when V = 0); V, F <= 2^31-1 and F * cascade <= 2^31-1 (argument 3);
+ * family 0 or 1; lattice: dims >= 1 each, nx*ny*nz <= 2^31-1 (argument 5),
+ * origin3 / spacing3 not NULL, origin finite with Bmax <= 2^40, spacing > 0 and
+ * finite, cascade = 1; cascade family: 2 <= nx <= 1024, ny = nz = nx, bound > 0
+ * and finite, 1 <= cascade <= 31; 0 <= dilate <= 2^40; count, mask, first,
+ * workspace not NULL when there is an item / a column; total <= 2^38, and 0
+ * when F = 0; accumulate 0 or 1; mask_capacity (bytes) >= cascade*nx*ny*nz;
+ * workspace_bytes as above.  An argument error comes before any launch;
+ * nothing outside mask[0 .. cascade*nx*ny*nz), count and the workspace is
+ * written. */
+#define UCSA_VOXELIZE_LATTICE 0u
+#define UCSA_VOXELIZE_CASCADE 1u
+uint64_t ucsa_mesh_voxelize_workspace_bytes(uint32_t nf, uint32_t cascade);
+int32_t ucsa_mesh_voxelize_count(const float* verts, uint32_t nv, const int32_t* faces,
+                                 uint32_t nf, uint32_t family, uint32_t nx, uint32_t ny,
+                                 uint32_t nz, const float* origin3, const float* spacing3,
+                                 float bound, uint32_t cascade, float dilate, int32_t* count,
+                                 void* workspace, uint64_t workspace_bytes, void* stream);
+int32_t ucsa_mesh_voxelize_fill(const float* verts, uint32_t nv, const int32_t* faces,
+                                uint32_t nf, uint32_t family, uint32_t nx, uint32_t ny,
+                                uint32_t nz, const float* origin3, const float* spacing3,
+                                float bound, uint32_t cascade, float dilate,
+                                const int64_t* first, uint64_t total, uint32_t accumulate,
+                                uint8_t* mask, uint64_t mask_capacity, const void* workspace,
+                                uint64_t workspace_bytes, void* stream);
+
 /* ---- voxel map: per-voxel class votes and a ray-caster over the TSDF volume
  * (not in the reference) ----------------------------------------------------
  * The voxel route of the mapping baseline (utils/voxel_map.py,

@@ -15,7 +15,18 @@ the space the sensor saw to be empty; ``empty`` also carves what no view
 observed and everything outside the volume.  Writes the mask and its parameters
 (``utils.occupancy_prior.save_prior``); ``nerf: {cuda_ray: true,
 occupancy_prior: prior.npz}`` in an experiment YAML makes the training loop load
-it.  Prints one ``occupancy_prior:`` line of statistics."""
+it.  Prints one ``occupancy_prior:`` line of statistics.
+
+    python scripts/occupancy_prior.py --mesh M.ply [--mesh_pose_frame] --out prior.npz \\
+        [--bound 4] [--dilate UNITS] [--H 128]
+
+The mesh route (``ops.mesh_occupancy``): no depth frames, no ``--scene_root``.
+The prior is the shell of cells the mesh's faces pass through, grown by
+``--dilate`` (scene units; default: one finest cell).  The vertices are in the
+field's (NGP) frame, in scene units, as ``fuse_tsdf_mesh.py`` and
+``export_semantic_mesh.py`` write them by default; ``--mesh_pose_frame`` says they
+are in the frame of transforms_train.json's poses instead (metres with
+``--one_m_to_scene_uom``, as for ``score_mesh_3d.py``)."""
 import argparse
 import json
 import os
@@ -26,14 +37,20 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ucsa_neural_rendering_amd.utils.mesh_render import read_frames  # noqa: E402
+from ucsa_neural_rendering_amd.utils.mesh_render import load_mesh, read_frames  # noqa: E402
 from ucsa_neural_rendering_amd.utils.occupancy_prior import (  # noqa: E402
-    prior_from_depth_views, save_prior)
+    prior_from_depth_views, prior_from_mesh, save_prior)
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument("--scene_root", required=True, help="<root>/<scene>")
+    p.add_argument("--scene_root", default=None, help="<root>/<scene> (the depth route)")
+    p.add_argument("--mesh", default=None, help="a triangle mesh (.ply): the mesh route")
+    p.add_argument("--mesh_pose_frame", action="store_true",
+                   help="the mesh is in the frame of transforms_train.json's poses")
+    p.add_argument("--one_m_to_scene_uom", type=float, default=None,
+                   help="with --mesh_pose_frame: the mesh is in metres")
+    p.add_argument("--H", type=int, default=128, help="the grid's resolution (the mesh route)")
     p.add_argument("--out", required=True, help="the prior to write (.npz)")
     p.add_argument("--bound", type=float, default=4.0, help="the renderer's bound")
     p.add_argument("--voxel", type=float, default=0.05, help="metres")
@@ -41,12 +58,31 @@ def parse_args(argv=None):
     p.add_argument("--dilate", type=float, default=None, help="metres (default: one voxel)")
     p.add_argument("--unknown", choices=("keep", "empty"), default="keep")
     p.add_argument("--every", type=int, default=1, help="use every N-th frame")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if (a.scene_root is None) == (a.mesh is None):
+        p.error("one of --scene_root (the depth route) and --mesh (the mesh route) is required")
+    return a
+
+
+def main_mesh(a):
+    mesh = load_mesh(a.mesh, pose_frame=a.mesh_pose_frame, one_m_to_scene_uom=a.one_m_to_scene_uom)
+    mask, st = prior_from_mesh(mesh["verts"], mesh["faces"], a.bound, H=a.H, dilate=a.dilate)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    save_prior(a.out, mask, a.bound, source="mesh", dilate=np.float32(st["dilate"]),
+               faces=np.int64(st["faces"]))
+    rec = {"out": a.out, "source": "mesh", "faces": st["faces"], "skipped": st["skipped"],
+           "bound": a.bound, "cascade": int(mask.shape[0]), "H": int(mask.shape[1]),
+           "dilate": round(st["dilate"], 6), "kept": [round(v, 4) for v in st["kept"]],
+           "voxelize_ms": round(st["voxelize_ms"], 3)}
+    print("occupancy_prior: " + json.dumps(rec))
+    return rec
 
 
 def main(argv=None):
     from PIL import Image
     a = parse_args(argv)
+    if a.mesh is not None:
+        return main_mesh(a)
     if a.every < 1:
         raise SystemExit("--every must be >= 1")
     fr = read_frames(a.scene_root)

@@ -34,6 +34,10 @@ samples are measured to the other mesh's surface instead of to its samples
 even on one surface: keep ``--threshold`` above it, or use ``--surface``).
 Both lines then carry a ``"sampled"`` entry: the number of ground-truth samples
 in ``3d:``, ``[n_pred, n_gt]`` in ``geometry:``.
+``--voxel_iou VOXEL`` adds a ``"voxel_iou"`` entry to ``geometry:``: both meshes
+voxelized on one lattice of that spacing (``utils.mesh_eval.voxel_iou``), IoU /
+precision / recall of the occupied voxel sets: a geometry score that depends
+neither on tessellation nor on a distance threshold.
 Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
 import argparse
 import json
@@ -46,7 +50,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from ucsa_neural_rendering_amd.utils.mesh_eval import (  # noqa: E402
-    mesh_distance, sample_surface, score_labels_3d)
+    mesh_distance, sample_surface, score_labels_3d, voxel_iou)
 from ucsa_neural_rendering_amd.utils.mesh_render import load_mesh  # noqa: E402
 
 
@@ -66,6 +70,9 @@ def parse_args(argv=None):
     p.add_argument("--sample_density", type=float, default=None,
                    help="query points sampled from the surfaces, so many per unit area")
     p.add_argument("--sample_seed", type=int, default=0)
+    p.add_argument("--voxel_iou", type=float, default=None, metavar="VOXEL",
+                   help="add the volumetric IoU of the two meshes' voxel sets at this voxel "
+                        "size (scene units) to geometry")
     return p.parse_args(argv)
 
 
@@ -108,6 +115,13 @@ def main(argv=None):
         gs, _, gres = sample_surface(gv, gt["faces"], dens, a.sample_seed)
         rec["geometry"] = mesh_distance(ps, gs, a.threshold, a.max_dist)
         rec["geometry"]["sampled"] = [pres["n_samples"], gres["n_samples"]]
+    if a.voxel_iou is not None:
+        if not a.voxel_iou > 0:
+            raise SystemExit("--voxel_iou must be > 0")
+        if any(m["faces"] is None or not len(m["faces"]) for m in (pred, gt)):
+            raise SystemExit("--voxel_iou needs faces in both meshes")
+        rec["geometry"]["voxel_iou"] = voxel_iou(pred["verts"], pred["faces"], gv, gt["faces"],
+                                                 a.voxel_iou)
     print("geometry: " + json.dumps(rec["geometry"]))
     return rec
 

@@ -325,6 +325,14 @@ SIGNATURES = {
     "ucsa_tsdf_occupancy": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
                                         C.POINTER(_f), _f, _f, _u32, _f, _u32, _u32, _f,
                                         _p, C.c_uint64, _p, C.c_uint64, _p]),
+    # ---- mesh voxelization (the cells of a lattice or of the cascade grid a mesh meets) ----
+    "ucsa_mesh_voxelize_workspace_bytes": (C.c_uint64, [_u32, _u32]),
+    "ucsa_mesh_voxelize_count": (C.c_int32, [_p, _u32, _p, _u32, _u32, _u32, _u32, _u32,
+                                             C.POINTER(_f), C.POINTER(_f), _f, _u32, _f, _p, _p,
+                                             C.c_uint64, _p]),
+    "ucsa_mesh_voxelize_fill": (C.c_int32, [_p, _u32, _p, _u32, _u32, _u32, _u32, _u32,
+                                            C.POINTER(_f), C.POINTER(_f), _f, _u32, _f, _p,
+                                            C.c_uint64, _u32, _p, C.c_uint64, _p, C.c_uint64, _p]),
     # ---- voxel map (per-voxel class votes, ray-caster over the TSDF volume) ----
     "ucsa_tsdf_vote": (C.c_int32, [_p, C.c_uint64, _u32, _u32, _u32, _u32, C.POINTER(_f),
                                    C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f, _u32,

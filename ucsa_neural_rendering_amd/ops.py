@@ -2909,3 +2909,127 @@ def sample_mesh_surface(verts, faces, density, seed: int = 0, normals=None, rgb=
                                           _stream()), "ucsa_mesh_surface_samples")
     out.update(area=area, count=count, first=first, n_samples=S, density=density)
     return out
+
+
+# ---------------------------------------------------------------------------
+# mesh voxelization (the cells of a lattice or of the cascade grid a mesh meets)
+# ---------------------------------------------------------------------------
+VOXELIZE_LATTICE, VOXELIZE_CASCADE = 0, 1
+
+
+def _voxelize(what, verts, faces, family, dims, origin, spacing, bound, cascade, dilate, out):
+    pts = _points3(verts, "verts")
+    dev = pts.device
+    if dev.index != torch.cuda.current_device():
+        raise _lib.UcsaError(f"the mesh is on {dev} but the current device is cuda:"
+                             f"{torch.cuda.current_device()}: call torch.cuda.set_device first")
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.device == dev):
+        raise _lib.UcsaError("faces must be a GPU tensor on the vertices' device: the HIP path "
+                             "has no CPU fallback")
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+        raise _lib.UcsaError(f"faces must be an integer tensor, got {faces.dtype}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.UcsaError(f"faces must be [F,3], got {tuple(faces.shape)}")
+    V, F = int(pts.shape[0]), int(faces.shape[0])
+    if F * cascade > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"{what}: faces x cascades must be at most 2^31-1")
+    lo_hi = torch.stack(torch.aminmax(faces)).tolist() if F else [0, 0]
+    if F and (lo_hi[0] < 0 or lo_hi[1] >= V):
+        raise _lib.UcsaError(f"faces index outside [0, {V})")
+    fc = _i32(faces.to(torch.int32).contiguous(), "faces")
+    if not (dilate >= 0 and math.isfinite(dilate)):
+        raise _lib.UcsaError(f"{what}: dilate must be >= 0 and finite, got {dilate}")
+    nx, ny, nz = dims
+    shape = (nx, ny, nz) if family == VOXELIZE_LATTICE else (cascade, nx, ny, nz)
+    if out is None:
+        mask = torch.empty(shape, dtype=torch.uint8, device=dev)
+    else:
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == dev
+                and out.dtype == torch.uint8 and tuple(out.shape) == shape
+                and out.is_contiguous()):
+            raise _lib.UcsaError(f"out must be a contiguous uint8 {list(shape)} tensor on the "
+                                 "vertices' device")
+        mask = out
+    o3 = fvec(origin) if origin is not None else None
+    s3 = fvec(spacing) if spacing is not None else None
+    geo = (_ptr(pts) if V else None, V, _ptr(fc) if F else None, F, family, nx, ny, nz, o3, s3,
+           bound, cascade, dilate)
+    items = F * cascade
+    ws_bytes = int(lib().ucsa_mesh_voxelize_workspace_bytes(F, cascade))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev) if items else None
+    count = torch.empty(items, dtype=torch.int32, device=dev) if items else None
+    check(lib().ucsa_mesh_voxelize_count(*geo, _ptr(count), _ptr(ws), ws_bytes, _stream()),
+          "ucsa_mesh_voxelize_count")
+    first, total = None, 0
+    if items:
+        first = torch.zeros(items + 1, dtype=torch.int64, device=dev)
+        first[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+        total = int(first[items])
+    check(lib().ucsa_mesh_voxelize_fill(*geo, _ptr(first), total, 0 if out is None else 1,
+                                        _ptr(mask), mask.numel(), _ptr(ws), ws_bytes, _stream()),
+          "ucsa_mesh_voxelize_fill")
+    return mask
+
+
+def voxelize_mesh(verts, faces, dims, origin, spacing, dilate: float = 0.0, out=None):
+    """The voxels of a lattice that a triangle mesh passes through: uint8
+    [nx,ny,nz] on the mesh's device, 1 = some face meets the voxel's box.  The
+    lattice is ``tsdf_volume``'s: voxel (i,j,k) is the box of side ``spacing``
+    (a number or 3) centred on origin + (i,j,k)*spacing, grown by ``dilate``
+    (scene units) on every side; the mask can index a volume's arrays and go to
+    ``voxel_components``.  ``verts`` float32 [V,3], ``faces`` an integer tensor
+    [F,3] with indices in [0,V), both on the GPU; a face with a non-finite
+    corner marks nothing, a segment or a point marks the voxels it touches.
+    ``out`` (uint8 [nx,ny,nz], contiguous) accumulates: met voxels are set to 1
+    and every other byte is left alone, so any split of the faces over calls
+    gives the bytes of one call.  F = 0 gives an all-zero mask.  Contract of
+    ucsa_mesh_voxelize_count / ucsa_mesh_voxelize_fill (include/ucsa_hip.h):
+    conservative in float32 (a touching pair is never lost), a pure OR, the
+    same bytes every run and for every face order.  Reads back the face index
+    range (validation) and, between the two kernels, the column total."""
+    try:
+        dims = tuple(int(d) for d in dims)
+    except (TypeError, ValueError):
+        raise _lib.UcsaError(f"voxelize_mesh: dims must be 3 integers, got {dims!r}")
+    if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"voxelize_mesh: dims must be 3 integers >= 1 with at most 2^31-1 "
+                             f"voxels, got {dims}")
+    spacing = [float(spacing)] * 3 if isinstance(spacing, (int, float)) else \
+        [float(v) for v in spacing]
+    origin = [float(v) for v in origin]
+    if len(origin) != 3 or len(spacing) != 3:
+        raise _lib.UcsaError("voxelize_mesh: origin and spacing have 3 entries each")
+    if not all(v > 0 and math.isfinite(v) for v in spacing):
+        raise _lib.UcsaError(f"voxelize_mesh: spacing must be > 0 and finite, got {spacing}")
+    if not all(math.isfinite(v) for v in origin):
+        raise _lib.UcsaError(f"voxelize_mesh: origin must be finite, got {origin}")
+    return _voxelize("voxelize_mesh", verts, faces, VOXELIZE_LATTICE, dims, origin, spacing, 0.0,
+                     1, float(dilate), out)
+
+
+def mesh_occupancy(verts, faces, bound, cascade=None, H: int = 128, dilate=None, out=None):
+    """Occupancy prior of a triangle mesh for the marcher's cascade grid: uint8
+    [cascade,H,H,H] on the mesh's device, 1 = some face meets the cell's box, 0
+    = the mesh does not come near the cell: a shell of cells around the
+    surfaces.  ``SemanticNeRFRenderer.set_occupancy_prior`` takes the result.
+    ``verts`` / ``faces`` as for ``voxelize_mesh``, in the field's (NGP) frame;
+    ``bound`` the renderer's; ``cascade`` None is the renderer's
+    ``1 + ceil(log2(bound))``, as in ``tsdf_occupancy``; ``dilate`` (scene
+    units, grows every cell's box on all sides) None is one finest cell,
+    ``2 * min(1, bound) / H``: a mesh is a surface estimate, and the field's
+    surface may sit a cell beside it; ``out`` accumulates as in
+    ``voxelize_mesh``.  F = 0 gives an all-zero mask.  Contract of
+    ucsa_mesh_voxelize_count / ucsa_mesh_voxelize_fill (include/ucsa_hip.h)."""
+    bound = float(bound)
+    if not (bound > 0 and math.isfinite(bound)):
+        raise _lib.UcsaError(f"mesh_occupancy: bound must be > 0 and finite, got {bound}")
+    if cascade is None:
+        cascade = 1 + math.ceil(math.log2(bound))
+    cascade, H = int(cascade), int(H)
+    if not 1 <= cascade <= 31:
+        raise _lib.UcsaError(f"mesh_occupancy: cascade must be in 1..31, got {cascade}")
+    if not 2 <= H <= 1024:
+        raise _lib.UcsaError(f"mesh_occupancy: H must be in 2..1024, got {H}")
+    dilate = 2.0 * min(1.0, bound) / H if dilate is None else float(dilate)
+    return _voxelize("mesh_occupancy", verts, faces, VOXELIZE_CASCADE, (H, H, H), None, None,
+                     bound, cascade, dilate, out)

@@ -21,7 +21,11 @@ That settles the target.  The query points are a mesh's vertices unless
 ``sample_density`` is given: then they are drawn from the mesh's surface
 (``ops.sample_mesh_surface``: so many points per unit area, deterministic for a
 ``seed``), so that a wall of two triangles weighs by its area and not by its
-four corners, and a hole in the middle of it costs what it covers."""
+four corners, and a hole in the middle of it costs what it covers.
+
+``voxel_iou`` is the score that depends neither on tessellation nor on a
+distance threshold: both meshes are voxelized on one lattice
+(``ops.voxelize_mesh``) and the occupied voxel sets are compared."""
 from __future__ import annotations
 
 import numpy as np
@@ -233,3 +237,45 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
     if sample_density is not None:
         out["sampled"] = sampled
     return out
+
+
+def voxel_iou(pred_verts, pred_faces, gt_verts, gt_faces, voxel, dilate=0.0, aabb=None,
+              max_voxels=1 << 28):
+    """Volumetric IoU of the voxel sets two meshes pass through
+    (``ops.voxelize_mesh``, surface voxelization: a cell counts when a face
+    meets its box grown by ``dilate``).  The lattice is cubic with spacing
+    ``voxel`` over the union box of the finite vertices of both meshes (or
+    ``aabb`` [2,3]) padded by one voxel: origin = lo - voxel, dims =
+    ceil((hi + voxel - origin) / voxel) + 1 per axis, in float32.  -> {"iou":
+    |P & G| / |P | G| (1.0 when both are empty), "precision": |P & G| / |P|,
+    "recall": |P & G| / |G| (1.0 for an empty denominator), "n_pred", "n_gt",
+    "dims", "voxel"}.  More than ``max_voxels`` voxels is an error raised
+    before anything of that size is allocated."""
+    pred = _verts(pred_verts)
+    gt = _verts(gt_verts, pred.device)
+    voxel = float(np.float32(voxel))
+    if not (voxel > 0 and np.isfinite(voxel)):
+        raise ValueError(f"voxel must be > 0 and finite, got {voxel}")
+    if aabb is None:
+        pts = torch.cat([pred, gt])
+        pts = pts[torch.isfinite(pts).all(1)]
+        if pts.shape[0] == 0:
+            raise ValueError("voxel_iou: no finite vertex and no aabb")
+        box = torch.stack([pts.amin(0), pts.amax(0)]).cpu().numpy()
+    else:
+        box = np.asarray(aabb, np.float32).reshape(2, 3)
+    v32 = np.float32(voxel)
+    lo = (box[0] - v32).astype(np.float32)
+    hi = (box[1] + v32).astype(np.float32)
+    dims = tuple(int(np.ceil(float(hi[a] - lo[a]) / voxel)) + 1 for a in range(3))
+    if dims[0] * dims[1] * dims[2] > min(int(max_voxels), 0x7FFFFFFF):
+        raise ValueError(f"voxel {voxel} gives {dims} voxels, more than max_voxels = "
+                         f"{max_voxels}: raise voxel")
+    origin = [float(v) for v in lo]
+    P = ops.voxelize_mesh(pred, _faces(pred_faces, pred.device), dims, origin, voxel, dilate) != 0
+    G = ops.voxelize_mesh(gt, _faces(gt_faces, pred.device), dims, origin, voxel, dilate) != 0
+    inter, n_p, n_g = int((P & G).sum()), int(P.sum()), int(G.sum())
+    union = n_p + n_g - inter
+    return {"iou": inter / union if union else 1.0, "precision": inter / n_p if n_p else 1.0,
+            "recall": inter / n_g if n_g else 1.0, "n_pred": n_p, "n_gt": n_g,
+            "dims": list(dims), "voxel": voxel}

@@ -8,9 +8,17 @@ NeRF's frame, so the marcher need not learn it.
 A fresh field has sigma ~ 1 everywhere and the marcher walks the air densely
 until the grid has forgotten it (``refresh_due``); with the prior the measured
 free space is skipped from step 0 and stays skipped.  The volume is picked the
-way ``tsdf_fusion.fuse_depth_views`` picks it.  Out of scope: carving straight
-from depth views without a volume, camera-coverage marking without depth,
-sparse volumes."""
+way ``tsdf_fusion.fuse_depth_views`` picks it.
+
+A scene that comes with a mesh (ScanNet's ``*_vh_clean_2.ply``, the PLY of an
+earlier ``fuse_tsdf_mesh.py`` run, the previous stage's exported field) needs no
+depth frames and no volume: ``prior_from_mesh`` keeps the shell of cells the
+mesh passes through (``ops.mesh_occupancy``).
+
+    mesh --ops.mesh_occupancy--> mask --set_occupancy_prior--> density_grid
+
+Out of scope: carving straight from depth views without a volume,
+camera-coverage marking without depth, sparse volumes."""
 from __future__ import annotations
 
 import time
@@ -87,6 +95,34 @@ def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.0
              "free": float(free.float().mean()), "dims": tuple(vol["tsdf"].shape),
              "origin": vol["origin"], "spacing": vol["spacing"], "trunc": trunc,
              "integrate_ms": t_i, "occupancy_ms": 1e3 * t_o}
+    return mask, stats
+
+
+def prior_from_mesh(verts, faces, bound, **mesh_occupancy_kw):
+    """``verts`` [V,3] / ``faces`` [F,3] (numpy or tensors) in the field's (NGP)
+    frame, ``bound`` the renderer's; ``mesh_occupancy_kw`` goes to
+    ``ops.mesh_occupancy`` (cascade, H, dilate).  -> (mask uint8 [cascade,H,H,H]
+    on the device, stats): ``kept`` the kept share per cascade, ``faces`` the
+    face count, ``skipped`` the faces that mark nothing because a corner is not
+    finite, ``dilate`` as used, and the wall time ``voxelize_ms``
+    (device-synchronised host clock)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    v = torch.as_tensor(np.asarray(verts, np.float32) if not torch.is_tensor(verts) else verts)
+    v = v.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    f = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces)
+    f = f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mask = ops.mesh_occupancy(v, f, bound, **mesh_occupancy_kw)
+    torch.cuda.synchronize()
+    t_v = time.perf_counter() - t0
+    skipped = int((~torch.isfinite(v)[f.long()].all(-1).all(-1)).sum()) if f.shape[0] else 0
+    dilate = mesh_occupancy_kw.get("dilate")
+    if dilate is None:
+        dilate = 2.0 * min(1.0, float(bound)) / int(mask.shape[1])
+    stats = {"kept": [float(x) for x in mask.float().mean((1, 2, 3)).tolist()],
+             "faces": int(f.shape[0]), "skipped": skipped, "dilate": float(dilate),
+             "voxelize_ms": 1e3 * t_v}
     return mask, stats
 
 
