@@ -22,7 +22,8 @@
  *     it (INTEGRATION.md "Environment variables": launch shapes and kernel
  *     choices, never results); (b) per caller-stream sets of internal streams /
  *     events created on first use by the calls documented as pipelined
- *     (ucsa_render_view, the merged grid backward).
+ *     (ucsa_render_view, the merged grid backward); (c) the device's LDS per
+ *     workgroup, asked of the runtime at the first ucsa_resample.
  */
 #ifndef UCSA_HIP_H_
 #define UCSA_HIP_H_
@@ -162,7 +163,13 @@ int32_t ucsa_sigma_mlp_fwd(const float* feat, const float* packed_sigma,
  * Replaces renderer_semantics.py:182-207 and sample_pdf :10-46.
  *   z [N,T], sigma [N,T], u [N,t] in [0,1); out new_z [N,t], ASCENDING per
  *   ray (the uniforms are sorted first; the reference only ever consumes
- *   new_z through its sort/merge, :221-222, so the order is unobservable). */
+ *   new_z through its sort/merge, :221-222, so the order is unobservable).
+ *   Sizes: 3 <= T <= 4096, t <= 4096, AND the ray's arrays fit the LDS of one
+ *   workgroup: 16 (3 T + tpad) bytes, tpad = the next power of two >= t (>= 2),
+ *   at most hipDeviceAttributeMaxSharedMemoryPerBlock (163,840 B on gfx950, asked
+ *   of the runtime once per process): T = t = 2048 fits, T = 2048 with t = 4096
+ *   fills it exactly, T >= 3414 never fits.  A larger request returns UCSA_ERR_ARG - 4 (the T arrays
+ *   alone are too large) or UCSA_ERR_ARG - 5 before anything is launched. */
 int32_t ucsa_resample(const float* z, const float* sigma, const float* u,
                       uint32_t N, uint32_t T, uint32_t t,
                       float density_scale, float* new_z, void* stream);

@@ -170,6 +170,20 @@ k_resample(const float* __restrict__ z, const float* __restrict__ sigma,
   }
 }
 
+// LDS a workgroup may hold on the current device (163,840 B on gfx950), asked
+// of the runtime once; 64 KiB, what every device grants, if it does not say.
+static size_t rs_lds_per_workgroup() {
+  static const size_t bytes = [] {
+    int dev = 0, b = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&b, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+        b <= 0)
+      b = 65536;
+    return (size_t)b;
+  }();
+  return bytes;
+}
+
 extern "C" int32_t ucsa_resample(const float* z, const float* sigma,
                                  const float* u, uint32_t N, uint32_t T,
                                  uint32_t t, float density_scale, float* new_z,
@@ -183,7 +197,20 @@ extern "C" int32_t ucsa_resample(const float* z, const float* sigma,
   UCSA_CHECK_ARG(t <= 4096, 5);
   uint32_t tpad = 2;
   while (tpad < t) tpad <<= 1;
+  // zs, cdf, bins [T] and us [tpad] per wave, RS_WAVES waves: 16 (3 T + tpad) bytes
+  // of dynamic LDS.  What a workgroup cannot hold is an argument error, not a
+  // failed launch: T when the three ray arrays alone do not fit, else t.
+  const size_t lds_max = rs_lds_per_workgroup();
+  UCSA_CHECK_ARG((size_t)RS_WAVES * 3 * T * sizeof(float) <= lds_max, 4);
   const size_t smem = (size_t)RS_WAVES * (3 * T + tpad) * sizeof(float);
+  UCSA_CHECK_ARG(smem <= lds_max, 5);
+  // past the 64 KiB every launch may ask for, the kernel's limit is raised first
+  if (smem > 65536) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resample),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)smem);
+    if (e != hipSuccess) return -(int32_t)e;
+  }
   UCSA_CLEAR_ERR();
   hipLaunchKernelGGL(k_resample, dim3(ucsa_div_up(N, RS_WAVES)),
                      dim3(64 * RS_WAVES), smem, (hipStream_t)stream, z, sigma,

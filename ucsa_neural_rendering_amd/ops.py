@@ -292,6 +292,12 @@ def sigma_mlp_fwd(feat, packed_sigma) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 def resample(z, sigma, u, density_scale: float = 1.0):
+    """z, sigma [N, T], u [N, t] in [0, 1) -> new_z [N, t], ascending per ray
+    (``ucsa_resample``).  3 <= T <= 4096, t <= 4096, and one workgroup's LDS
+    must hold the rays of four waves: ``16 * (3 * T + tpad)`` bytes with
+    ``tpad`` the next power of two >= t, at most 163,840 on gfx950 (T = t =
+    2048 fits).  Anything larger raises ``UcsaError`` with the argument code of
+    T (-1004) or t (-1005); nothing is launched."""
     z = _f32(z, "z")
     sigma = _f32(sigma, "sigma")
     u = _f32(u, "u")
