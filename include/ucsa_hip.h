@@ -2206,6 +2206,100 @@ int32_t ucsa_mesh_surface_samples(const float* verts, uint32_t nv, const int32_t
                                   float* bary, float* out_normals, uint8_t* out_rgb,
                                   uint8_t* out_labels, void* stream);
 
+/* ---- signed distance to a triangle mesh (not in the reference) ----
+ * The nearest-triangle search says how far a point is from a surface; this
+ * section says on which side.  The sign is that of the angle-weighted
+ * pseudonormal of the feature (face, edge or vertex) the closest point lies on
+ * (Baerentzen and Aanaes 2005): the nearest face's own normal gives the wrong
+ * sign near convex edges and vertices, the pseudonormal does not.  Positive is
+ * the side (B - A) x (C - A) points to.  tests/sdf_numpy.py restates the four
+ * contracts in plain loops and the outputs match it byte for byte.  The inputs
+ * are never modified.  All arithmetic is float32, every operation rounded and
+ * nothing fused, sqrt and divide correctly rounded;
+ * dot(x,y) = (x0*y0 + x1*y1) + x2*y2 and a face is valid as in the
+ * nearest-triangle section: corner indices in [0, nv), finite corners.
+ *
+ * ucsa_face_unit_normals: verts [nv][3] float32, faces [nf][3] int32 ->
+ *   unit_normal [nf][3] float32.  One lane per face with corners A, B, C:
+ *   e1 = B - A, e2 = C - A, n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z,
+ *   e1x*e2y - e1y*e2x), l = sqrt(dot(n, n)); the row is n / l per component if
+ *   l > 0 and finite, else zeros; zeros for an invalid face too.
+ *   Limits: nv, nf <= 2^31-1 (arguments 1, 3).  nf == 0: returns 0, launches
+ *   nothing.
+ * ucsa_normal_runs: items [n_items] int32, run_first [n_runs+1] int32, weight
+ *   [3*nf] float32 or NULL, unit_normal [nf][3] -> out [n_runs][3] float32.  One
+ *   lane per run r: acc = 0; for pos = run_first[r] .. run_first[r+1]-1 in
+ *   order, it = items[pos], w = weight ? weight[it] : 1, f = it / 3:
+ *   acc_c = acc_c + w * unit_normal[f][c] (the product, then the sum);
+ *   out[r] = acc, not normalised: only its direction is used.  Offsets are
+ *   clamped into [0, n_items] and a decreasing pair is an empty run (zeros); an
+ *   item outside [0, 3*nf) is skipped.  The same entry point serves
+ *   vertices: runs are vertices, items the corners 3f+k that touch the vertex,
+ *             weights the corner angles (an input: no transcendental function is
+ *             part of a byte promise here);
+ *   edges:    runs are undirected edges, items the half-edges 3f+k (edge k of
+ *             face f runs from corner k to corner (k+1)%3), no weights.
+ *   ops.mesh_pseudonormals builds the runs with stable sorts, so the items of a
+ *   run ascend and a sum has one order.  A sequential float sum is the
+ *   definition: no atomics, no LDS, and a run is one lane's loop that is not
+ *   split across lanes, so a vertex shared by every face of a mesh costs one
+ *   lane walking all of them.  The loop is bounded by n_items.
+ *   Limits: n_runs, n_items <= 2^31-1 (arguments 2, 3), nf <= (2^31-1)/3 (6).
+ *   n_runs == 0: returns 0, launches nothing.
+ * ucsa_mesh_sign: vertex_normal [nv][3] and edge_normal [nf][3][3] (row k of a
+ *   face: the sum of its edge k, scattered to every half-edge of that edge) are
+ *   the sums above; queries [nq][3], face [nq] int32 (an input: the face the
+ *   search found) -> sdf [nq] float32, feature [nq] int32.  One lane per query.
+ *   face < 0, face >= nf or an invalid face: sdf = +inf, feature = -1.
+ *   Otherwise the closest-point expressions of the nearest-triangle section are
+ *   evaluated again for (query, face): the same operands, so the same bits.
+ *   The region that decided (v, w), numbered in that section's order from 0,
+ *   gives the feature:  0 -> 4 (vertex A)   1 -> 5 (vertex B)   3 -> 6 (vertex C)
+ *                       2 -> 1 (edge AB)    5 -> 2 (edge BC)    4 -> 3 (edge CA)
+ *                       otherwise -> 0 (the face's interior).
+ *   N = unit_normal[f] (feature 0), edge_normal[f][feature-1] (1..3) or
+ *   vertex_normal[faces[f][feature-4]] (4..6); s = -dot(p, N) with p the closest
+ *   point, the query at the origin; d = sqrt(dist2); sdf = s < 0 ? -d : d.  A
+ *   zero or NaN N gives +d; a query on the surface (p = 0) gives +0.
+ *   Limits: nv, nf, nq <= 2^31-1 (arguments 1, 3, 8).  nq == 0: returns 0,
+ *   launches nothing.
+ * ucsa_mesh_tsdf: records, offsets, n_pairs, origin, cell, dims are the grid of
+ *   ucsa_nearest_triangle; tsdf and weight [nx][ny][nz] float32 are the arrays of
+ *   ucsa_tsdf_integrate with its lattice vol_origin[3], vol_spacing[3] (host
+ *   arrays; a spacing may be negative).  One launch, one lane per voxel, z
+ *   fastest, so a wave walks neighbouring cells.  The voxel's point is
+ *   vol_origin[a] + (float)i_a * vol_spacing[a] (the product, then the sum).
+ *   From it runs exactly ucsa_nearest_triangle's search with max_dist = trunc
+ *   (the smallest dist2 within trunc*trunc, inclusive, the smallest face index
+ *   on a tie), without a queries array and without a face / dist2 / bary round
+ *   trip; then the sign as in ucsa_mesh_sign.  On a match t = sdf / trunc, then
+ *   as selects t = t < -1 ? -1 : t; t = t > 1 ? 1 : t; tsdf[v] = t and
+ *   weight[v] = weight_value.  A voxel without a match is neither read nor
+ *   written: the band is overwritten, not averaged with what the volume held.
+ *   Cost: that of the search; a voxel farther than trunc from the grid's box
+ *   walks nothing, one with nothing near walks every cell within trunc.
+ *   Limits: n_pairs <= 2^31-1 (argument 2), the grid as in ucsa_nearest_triangle
+ *   (3..5), nv, nf <= 2^31-1 (7, 9), nx, ny, nz >= 2 each with at most 2^31-1
+ *   voxels (15), trunc > 0 with a finite float32 square (20), records 16-byte
+ *   aligned (0).  n_pairs == 0: returns 0 and writes nothing.
+ * An argument error comes before any launch and nothing is written. */
+int32_t ucsa_face_unit_normals(const float* verts, uint32_t nv, const int32_t* faces, uint32_t nf,
+                               float* unit_normal, void* stream);
+int32_t ucsa_normal_runs(const int32_t* items, const int32_t* run_first, uint32_t n_runs,
+                         uint32_t n_items, const float* weight, const float* unit_normal,
+                         uint32_t nf, float* out, void* stream);
+int32_t ucsa_mesh_sign(const float* verts, uint32_t nv, const int32_t* faces, uint32_t nf,
+                       const float* unit_normal, const float* vertex_normal,
+                       const float* edge_normal, const float* queries, uint32_t nq,
+                       const int32_t* face, float* sdf, int32_t* feature, void* stream);
+int32_t ucsa_mesh_tsdf(const float* records, const int32_t* offsets, uint32_t n_pairs,
+                       const float* origin, float cell, const uint32_t* dims, const float* verts,
+                       uint32_t nv, const int32_t* faces, uint32_t nf, const float* unit_normal,
+                       const float* vertex_normal, const float* edge_normal, float* tsdf,
+                       float* weight, uint32_t nx, uint32_t ny, uint32_t nz,
+                       const float* vol_origin, const float* vol_spacing, float trunc,
+                       float weight_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ and the geometry as accuracy, completeness, chamfer and F-score.
 
     python scripts/score_mesh_3d.py --pred P.ply --gt G.ply [--max_dist M] \\
         [--threshold T] [--pred_pose_frame] [--gt_pose_frame] [--one_m_to_scene_uom U] \\
-        [--gt_transform T.txt] [--num_classes C] [--surface] \\
+        [--gt_transform T.txt] [--num_classes C] [--surface] [--signed] \\
         [--sample_density D [--sample_seed S]]
 
 Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
@@ -38,6 +38,14 @@ in ``3d:``, ``[n_pred, n_gt]`` in ``geometry:``.
 voxelized on one lattice of that spacing (``utils.mesh_eval.voxel_iou``), IoU /
 precision / recall of the occupied voxel sets: a geometry score that depends
 neither on tessellation nor on a distance threshold.
+``--signed`` (needs faces in the ground truth) measures the pred -> gt direction
+to the ground-truth surface, as ``--surface`` does for that direction, with
+``ops.signed_distance``, and adds ``"signed_mean"``, ``"signed_median"`` and
+``"behind_share"`` to ``geometry:``: the signed offset of the predicted points
+from the ground-truth surface over the matched points, positive on the side the
+ground-truth faces' normals (B-A)x(C-A) point to, and the share of points on
+the other side.  That tells an inflated surface from a deflated one, which
+accuracy and completeness cannot.
 Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
 import argparse
 import json
@@ -67,6 +75,9 @@ def parse_args(argv=None):
     p.add_argument("--num_classes", type=int, default=40)
     p.add_argument("--surface", action="store_true",
                    help="measure to the nearest point on the other mesh's faces, not its vertices")
+    p.add_argument("--signed", action="store_true",
+                   help="add the signed offset of pred from the gt surface to geometry "
+                        "(pred -> gt is then measured to the gt faces)")
     p.add_argument("--sample_density", type=float, default=None,
                    help="query points sampled from the surfaces, so many per unit area")
     p.add_argument("--sample_seed", type=int, default=0)
@@ -90,6 +101,12 @@ def main(argv=None):
     pf, gf = (pred["faces"], gt["faces"]) if a.surface else (None, None)
     if a.surface and (pf is None or gf is None or not len(pf) or not len(gf)):
         raise SystemExit("--surface needs faces in both meshes")
+    if a.signed and (gt["faces"] is None or not len(gt["faces"])):
+        raise SystemExit("--signed needs faces in the ground-truth mesh")
+    if a.signed and a.sample_density is not None and not a.surface:
+        raise SystemExit("--signed with --sample_density needs --surface: the samples are "
+                         "measured to the ground-truth surface")
+    more_g = {"gt_faces": gt["faces"], "signed": True} if a.signed else {"gt_faces": gf}
     dens = a.sample_density
     if dens is not None:
         if not dens > 0:
@@ -106,10 +123,10 @@ def main(argv=None):
         print("3d: " + json.dumps(rec["3d"]))
     if dens is None:
         rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist, pred_faces=pf,
-                                        gt_faces=gf)
+                                        **more_g)
     elif a.surface:
         rec["geometry"] = mesh_distance(pred["verts"], gv, a.threshold, a.max_dist, pred_faces=pf,
-                                        gt_faces=gf, sample_density=dens, seed=a.sample_seed)
+                                        sample_density=dens, seed=a.sample_seed, **more_g)
     else:                                           # the two sampled point sets, point to point
         ps, _, pres = sample_surface(pred["verts"], pred["faces"], dens, a.sample_seed)
         gs, _, gres = sample_surface(gv, gt["faces"], dens, a.sample_seed)

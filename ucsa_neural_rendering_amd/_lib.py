@@ -382,6 +382,13 @@ SIGNATURES = {
     "ucsa_face_sample_counts": (C.c_int32, [_p, _u32, _p, _u32, _f, _u32, _p, _p, _p]),
     "ucsa_mesh_surface_samples": (C.c_int32, [_p, _u32, _p, _u32, _p, _u32, _u32, _p, _p, _p, _p,
                                               _p, _p, _p, _p, _p, _p]),
+    # ---- signed distance to a triangle mesh ----
+    "ucsa_face_unit_normals": (C.c_int32, [_p, _u32, _p, _u32, _p, _p]),
+    "ucsa_normal_runs": (C.c_int32, [_p, _p, _u32, _u32, _p, _p, _u32, _p, _p]),
+    "ucsa_mesh_sign": (C.c_int32, [_p, _u32, _p, _u32, _p, _p, _p, _p, _u32, _p, _p, _p, _p]),
+    "ucsa_mesh_tsdf": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _u32,
+                                   _p, _u32, _p, _p, _p, _p, _p, _u32, _u32, _u32,
+                                   C.POINTER(_f), C.POINTER(_f), _f, _f, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

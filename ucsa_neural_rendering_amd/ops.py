@@ -3039,3 +3039,204 @@ def mesh_occupancy(verts, faces, bound, cascade=None, H: int = 128, dilate=None,
     dilate = 2.0 * min(1.0, bound) / H if dilate is None else float(dilate)
     return _voxelize("mesh_occupancy", verts, faces, VOXELIZE_CASCADE, (H, H, H), None, None,
                      bound, cascade, dilate, out)
+
+
+# ---------------------------------------------------------------------------
+# signed distance to a triangle mesh (pseudonormal sign, mesh to TSDF volume)
+# ---------------------------------------------------------------------------
+def _mesh_i32(verts, faces):
+    v = _points3(verts, "verts")
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.dtype == torch.int32 and faces.device == v.device):
+        raise _lib.UcsaError("faces must be an int32 [F,3] tensor on the GPU of verts: the HIP "
+                             "path has no CPU fallback")
+    if faces.shape[0] > 0x7FFFFFFF // 3:
+        raise _lib.UcsaError("faces must have at most (2^31-1)/3 rows")
+    return v, faces.contiguous()
+
+
+def _normal_runs(items, run_first, n_runs, weight, unit, nf):
+    out = torch.zeros((n_runs, 3), dtype=torch.float32, device=unit.device)
+    check(lib().ucsa_normal_runs(_ptr(items) if items.numel() else None, _ptr(run_first), n_runs,
+                                 int(items.numel()), _ptr(weight), _ptr(unit) if nf else None, nf,
+                                 _ptr(out) if n_runs else None, _stream()), "ucsa_normal_runs")
+    return out
+
+
+def mesh_pseudonormals(verts, faces):
+    """The normals the sign of ``signed_distance`` / ``mesh_tsdf`` is taken from
+    (Baerentzen and Aanaes 2005) -> dict: ``unit_normal`` [F,3] (of
+    (B-A)x(C-A); zeros for a degenerate or invalid face), ``corner_angle``
+    [F,3] (radians, 0 for an invalid face), ``vertex_normal`` [V,3] (the sum
+    over the faces at a vertex of corner angle * unit normal) and
+    ``edge_normal`` [F,3,3] (row k of a face: the sum of the unit normals of all
+    faces that share its edge corner k -> corner (k+1)%3), all float32 on the
+    mesh's device, not normalised: only directions are used.  ``verts`` [V,3]
+    float32, ``faces`` [F,3] int32, on the GPU; a face with a corner index
+    outside [0,V) or a non-finite corner contributes nothing.  The unit normals
+    and the two sums are kernels (ucsa_face_unit_normals, ucsa_normal_runs);
+    the corner angles -- atan2(|u x w|, u.w) of the two edges leaving the corner
+    -- and the stable sorts that group corners by vertex and half-edges by
+    undirected edge are torch on the device.  The sorts are stable, so the
+    items of a run ascend in 3f+k and every sum has one order."""
+    v, f = _mesh_i32(verts, faces)
+    dev = v.device
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    unit = torch.zeros((nf, 3), dtype=torch.float32, device=dev)
+    check(lib().ucsa_face_unit_normals(_ptr(v) if nv else None, nv, _ptr(f) if nf else None, nf,
+                                       _ptr(unit) if nf else None, _stream()),
+          "ucsa_face_unit_normals")
+    ok = ((f >= 0) & (f < nv)).all(1) if nv else torch.zeros(nf, dtype=torch.bool, device=dev)
+    if nv and nf:
+        ok &= torch.isfinite(v).all(1)[f.clamp(0, nv - 1).long()].all(1)
+    angle = torch.zeros((nf, 3), dtype=torch.float32, device=dev)
+    if nv and nf:
+        P = v[f.clamp(0, nv - 1).long()]                                # [F,3 corners,3]
+        for k in range(3):
+            u, w = P[:, (k + 1) % 3] - P[:, k], P[:, (k + 2) % 3] - P[:, k]
+            a = torch.atan2(torch.linalg.cross(u, w).norm(dim=1), (u * w).sum(1))
+            angle[:, k] = torch.where(ok & torch.isfinite(a), a, torch.zeros_like(a))
+    corner = torch.arange(3 * nf, dtype=torch.int32, device=dev)
+    valid = ok.repeat_interleave(3)
+    items0 = corner[valid]
+    flat = f.reshape(-1).long()
+    # vertices: the valid corners by vertex index, ties by 3f+k
+    vid = flat[valid]
+    order = torch.sort(vid, stable=True).indices
+    v_items = items0[order].contiguous()
+    v_first = torch.searchsorted(vid[order].contiguous(),
+                                 torch.arange(nv + 1, dtype=torch.int64, device=dev)
+                                 ).to(torch.int32)
+    vertex_normal = _normal_runs(v_items, v_first, nv, angle.reshape(-1), unit, nf)
+    # edges: the valid half-edges by undirected edge, ties by 3f+k
+    nxt = f[:, [1, 2, 0]].reshape(-1).long()
+    a, b = flat[valid], nxt[valid]
+    key = torch.minimum(a, b) * max(nv, 1) + torch.maximum(a, b)
+    order = torch.sort(key, stable=True).indices
+    e_items = items0[order].contiguous()
+    skey = key[order]
+    n_half = int(skey.numel())
+    head = torch.ones(n_half, dtype=torch.bool, device=dev)
+    if n_half > 1:
+        head[1:] = skey[1:] != skey[:-1]
+    starts = torch.nonzero(head).reshape(-1)
+    n_edges = int(starts.numel())
+    e_first = torch.empty(n_edges + 1, dtype=torch.int32, device=dev)
+    e_first[:n_edges] = starts
+    e_first[n_edges] = n_half
+    sums = _normal_runs(e_items, e_first, n_edges, None, unit, nf)
+    edge_normal = torch.zeros((3 * nf, 3), dtype=torch.float32, device=dev)
+    if n_half:
+        edge_normal[e_items.long()] = sums[torch.cumsum(head, 0) - 1]
+    return {"unit_normal": unit, "corner_angle": angle, "vertex_normal": vertex_normal,
+            "edge_normal": edge_normal.view(nf, 3, 3)}
+
+
+def _normals_args(normals, nv, nf, dev):
+    try:
+        un, vn, en = normals["unit_normal"], normals["vertex_normal"], normals["edge_normal"]
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("normals must be the dict of ops.mesh_pseudonormals")
+    for t, shape, name in ((un, (nf, 3), "unit_normal"), (vn, (nv, 3), "vertex_normal"),
+                           (en, (nf, 3, 3), "edge_normal")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev
+                and tuple(t.shape) == shape and t.is_contiguous()):
+            raise _lib.UcsaError(f"normals: {name} must be a contiguous float32 {list(shape)} "
+                                 "tensor on the mesh's device (a different mesh?)")
+    return (_ptr(un) if nf else None, _ptr(vn) if nv else None, _ptr(en) if nf else None)
+
+
+def signed_distance(grid, normals, verts, faces, queries, max_dist: float,
+                    sort_queries: bool = True):
+    """For each of ``queries`` [Q,3] the signed distance to the mesh ``verts`` /
+    ``faces`` within ``max_dist`` -> (``sdf`` float32 [Q], ``face``, ``dist2``,
+    ``bary``, ``feature`` int32 [Q]): ``nearest_triangle`` (``grid`` is
+    ``triangle_grid``'s dict of the same mesh; face, dist2 and bary are its
+    outputs) followed by the sign.  ``abs(sdf)`` is ``sqrt(dist2)``; the sign is
+    that of the angle-weighted pseudonormal (``normals``:
+    ``mesh_pseudonormals``'s dict) of the feature the closest point lies on:
+    ``feature`` 0 the face's interior, 1..3 its edges AB, BC, CA, 4..6 its
+    corners A, B, C.  Positive is the side (B-A)x(C-A) points to: outside a
+    mesh whose faces are counter-clockwise seen from outside.  No face within
+    ``max_dist``: +inf and feature -1; a query on the surface: +0.  The sign is
+    right wherever the mesh is a consistently oriented surface near the query;
+    it is not a winding number and does not repair a badly oriented mesh.
+    Contract of ucsa_mesh_sign (include/ucsa_hip.h)."""
+    v, f = _mesh_i32(verts, faces)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    try:
+        grid_faces = int(grid["n_faces"])
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("grid must be the dict of ops.triangle_grid")
+    if grid_faces != nf:
+        raise _lib.UcsaError(f"grid was built over {grid_faces} faces, the mesh has {nf}")
+    un, vn, en = _normals_args(normals, nv, nf, v.device)
+    face, dist2, bary = nearest_triangle(grid, queries, max_dist, sort_queries)
+    q = _points3(queries, "queries")
+    if q.device != v.device:
+        raise _lib.UcsaError(f"the mesh is on {v.device}, the queries on {q.device}")
+    nq = int(q.shape[0])
+    sdf = torch.empty(nq, dtype=torch.float32, device=q.device)
+    feature = torch.empty(nq, dtype=torch.int32, device=q.device)
+    check(lib().ucsa_mesh_sign(_ptr(v) if nv else None, nv, _ptr(f) if nf else None, nf, un, vn,
+                               en, _ptr(q), nq, _ptr(face), _ptr(sdf), _ptr(feature), _stream()),
+          "ucsa_mesh_sign")
+    return sdf, face, dist2, bary, feature
+
+
+def mesh_tsdf(volume, verts, faces, trunc: float, weight: float = 1.0, grid=None, normals=None):
+    """Write the truncated signed distance to a mesh into ``volume``
+    (``tsdf_volume``), in place; returns ``volume``.  Every voxel within
+    ``trunc`` (scene units, inclusive) of the surface gets
+    ``tsdf = clamp(sdf / trunc, -1, 1)`` and ``weight = weight``; every other
+    voxel keeps what it held, so a fresh volume stays free and unobserved
+    outside the band, as after ``integrate_tsdf``, and ``raycast_tsdf``,
+    ``marching_cubes(valid=)``, ``tsdf_occupancy`` and ``voxel_components`` take
+    the result.  The band is overwritten: the mesh is not averaged with what
+    the volume held there, and ``rgb`` is not touched.  The sign is
+    ``signed_distance``'s (positive on the side (B-A)x(C-A) points to, which is
+    free space for a mesh that is counter-clockwise seen from outside).
+    ``grid`` / ``normals`` are ``triangle_grid``'s and ``mesh_pseudonormals``'s
+    dicts of the mesh, built here when not given.  One launch
+    (ucsa_mesh_tsdf, include/ucsa_hip.h): the search runs from the lattice
+    points themselves, byte for byte ``signed_distance`` on the materialised
+    lattice."""
+    (nx, ny, nz), dev = _volume_lattice(volume)
+    v, f = _mesh_i32(verts, faces)
+    if v.device != dev:
+        raise _lib.UcsaError(f"the volume is on {dev}, the mesh on {v.device}")
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    trunc = float(trunc)
+    if not (trunc > 0 and math.isfinite(trunc)):
+        raise _lib.UcsaError(f"mesh_tsdf: trunc must be positive and finite, got {trunc!r}")
+    weight = float(weight)
+    if math.isnan(weight):
+        raise _lib.UcsaError("mesh_tsdf: weight must not be NaN")
+    origin = [float(x) for x in volume["origin"]]
+    spacing = [float(x) for x in volume["spacing"]]
+    if len(origin) != 3 or len(spacing) != 3:
+        raise _lib.UcsaError("mesh_tsdf: origin and spacing have 3 entries each")
+    if grid is None:
+        grid = triangle_grid(v, f)
+    if normals is None:
+        normals = mesh_pseudonormals(v, f)
+    try:
+        rec, offsets, n = grid["records"], grid["offsets"], int(grid["n_pairs"])
+        g_origin, cell, dims, grid_faces = grid["origin"], float(grid["cell"]), grid["dims"], \
+            int(grid["n_faces"])
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("grid must be the dict of ops.triangle_grid")
+    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if not (torch.is_tensor(rec) and rec.dtype == torch.float32 and rec.is_contiguous()
+            and tuple(rec.shape) == (n, 12) and rec.device == dev and torch.is_tensor(offsets)
+            and offsets.dtype == torch.int32 and offsets.is_contiguous()
+            and offsets.device == dev and offsets.numel() == ncells + 1 and grid_faces == nf):
+        raise _lib.UcsaError("grid: records must be float32 [n_pairs,12] and offsets int32 "
+                             "[cells+1], contiguous, on the volume's GPU, built over this mesh")
+    un, vn, en = _normals_args(normals, nv, nf, dev)
+    check(lib().ucsa_mesh_tsdf(
+        _ptr(rec) if n else None, _ptr(offsets) if n else None, n, fvec(g_origin), cell,
+        (C.c_uint32 * 3)(*[int(d) for d in dims]), _ptr(v) if nv else None, nv,
+        _ptr(f) if nf else None, nf, un, vn, en, _ptr(volume["tsdf"]), _ptr(volume["weight"]),
+        nx, ny, nz, fvec(origin), fvec(spacing), trunc, weight, _stream()), "ucsa_mesh_tsdf")
+    return volume

@@ -25,7 +25,12 @@ four corners, and a hole in the middle of it costs what it covers.
 
 ``voxel_iou`` is the score that depends neither on tessellation nor on a
 distance threshold: both meshes are voxelized on one lattice
-(``ops.voxelize_mesh``) and the occupied voxel sets are compared."""
+(``ops.voxelize_mesh``) and the occupied voxel sets are compared.
+
+All of these are unsigned.  ``mesh_distance(signed=True)`` and ``tsdf_bias`` say
+on which side of the ground-truth surface a mesh or a fused volume lies
+(``ops.signed_distance``, ``ops.mesh_tsdf``): an inflated surface and a deflated
+one score the same everywhere else."""
 from __future__ import annotations
 
 import numpy as np
@@ -178,7 +183,7 @@ def score_voxel_labels_3d(volume, voxel_labels, gt_verts, gt_labels, max_dist, C
 
 
 def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt_faces=None,
-                  sample_density=None, seed=0):
+                  sample_density=None, seed=0, signed=False):
     """Vertex-to-vertex distances both ways -> {"accuracy": mean pred -> gt,
     "completeness": mean gt -> pred, "chamfer": their mean, "precision": the share
     of pred vertices within ``threshold`` of gt, "recall": the share of gt
@@ -198,9 +203,22 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
     those of ``gt_faces``.  Recall then falls by the share of the ground-truth
     area that the predicted mesh leaves uncovered.  The dict also holds
     "sampled": [n_pred, n_gt], the number of samples on each side (0 for a side
-    without faces, which is measured from its vertices)."""
+    without faces, which is measured from its vertices).
+
+    ``signed`` (needs ``gt_faces``): the pred -> gt direction is
+    ``ops.signed_distance`` and the dict gains, over the matched points only, in
+    float64 on the device, "signed_mean" and "signed_median" (the median is the
+    lower one) of the signed distance and "behind_share", the share with a
+    negative one; nan when nothing matched.  Positive is the side the
+    ground-truth faces' (B-A)x(C-A) points to: for a ground truth that is
+    counter-clockwise seen from outside, a positive mean is an inflated
+    prediction and a negative one a deflated one.  Every other entry is what it
+    is without the keyword."""
     pred = _verts(pred_verts)
     gt = _verts(gt_verts, pred.device)
+    if signed and gt_faces is None:
+        raise ValueError("mesh_distance: signed needs gt_faces")
+    signed_out = {}
     pred_from, gt_from, sampled = pred, gt, [0, 0]
     if sample_density is not None:
         if pred_faces is not None:
@@ -210,10 +228,22 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
             gt_from, _, res = sample_surface(gt, gt_faces, sample_density, seed)
             sampled[1] = res["n_samples"]
 
-    def one_way(a, b, b_faces):
+    def one_way(a, b, b_faces, with_sign=False):
+        if with_sign:
+            signed_out.update(signed_mean=float("nan"), signed_median=float("nan"),
+                              behind_share=float("nan"))
         if a.shape[0] == 0:
             return float("nan"), float("nan")
-        if b_faces is not None:
+        if with_sign:
+            fc = _faces(b_faces, b.device)
+            sdf, index, dist2, _, _ = ops.signed_distance(
+                ops.triangle_grid(b, fc), ops.mesh_pseudonormals(b, fc), b, fc, a, max_dist)
+            s = sdf[index >= 0].double()
+            if s.numel():
+                signed_out.update(signed_mean=float(s.mean()),
+                                  signed_median=float(s.median()),
+                                  behind_share=float((s < 0).double().mean()))
+        elif b_faces is not None:
             grid = ops.triangle_grid(b, _faces(b_faces, b.device))
             index, dist2, _ = ops.nearest_triangle(grid, a, max_dist)
         else:
@@ -222,7 +252,7 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
                         torch.full_like(dist2, float(max_dist), dtype=torch.float64))
         return float(d.mean()), float(((index >= 0) & (d <= float(threshold))).double().mean())
 
-    acc, prec = one_way(pred_from, gt, gt_faces)
+    acc, prec = one_way(pred_from, gt, gt_faces, bool(signed))
     comp, rec = one_way(gt_from, pred, pred_faces)
     if not prec + rec >= 0:                         # an empty set: nan
         f = float("nan")
@@ -236,6 +266,7 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
         out["surface"] = (gt_faces is not None, pred_faces is not None)
     if sample_density is not None:
         out["sampled"] = sampled
+    out.update(signed_out)
     return out
 
 
@@ -279,3 +310,26 @@ def voxel_iou(pred_verts, pred_faces, gt_verts, gt_faces, voxel, dilate=0.0, aab
     return {"iou": inter / union if union else 1.0, "precision": inter / n_p if n_p else 1.0,
             "recall": inter / n_g if n_g else 1.0, "n_pred": n_p, "n_gt": n_g,
             "dims": list(dims), "voxel": voxel}
+
+
+def tsdf_bias(volume, gt_verts, gt_faces, trunc, min_weight=1.0):
+    """The signed offset of a fused TSDF volume from a ground-truth mesh, voxel
+    by voxel: ``ops.mesh_tsdf`` fills a scratch volume of the same lattice from
+    the mesh, and over the voxels observed in both (``weight >= min_weight`` in
+    ``volume``, inside the mesh's band of ``trunc``) the differences
+    ``(tsdf - tsdf_gt) * trunc`` (scene units) give {"mean", "median" (the lower
+    one), "mean_abs", "n"}; nan with n = 0 when no voxel is shared.  ``trunc``
+    is the truncation ``volume`` was fused with.  A positive mean says the
+    fused surface lies on the negative side of the mesh (behind it, for a mesh
+    that is counter-clockwise seen from outside): the fused volume is
+    deflated."""
+    (nx, ny, nz), dev = ops._volume_lattice(volume)
+    ref = ops.tsdf_volume((nx, ny, nz), volume["origin"], volume["spacing"], device=dev)
+    ops.mesh_tsdf(ref, _verts(gt_verts, dev), _faces(gt_faces, dev), trunc, weight=1.0)
+    both = (volume["weight"] >= float(min_weight)) & (ref["weight"] > 0)
+    d = (volume["tsdf"][both].double() - ref["tsdf"][both].double()) * float(trunc)
+    n = int(d.numel())
+    if n == 0:
+        return {"mean": float("nan"), "median": float("nan"), "mean_abs": float("nan"), "n": 0}
+    return {"mean": float(d.mean()), "median": float(d.median()),
+            "mean_abs": float(d.abs().mean()), "n": n}

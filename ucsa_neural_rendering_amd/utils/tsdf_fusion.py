@@ -192,3 +192,46 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
             "rgb": None if rgb is None else rgb.cpu().numpy(), "labels": None,
             "dims": tuple(dims), "origin": vol["origin"], "spacing": vol["spacing"],
             "observed": observed, "integrate_ms": 1e3 * t_i, "extract_ms": 1e3 * t_e}
+
+
+def volume_from_mesh(verts, faces, voxel, trunc, aabb=None, max_voxels=1 << 28):
+    """A TSDF volume made from a triangle mesh instead of from depth frames
+    (``ops.mesh_tsdf``): a ground-truth mesh, an earlier stage's export or a
+    simplified mesh can then be ray-cast (``ops.raycast_tsdf``), re-meshed at a
+    uniform step (``extract_mesh``), turned into the occupancy prior
+    (``ops.tsdf_occupancy``) or compared voxel by voxel with a fused volume
+    (``utils.mesh_eval.tsdf_bias``).  The lattice is ``voxel_iou``'s rule padded
+    by ``trunc``: cubic with spacing ``voxel`` over the box of the finite
+    vertices (or ``aabb`` [2,3]), origin = lo - (trunc + voxel), dims =
+    ceil((hi + (trunc + voxel) - origin) / voxel) + 1 per axis, in float32.
+    Voxels within ``trunc`` of the surface hold tsdf = clamp(sdf / trunc, -1, 1)
+    and weight 1, all others tsdf 1 and weight 0 (free, unobserved), as after
+    ``ops.integrate_tsdf``; positive is the side the faces' (B-A)x(C-A) points
+    to, so the mesh must be counter-clockwise seen from free space
+    (``ops.marching_cubes`` of ``-tsdf``, which ``extract_mesh`` uses, makes
+    such meshes).  More than ``max_voxels`` voxels is an error raised before
+    anything of that size is allocated."""
+    v = torch.as_tensor(np.asarray(verts, np.float32) if not torch.is_tensor(verts) else verts)
+    v = v.to(device="cuda" if not v.is_cuda else v.device, dtype=torch.float32).reshape(-1, 3)
+    v = v.contiguous()
+    f = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces)
+    f = f.to(device=v.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    voxel, trunc = float(np.float32(voxel)), float(np.float32(trunc))
+    if not (voxel > 0 and np.isfinite(voxel) and trunc > 0 and np.isfinite(trunc)):
+        raise ValueError(f"voxel and trunc must be > 0 and finite, got {voxel}, {trunc}")
+    if aabb is None:
+        pts = v[torch.isfinite(v).all(1)]
+        if pts.shape[0] == 0:
+            raise ValueError("volume_from_mesh: no finite vertex and no aabb")
+        box = torch.stack([pts.amin(0), pts.amax(0)]).cpu().numpy()
+    else:
+        box = np.asarray(aabb, np.float32).reshape(2, 3)
+    pad = np.float32(trunc) + np.float32(voxel)
+    lo = (box[0] - pad).astype(np.float32)
+    hi = (box[1] + pad).astype(np.float32)
+    dims = tuple(int(np.ceil(float(hi[a] - lo[a]) / voxel)) + 1 for a in range(3))
+    if dims[0] * dims[1] * dims[2] > min(int(max_voxels), 0x7FFFFFFF):
+        raise ValueError(f"voxel {voxel} gives {dims} voxels, more than max_voxels = "
+                         f"{max_voxels}: raise voxel")
+    volume = ops.tsdf_volume(dims, [float(x) for x in lo], voxel, device=v.device)
+    return ops.mesh_tsdf(volume, v, f, trunc)
