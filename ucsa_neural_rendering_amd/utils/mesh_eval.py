@@ -323,7 +323,7 @@ def tsdf_bias(volume, gt_verts, gt_faces, trunc, min_weight=1.0):
     fused surface lies on the negative side of the mesh (behind it, for a mesh
     that is counter-clockwise seen from outside): the fused volume is
     deflated."""
-    (nx, ny, nz), dev = ops._volume_lattice(volume)
+    (nx, ny, nz), dev = ops.volume_lattice(volume)
     ref = ops.tsdf_volume((nx, ny, nz), volume["origin"], volume["spacing"], device=dev)
     ops.mesh_tsdf(ref, _verts(gt_verts, dev), _faces(gt_faces, dev), trunc, weight=1.0)
     both = (volume["weight"] >= float(min_weight)) & (ref["weight"] > 0)
