@@ -10,12 +10,112 @@ from __future__ import annotations
 
 import numpy as np
 import os
+from typing import NamedTuple
 
 import torch
 
 from .. import _lib, ops
 from .encoding import FullyFusedMLP, HashGridEncoding, SHEncoding
 from .renderer_semantics import SemanticNeRFRenderer
+
+
+NETS = {"sigma": "sigma_net", "color": "color_net", "sem": "semantics_net"}
+
+# pack form -> (ops function, suffix of the cache slot).  The function is a NAME,
+# looked up at the call, so that replacing ``ops.NAME`` (lab tools, tests) takes.
+PACK_FORMS = {"f32": ("mlp_pack", ""), "t": ("mlp_pack_t", "_t"),
+              "h": ("mlp_pack_f16", "_h"), "th": ("mlp_pack_t_f16", "_th"),
+              "x3": ("mlp_pack_x3", "_x3"), "t_x3": ("mlp_pack_t_x3", "_t_x3"),
+              "h2": ("mlp_pack_h2", "_h2")}
+
+# A pack is named (form, net); forms "r16" / "r16_t": _pack_rounded_sigma.
+_F32_BWD = dict(packed_color=("f32", "color"), packed_sem=("f32", "sem"),
+                packed_color_t=("t", "color"), packed_sem_t=("t", "sem"),
+                packed_sigma=("f32", "sigma"), packed_sigma_t=("t", "sigma"))
+_F16_BWD = dict(_F32_BWD, packed_color=("h", "color"), packed_sem=("h", "sem"),
+                packed_color_t=("th", "color"), packed_sem_t=("th", "sem"))
+_X2_BWD = dict(packed_color=("x3", "color"), packed_sem=("x3", "sem"),
+               packed_color_t=("t_x3", "color"), packed_sem_t=("t_x3", "sem"),
+               packed_sigma=("x3", "sigma"), packed_sigma_t=("t_x3", "sigma"))
+# what _field_f16(transposed=True) packs, in its order
+_F16_SET = (("h", "sigma"), ("h", "color"), ("h", "sem"), ("th", "color"), ("th", "sem"))
+_FUSED_PACKS = tuple((form, name) for form in ("x3", "t_x3", "h2") for name in NETS)
+
+
+class _TrainPlan(NamedTuple):
+    """What one training pass through ``_RenderFn`` runs: decided once, by
+    ``_train_plan``, read by the forward and the backward."""
+    fused: bool = False          # forward and backward as ONE C call each
+    fused_packs: tuple = ()      # ... over these packs (ops.train_packs order)
+    half: bool = False           # colour / semantics nets on f16 MFMA
+    tcnn: bool = False           # tiny-cuda-nn's numerics end to end
+    x2: bool = False             # the backward's contractions as bf16 two-term splits
+    half_table: bool = False     # the hash grid read from the table's fp16 copy
+    sigma_fwd: str = ""          # ops.sigma_mlp_fwd* and the pack it reads
+    sigma_pack: tuple = ()
+    shade_fwd: str = ""          # the composite op, its colour / semantics packs, keywords
+    shade_packs: tuple = ()
+    shade_kw: dict = {}
+    bwd: dict = {}               # argument of the backward ops -> pack
+    # packs refreshed before the sigma pass / before the shade although that stage
+    # does not read them (all of them, or some): the order of the launches is kept
+    warm_sigma: tuple = ()
+    warm_shade: tuple = ()
+
+
+def _train_plan(net, t: int) -> _TrainPlan:
+    prec = net.train_precision
+    x3 = prec == "bf16x3"
+    # (round 4) the backward's contractions on the bf16 pipe as two-term splits
+    # (2^-16 per product; `nerf: {bwd_precision: fp32}` keeps the f32-input MFMA
+    # kernels)
+    x2 = x3 and net.bwd_precision == "bf16x2" and ops.shade_bwd_split()
+    fwd = "h2" if net.train_fwd_f16x2 else "x3"
+    if (x2 and not net.deterministic and net.fused_train_calls and net.grid_records_packed
+            and (net.grid_bwd_merged or t == 0)):
+        # the default training mode: forward and backward are ONE C call each
+        # (ucsa_render_fused_fwd / _bwd: the same launches as the staged passes,
+        # sequenced in the library); forward nets as f16x2 (three passes instead
+        # of six) with train_fwd_f16x2
+        # (no f32 weight packs in this mode: six small launches less per step)
+        return _TrainPlan(fused=True, x2=True,
+                          fused_packs=_FUSED_PACKS if fwd == "h2" else _FUSED_PACKS[:6])
+    if x3:
+        # sigma net: fp32-grade on the bf16 pipe, like the colour / semantics
+        # forward (1e-7 from the f32-input MFMA chain, 0.04 instead of 0.07 ms per
+        # million samples).  Forward of the colour / semantics stage on the split
+        # pair with the bf16x3 nets (fp32-grade, the dense bf16 MFMA pipe): same
+        # values as the f32-input MFMA chain to ~1e-7; the backward recomputes the
+        # nets with the f32-input MFMA as before, or (x2) from the bf16 packs
+        return _TrainPlan(
+            x2=x2, sigma_fwd="sigma_mlp_fwd_" + fwd, sigma_pack=(fwd, "sigma"),
+            shade_fwd="composite_train_fwd_x3", shade_packs=((fwd, "color"), (fwd, "sem")),
+            shade_kw=dict(h2=fwd == "h2"), warm_shade=(("x3", "color"), ("x3", "sem")),
+            bwd=_X2_BWD if x2 else _F32_BWD)
+    # train_precision="fp16": the colour / semantics nets (forward and
+    # backward) on f16 MFMA; the sigma net and the hash grid stay fp32
+    half = prec in ("fp16", "tcnn")
+    plan = _TrainPlan(
+        half=half, sigma_fwd="sigma_mlp_fwd", sigma_pack=("f32", "sigma"),
+        shade_fwd="composite_fwd", shade_kw=dict(want_aux=True, half=half),
+        shade_packs=(("h", "color"), ("h", "sem")) if half else (("f32", "color"), ("f32", "sem")),
+        bwd=_F16_BWD if half else _F32_BWD, warm_shade=_F16_SET if half else ())
+    if prec != "tcnn":
+        return plan
+    # train_precision="tcnn": tiny-cuda-nn's numerics end to end -- the
+    # hash table read from its fp16 copy, fp16 features, all three nets on
+    # f16 MFMA (fp16 weights / layer inputs, fp32 accumulate), half2 bin
+    # records; the fp32 parameters are the optimizer's master copy, as in
+    # tcnn (network_tcnn_semantics.py:36-58 of the reference).
+    # The sigma net's backward runs the fp32 kernel on the forward's
+    # fp16-rounded operands (rounded weights, rounded features; fp32
+    # accumulation like the f16 MFMA) with the recomputed hidden layer
+    # rounded to fp16 as tcnn's forward stored it (round 4:
+    # ucsa_sigma_mlp_bwd_h16)
+    return plan._replace(
+        tcnn=True, half_table=True, sigma_fwd="sigma_mlp_fwd_f16", sigma_pack=("h", "sigma"),
+        warm_sigma=_F16_SET, warm_shade=(("r16", "sigma"),),
+        bwd=dict(_F16_BWD, packed_sigma=("r16", "sigma"), packed_sigma_t=("r16_t", "sigma")))
 
 
 class _RenderFn(torch.autograd.Function):
@@ -30,118 +130,46 @@ class _RenderFn(torch.autograd.Function):
         N = o.shape[0]
         C = net.num_semantic_classes
         ds = float(net.density_scale)
-        ctx.fused = False
-        if (not net.deterministic and net.fused_train_calls and net.train_precision == "bf16x3"
-                and net.bwd_precision == "bf16x2" and ops.shade_bwd_split()
-                and net.grid_records_packed and (net.grid_bwd_merged or t == 0)):
-            # the default training mode: forward and backward are ONE C call each
-            # (ucsa_render_fused_fwd / _bwd: the same launches as the staged code
-            # below, sequenced in the library)
-            pk = [net._pack_x3(k, n) for k, n in (("sigma", net.sigma_net), ("color", net.color_net),
-                                                  ("sem", net.semantics_net))]
-            pk += [net._pack_t_x3(k, n) for k, n in (("sigma", net.sigma_net), ("color", net.color_net),
-                                                     ("sem", net.semantics_net))]
-            if net.train_fwd_f16x2:   # forward nets as f16x2 (three passes instead of six)
-                pk += [net._pack_h2(k, n) for k, n in (("sigma", net.sigma_net), ("color", net.color_net),
-                                                       ("sem", net.semantics_net))]
-            # (no f32 weight packs in this mode: six small launches less per step)
+        plan = _train_plan(net, t)
+        ctx.plan, ctx.net, ctx.aabb, ctx.T, ctx.t = plan, net, aabb, T, t
+        if plan.fused:
+            pk = [net._pack(form, name) for form, name in plan.fused_packs]
             f = dict(grid=net.encoder.grid, table=net.encoder.params.detach())
             image, depth, sem, sv = ops.render_fused_fwd(
                 f["grid"], f["table"], ops.train_packs(*pk), o, d, nrm, aabb, min_near,
                 rng_t, rng_u, T, t, C, ds)
-            ctx.fused, ctx.pk, ctx.sv = True, pk, sv
-            ctx.net, ctx.f, ctx.aabb, ctx.T, ctx.t = net, f, aabb, T, t
-            ctx.rays = (o, d, nrm)
+            ctx.f, ctx.pk, ctx.sv, ctx.rays = f, pk, sv, (o, d, nrm)
             return image, depth, sem
-        f = net._field(transposed=True)
+        f32 = net._field(transposed=True)
         near, far = ops.near_far_from_aabb(o, d, aabb, min_near)
         z_c = ops.sample_coarse(near, far, T, rng_t)
-        # train_precision="tcnn": tiny-cuda-nn's numerics end to end -- the
-        # hash table read from its fp16 copy, fp16 features, all three nets on
-        # f16 MFMA (fp16 weights / layer inputs, fp32 accumulate), half2 bin
-        # records; the fp32 parameters are the optimizer's master copy, as in
-        # tcnn (network_tcnn_semantics.py:36-58 of the reference)
-        tcnn = net.train_precision == "tcnn"
-        if tcnn:
-            fh = net._field_f16(transposed=True)
-            table, sig_fwd, sig_pack = net._table_half(), ops.sigma_mlp_fwd_f16, fh["packed_sigma"]
-        elif net.train_precision == "bf16x3":
-            # fp32-grade on the bf16 pipe, like the colour / semantics forward
-            # below (1e-7 from the f32-input MFMA chain, 0.04 instead of 0.07 ms
-            # per million samples)
-            if net.train_fwd_f16x2:
-                table, sig_fwd = f["table"], ops.sigma_mlp_fwd_h2
-                sig_pack = net._pack_h2("sigma", net.sigma_net)
-            else:
-                table, sig_fwd = f["table"], ops.sigma_mlp_fwd_x3
-                sig_pack = net._pack_x3("sigma", net.sigma_net)
-        else:
-            table, sig_fwd, sig_pack = f["table"], ops.sigma_mlp_fwd, f["packed_sigma"]
-        feat_c = ops.hashgrid_encode_rays(f["grid"], table, o, d, z_c, aabb)
+        net._build(plan.warm_sigma)
+        table = net._table_half() if plan.half_table else f32["table"]
+        sig_fwd, sig_pack = getattr(ops, plan.sigma_fwd), net._pack(*plan.sigma_pack)
+        feat_c = ops.hashgrid_encode_rays(f32["grid"], table, o, d, z_c, aabb)
         h_c, s_c = sig_fwd(feat_c, sig_pack)
         s_c = s_c.view(N, T)
         if t > 0:
             z_f = ops.resample(z_c, s_c, rng_u, ds)
-            feat_f = ops.hashgrid_encode_rays(f["grid"], table, o, d, z_f, aabb)
+            feat_f = ops.hashgrid_encode_rays(f32["grid"], table, o, d, z_f, aabb)
             h_f, s_f = sig_fwd(feat_f, sig_pack)
             s_f = s_f.view(N, t)
         else:
             z_f = feat_f = h_f = s_f = None
-        # train_precision="fp16": the colour / semantics nets (forward and
-        # backward) on f16 MFMA; the sigma net and the hash grid stay fp32
-        half = net.train_precision in ("fp16", "tcnn")
-        if half:
-            fh = net._field_f16(transposed=True)
-            f = dict(f, packed_color=fh["packed_color"], packed_sem=fh["packed_sem"],
-                     packed_color_t=fh["packed_color_t"],
-                     packed_sem_t=fh["packed_sem_t"])
-        if tcnn:
-            # the sigma net's backward runs the fp32 kernel on the forward's
-            # fp16-rounded operands (rounded weights, rounded features; fp32
-            # accumulation like the f16 MFMA) with the recomputed hidden layer
-            # rounded to fp16 as tcnn's forward stored it (round 4:
-            # ucsa_sigma_mlp_bwd_h16)
-            ps, pst = net._pack_rounded_sigma()
-            f = dict(f, packed_sigma=ps, packed_sigma_t=pst)
-        if net.train_precision == "bf16x3":
-            # forward of the colour / semantics stage on the split pair with
-            # the bf16x3 nets (fp32-grade, the dense bf16 MFMA pipe): same
-            # values as the f32-input MFMA chain to ~1e-7; the backward
-            # recomputes the nets with the f32-input MFMA as before
-            pcx, psx = net._pack_x3("color", net.color_net), net._pack_x3("sem", net.semantics_net)
-            if net.train_fwd_f16x2:
-                image, depth, sem, src, w = ops.composite_train_fwd_x3(
-                    d, nrm, z_c, s_c, h_c, z_f, s_f, h_f, net._pack_h2("color", net.color_net),
-                    net._pack_h2("sem", net.semantics_net), C, ds, h2=True)
-            else:
-                image, depth, sem, src, w = ops.composite_train_fwd_x3(
-                    d, nrm, z_c, s_c, h_c, z_f, s_f, h_f, pcx, psx, C, ds)
-            # ... and (round 4) the backward's contractions on the bf16 pipe as
-            # two-term splits (2^-16 per product; `nerf: {bwd_precision: fp32}`
-            # keeps the f32-input MFMA kernels)
-            if net.bwd_precision == "bf16x2" and ops.shade_bwd_split():
-                ctx.x2 = True
-                f = dict(f, packed_color=pcx, packed_sem=psx,
-                         packed_color_t=net._pack_t_x3("color", net.color_net),
-                         packed_sem_t=net._pack_t_x3("sem", net.semantics_net),
-                         packed_sigma=net._pack_x3("sigma", net.sigma_net),
-                         packed_sigma_t=net._pack_t_x3("sigma", net.sigma_net))
-        else:
-            image, depth, sem, src, w = ops.composite_fwd(
-                d, nrm, z_c, s_c, h_c, z_f, s_f, h_f, f["packed_color"],
-                f["packed_sem"], C, ds, want_aux=True, half=half)
-        ctx.half = half
-        ctx.tcnn = tcnn
-        ctx.x2 = bool(getattr(ctx, "x2", False))
-        ctx.net, ctx.f, ctx.aabb, ctx.T, ctx.t = net, f, aabb, T, t
+        net._build(plan.warm_shade)
+        image, depth, sem, src, w = getattr(ops, plan.shade_fwd)(
+            d, nrm, z_c, s_c, h_c, z_f, s_f, h_f, net._pack(*plan.shade_packs[0]),
+            net._pack(*plan.shade_packs[1]), C, ds, **plan.shade_kw)
+        # the backward's packs, stale ones made now, in this order
+        ctx.f = dict(grid=f32["grid"], **{k: net._pack(*fn) for k, fn in plan.bwd.items()})
         ctx.saved = (o, d, nrm, z_c, feat_c, h_c, s_c, z_f, feat_f, h_f, s_f,
                      src, w)
         return image, depth, sem
 
     @staticmethod
     def backward(ctx, d_image, d_depth, d_sem):
-        net, f, aabb, T, t = ctx.net, ctx.f, ctx.aabb, ctx.T, ctx.t
-        if ctx.fused:
+        net, f, aabb, T, t, plan = ctx.net, ctx.f, ctx.aabb, ctx.T, ctx.t, ctx.plan
+        if plan.fused:
             o, d, nrm = ctx.rays
             g_grid = torch.zeros_like(net.encoder.params)
             g_sigma = torch.empty_like(net.sigma_net.params)
@@ -161,27 +189,27 @@ class _RenderFn(torch.autograd.Function):
             d, nrm, z_c, s_c, h_c, z_f, s_f, h_f, src, w, f["packed_color"],
             f["packed_sem"], f["packed_color_t"], f["packed_sem_t"],
             d_image.contiguous(), d_depth.contiguous(), d_sem.contiguous(), C,
-            ds, half=ctx.half, f16_scale=float(net.f16_bwd_scale), x2=ctx.x2)
+            ds, half=plan.half, f16_scale=float(net.f16_bwd_scale), x2=plan.x2)
         g_color = torch.empty_like(net.color_net.params)
         g_sem = torch.empty_like(net.semantics_net.params)
         ops.reduce_partials(pc, g_color, False)
         ops.reduce_partials(ps, g_sem, False)
         g_sigma = torch.empty_like(net.sigma_net.params)
         g_grid = torch.zeros_like(net.encoder.params)
-        if ctx.tcnn:   # fp16 features -> the fp32 kernel's operand type
+        if plan.tcnn:   # fp16 features -> the fp32 kernel's operand type
             feat_c = feat_c.float()
             feat_f = None if feat_f is None else feat_f.float()
         d_feat, part = ops.sigma_mlp_bwd(feat_c, d_h_c, f["packed_sigma"],
-                                         f["packed_sigma_t"], x2=ctx.x2,
-                                         round_hidden=ctx.tcnn)
+                                         f["packed_sigma_t"], x2=plan.x2,
+                                         round_hidden=plan.tcnn)
         ops.reduce_partials(part, g_sigma, False)
         # f16 training mode: 8-byte bin records (half2 values under the same
         # loss scale as the nets' gradient operands)
-        rs = float(net.f16_bwd_scale) if (ctx.half and (net.f16_grid_records or ctx.tcnn)) else 0.0
+        rs = float(net.f16_bwd_scale) if (plan.half and (net.f16_grid_records or plan.tcnn)) else 0.0
         merged = t > 0 and net.grid_bwd_merged
         # bf16x2 backward: 8-byte packed bin records (26-bit values, 2^-18 --
         # finer than the two-term split that produced them)
-        pk = ctx.x2 and rs == 0.0 and net.grid_records_packed
+        pk = plan.x2 and rs == 0.0 and net.grid_records_packed
         if net.deterministic:
             # `UCSA_DETERMINISTIC=1` / net.deterministic: order-independent
             # fixed-point accumulation of the table gradient (two runs of a step
@@ -189,8 +217,8 @@ class _RenderFn(torch.autograd.Function):
             fix = ops.hashgrid_bwd_rays_det(f["grid"], o, d, z_c, aabb, d_feat)
             if t > 0:
                 d_feat_f, part = ops.sigma_mlp_bwd(feat_f, d_h_f, f["packed_sigma"],
-                                                   f["packed_sigma_t"], x2=ctx.x2,
-                                                   round_hidden=ctx.tcnn)
+                                                   f["packed_sigma_t"], x2=plan.x2,
+                                                   round_hidden=plan.tcnn)
                 ops.reduce_partials(part, g_sigma, True)
                 ops.hashgrid_bwd_rays_det(f["grid"], o, d, z_f, aabb, d_feat_f, fix)
             ops.hashgrid_bwd_det_finish(f["grid"], fix, g_grid)
@@ -201,8 +229,8 @@ class _RenderFn(torch.autograd.Function):
                                   rec_scale=rs, packed=pk)
         if t > 0:
             d_feat_f, part = ops.sigma_mlp_bwd(feat_f, d_h_f, f["packed_sigma"],
-                                               f["packed_sigma_t"], x2=ctx.x2,
-                                               round_hidden=ctx.tcnn)
+                                               f["packed_sigma_t"], x2=plan.x2,
+                                               round_hidden=plan.tcnn)
             ops.reduce_partials(part, g_sigma, True)
             if merged:
                 # both passes in one call, the ray's samples in sorted order: the
@@ -440,151 +468,91 @@ class SemanticNeRFNetwork(SemanticNeRFRenderer):
                     f"'f16x2' (< {lim:g}; csrc/mfma_mlp_h2.h).  Use nerf: {{precision: bf16x3}}.")
 
     # -- packed (MFMA A-fragment order) weights, refreshed when params change
-    def _pack(self, name: str, net: FullyFusedMLP):
-        p = net.params
+    def _cached(self, slot: str, p, make, *args):
+        """``self._packed[slot]``: what ``make(out, *args)`` made of the parameter
+        ``p``, made again when ``p`` was written to or replaced -- into the old
+        buffer (``out``) unless ``p`` moved to another device (``out`` None)."""
         key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name)
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            packed = ops.mlp_pack(net.kind, p, self.num_semantic_classes,
-                                  out=out)
-            self._packed[name] = (key, packed)
-        return self._packed[name][1]
+        hit = self._packed.get(slot)
+        here = hit is not None and (hit[1][0] if isinstance(hit[1], tuple) else hit[1]).device == p.device
+        if not here or hit[0] != key:
+            self._packed[slot] = (key, make(hit[1] if here else None, *args))
+            return self._packed[slot][1], True
+        return hit[1], False
 
-    def _pack_t(self, name: str, net: FullyFusedMLP):
-        p = net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name + "_t")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            packed = ops.mlp_pack_t(net.kind, p, self.num_semantic_classes,
-                                    out=out)
-            self._packed[name + "_t"] = (key, packed)
-        return self._packed[name + "_t"][1]
+    def _pack(self, form: str, name: str):
+        """The net ``name`` (NETS) packed in ``form`` (PACK_FORMS)."""
+        if form in ("r16", "r16_t"):
+            return self._pack_rounded_sigma()[form == "r16_t"]
+        net = getattr(self, NETS[name])
+        packed, fresh = self._cached(name + PACK_FORMS[form][1], net.params, self._make_pack,
+                                     form, name, net)
+        if fresh and form == "h2" and self._h2_guard_mode() != "off":
+            self._h2_after_pack(name)
+        return packed
 
-    def _pack_h(self, name: str, net: FullyFusedMLP):
-        p = net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name + "_h")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            packed = ops.mlp_pack_f16(net.kind, p, self.num_semantic_classes,
-                                      out=out)
-            self._packed[name + "_h"] = (key, packed)
-        return self._packed[name + "_h"][1]
+    def _make_pack(self, out, form, name, net):
+        p, kw = net.params, {}
+        if form == "h2":
+            # weights as two f16 terms (csrc/mfma_mlp_h2.h); under the range guard
+            # the pack kernel keeps max|value| in the net's pinned range word
+            guard = self._h2_guard_mode() != "off"
+            if guard and (name not in self._h2_scratch or self._h2_scratch[name].device != p.device):
+                self._h2_scratch[name] = torch.zeros(2, dtype=torch.int32, device=p.device)
+            kw = dict(range_bits=self._h2_flag(name, p.device) if guard else None,
+                      scratch=self._h2_scratch.get(name) if guard else None)
+        return getattr(ops, PACK_FORMS[form][0])(net.kind, p, self.num_semantic_classes,
+                                                  out=out, **kw)
 
-    def _pack_th(self, name: str, net: FullyFusedMLP):
-        p = net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name + "_th")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            packed = ops.mlp_pack_t_f16(net.kind, p, self.num_semantic_classes,
-                                        out=out)
-            self._packed[name + "_th"] = (key, packed)
-        return self._packed[name + "_th"][1]
+    def _build(self, packs):
+        for form, name in packs:
+            self._pack(form, name)
 
     def _pack_rounded_sigma(self):
         """fp32 packs (forward and transposed) of the sigma net's weights
         ROUNDED to fp16: what the f16 forward multiplied with, for the fp32
         backward kernel of train_precision="tcnn"."""
-        p = self.sigma_net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get("sigma_r16")
-        if hit is None or hit[0] != key or hit[1][0].device != p.device:
-            r = p.detach().half().float()
-            self._packed["sigma_r16"] = (key, (
-                ops.mlp_pack(self.sigma_net.kind, r, self.num_semantic_classes),
-                ops.mlp_pack_t(self.sigma_net.kind, r, self.num_semantic_classes)))
-        return self._packed["sigma_r16"][1]
+        return self._cached("sigma_r16", self.sigma_net.params, self._make_rounded_sigma)[0]
 
-    def _pack_x3(self, name: str, net: FullyFusedMLP):
-        p = net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name + "_x3")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            packed = ops.mlp_pack_x3(net.kind, p, self.num_semantic_classes,
-                                     out=out)
-            self._packed[name + "_x3"] = (key, packed)
-        return self._packed[name + "_x3"][1]
-
-    def _pack_h2(self, name: str, net: FullyFusedMLP):
-        """Weights as two f16 terms (csrc/mfma_mlp_h2.h), refreshed when the
-        parameters change."""
-        p = net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name + "_h2")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            guard = self._h2_guard_mode() != "off"
-            if guard and (name not in self._h2_scratch or self._h2_scratch[name].device != p.device):
-                self._h2_scratch[name] = torch.zeros(2, dtype=torch.int32, device=p.device)
-            packed = ops.mlp_pack_h2(net.kind, p, self.num_semantic_classes, out=out,
-                                     range_bits=self._h2_flag(name, p.device) if guard else None,
-                                     scratch=self._h2_scratch.get(name) if guard else None)
-            self._packed[name + "_h2"] = (key, packed)
-            if guard:
-                self._h2_after_pack(name)
-        return self._packed[name + "_h2"][1]
-
-    def _pack_t_x3(self, name: str, net: FullyFusedMLP):
-        """Transposed fragments of ``net`` as bf16 terms (the dX contractions
-        of the bf16x2 backward), refreshed when the parameters change."""
-        p = net.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get(name + "_t_x3")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            packed = ops.mlp_pack_t_x3(net.kind, p, self.num_semantic_classes, out=out)
-            self._packed[name + "_t_x3"] = (key, packed)
-        return self._packed[name + "_t_x3"][1]
+    def _make_rounded_sigma(self, out):
+        r = self.sigma_net.params.detach().half().float()
+        return (ops.mlp_pack(self.sigma_net.kind, r, self.num_semantic_classes),
+                ops.mlp_pack_t(self.sigma_net.kind, r, self.num_semantic_classes))
 
     def _table_half(self):
         """fp16 copy of the hash table (what tiny-cuda-nn stores), refreshed
         when the fp32 parameters change."""
-        p = self.encoder.params
-        key = (p.data_ptr(), p._version)
-        hit = self._packed.get("table_h16")
-        if hit is None or hit[0] != key or hit[1].device != p.device:
-            out = None if hit is None or hit[1].device != p.device else hit[1]
-            self._packed["table_h16"] = (key, ops.table_to_half(p, out=out))
-        return self._packed["table_h16"][1]
+        return self._cached("table_h16", self.encoder.params, self._make_table_half)[0]
+
+    def _make_table_half(self, out):
+        return ops.table_to_half(self.encoder.params, out=out)
+
+    def _nets(self, form: str, transposed: bool = False):
+        """grid, table and the three nets packed in ``form``; ``transposed``: also
+        the transposed packs (``form`` "f32": all three, "h": colour and
+        semantics, which is what their backward kernels read)."""
+        f = dict(grid=self.encoder.grid, table=self.encoder.params.detach())
+        for name in NETS:
+            f["packed_" + name] = self._pack(form, name)
+        if transposed:
+            t_form = {"f32": "t", "h": "th"}[form]
+            for name in (NETS if form == "f32" else ("color", "sem")):
+                f["packed_" + name + "_t"] = self._pack(t_form, name)
+        return f
 
     def _field_x3(self):
         """Weights as three bf16 terms each (csrc/mfma_mlp_x3.h)."""
-        return dict(grid=self.encoder.grid, table=self.encoder.params.detach(),
-                    packed_sigma=self._pack_x3("sigma", self.sigma_net),
-                    packed_color=self._pack_x3("color", self.color_net),
-                    packed_sem=self._pack_x3("sem", self.semantics_net))
+        return self._nets("x3")
 
     def _field_h2(self):
         """Weights as two f16 terms each (csrc/mfma_mlp_h2.h, "f16x2")."""
-        return dict(grid=self.encoder.grid, table=self.encoder.params.detach(),
-                    packed_sigma=self._pack_h2("sigma", self.sigma_net),
-                    packed_color=self._pack_h2("color", self.color_net),
-                    packed_sem=self._pack_h2("sem", self.semantics_net))
+        return self._nets("h2")
 
     def _field_f16(self, transposed: bool = False):
-        f = dict(grid=self.encoder.grid, table=self.encoder.params.detach(),
-                 packed_sigma=self._pack_h("sigma", self.sigma_net),
-                 packed_color=self._pack_h("color", self.color_net),
-                 packed_sem=self._pack_h("sem", self.semantics_net))
-        if transposed:
-            f.update(packed_color_t=self._pack_th("color", self.color_net),
-                     packed_sem_t=self._pack_th("sem", self.semantics_net))
-        return f
+        return self._nets("h", transposed)
 
     def _field(self, transposed: bool = False):
-        f = dict(grid=self.encoder.grid, table=self.encoder.params.detach(),
-                 packed_sigma=self._pack("sigma", self.sigma_net),
-                 packed_color=self._pack("color", self.color_net),
-                 packed_sem=self._pack("sem", self.semantics_net))
-        if transposed:
-            f.update(packed_sigma_t=self._pack_t("sigma", self.sigma_net),
-                     packed_color_t=self._pack_t("color", self.color_net),
-                     packed_sem_t=self._pack_t("sem", self.semantics_net))
-        return f
+        return self._nets("f32", transposed)
 
     def _render_fn(self):
         def call(net, o, d, nrm, aabb, T, t, rng_t, rng_u, min_near):

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -21,6 +22,27 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+
+
+class Arithmetic(NamedTuple):
+    """What a ``precision`` selects.  The ops are NAMES, looked up in ``ops`` at
+    the call, so that replacing ``ops.NAME`` (lab tools, tests) still takes."""
+    form: str           # pack form of the three nets (SemanticNeRFNetwork._nets)
+    half_table: bool    # read the hash grid from the fp16 copy of the table
+    sigma_mlp: str      # ops.sigma_mlp_fwd*
+    render: str         # ops.render_fwd*: one chunk of run()
+    view: str           # mode of ops.render_view: all chunks as one call
+
+
+# keyed by ``precision``; ``fp16_table`` selects "fp16_h16" (see __init__ for what
+# each arithmetic is)
+PRECISIONS = {
+    "fp32": Arithmetic("f32", False, "sigma_mlp_fwd", "render_fwd", "fp32"),
+    "fp16": Arithmetic("h", False, "sigma_mlp_fwd_f16", "render_fwd_f16", "fp16"),
+    "fp16_h16": Arithmetic("h", True, "sigma_mlp_fwd_f16", "render_fwd_f16_h16", "fp16_h16"),
+    "bf16x3": Arithmetic("x3", False, "sigma_mlp_fwd_x3", "render_fwd_x3", "bf16x3"),
+    "f16x2": Arithmetic("h2", False, "sigma_mlp_fwd_h2", "render_fwd_h2", "f16x2"),
+}
 
 
 class SemanticNeRFRenderer(nn.Module):
@@ -359,25 +381,8 @@ class SemanticNeRFRenderer(nn.Module):
             }
         aabb = self._aabb_list(self.training)
         nears, fars = ops.near_far_from_aabb(o, d, aabb, min_near)
-        if self.precision not in ("fp32", "fp16", "bf16x3", "f16x2"):
-            raise ValueError("precision must be fp32, bf16x3, f16x2 or fp16, got "
-                             f"{self.precision}")
-        # (the marcher's fused shading kernel has f32-input, f16 and -- round 6 -- f16x2
-        # nets: with bf16x3 the colour / semantics nets shade in fp32 here; the sigma MLP
-        # of the marched points runs on the 16-bit pipe in the selected arithmetic --
-        # round 6: it used to fall back to the f32-input MFMA, 0.33 instead of 0.21 ms
-        # per 5.9 M points)
-        fused = schedule == "segments" and fused_shade
-        half = self.precision == "fp16" and fused
-        f = self._field_f16() if half else self._field()
-        sigma_mlp = ops.sigma_mlp_fwd_f16 if half else ops.sigma_mlp_fwd
-        shade_mode, shade_nets = half, f
-        if not half and self.precision in ("bf16x3", "f16x2"):
-            fx = self._field_h2() if self.precision == "f16x2" else self._field_x3()
-            fwd = ops.sigma_mlp_fwd_h2 if self.precision == "f16x2" else ops.sigma_mlp_fwd_x3
-            sigma_mlp = lambda feat, _packed, _fx=fx, _fwd=fwd: _fwd(feat, _fx["packed_sigma"])  # noqa: E731
-            if self.precision == "f16x2" and fused:
-                shade_mode, shade_nets = "f16x2", fx
+        f, sigma_mlp, shade_mode, shade_nets = self._march_arith(
+            schedule == "segments" and fused_shade)
         ws = torch.zeros(N, device=device)
         depth = torch.zeros(N, device=device)
         image = torch.zeros(N, 3, device=device)
@@ -402,7 +407,7 @@ class SemanticNeRFRenderer(nn.Module):
                     xyzs, dirs, deltas = seg.write(n_alive, total, jitter)
                     feat = ops.hashgrid_encode_points(f["grid"], f["table"],
                                                       xyzs)
-                    h, sigma = sigma_mlp(feat, f["packed_sigma"])
+                    h, sigma = sigma_mlp(feat)
                     if fused_shade:
                         seg.shade(n_alive, cap, sigma,
                                   float(self.density_scale), h, deltas,
@@ -478,6 +483,46 @@ class SemanticNeRFRenderer(nn.Module):
     # -- hooks supplied by the field (SemanticNeRFNetwork) -------------------
     def _field(self):
         raise NotImplementedError()
+
+    def _nets(self, form: str, transposed: bool = False):
+        raise NotImplementedError()
+
+    def _table_half(self):
+        raise NotImplementedError()
+
+    def _arithmetic(self, fp16_table=None) -> Arithmetic:
+        """The row of PRECISIONS that ``precision`` and ``fp16_table`` select."""
+        if self.precision not in ("fp32", "fp16", "bf16x3", "f16x2"):
+            raise ValueError("precision must be fp32, bf16x3, f16x2 or fp16, got "
+                             f"{self.precision}")
+        half_table = self.fp16_table if fp16_table is None else fp16_table
+        if half_table and self.precision != "fp16":
+            raise ValueError("fp16_table needs precision='fp16' (its encoder emits "
+                             "fp16 features, which only the f16 sigma MLP reads)")
+        return PRECISIONS["fp16_h16" if half_table else self.precision]
+
+    def _march_arith(self, fused: bool):
+        """The marcher's arithmetic -> (field ``f``, sigma MLP of the marched points
+        as a callable of the features, ``shade_mode`` and nets of the fused shading
+        kernel).  That kernel has f32-input, f16 and -- round 6 -- f16x2 nets: with
+        bf16x3 the colour / semantics nets shade in fp32 here; the sigma MLP of the
+        marched points runs on the 16-bit pipe in the selected arithmetic -- round
+        6: it used to fall back to the f32-input MFMA, 0.33 instead of 0.21 ms per
+        5.9 M points.  fp16 nets run only with the fused kernel, everything else is
+        fp32 then.  The marcher always reads the fp32 table."""
+        row = self._arithmetic(fp16_table=False)
+        if self.precision == "fp16" and not fused:
+            row = PRECISIONS["fp32"]
+        half = row.form == "h"
+        f = self._nets("h") if half else self._field()
+        sigma_nets = f if row.form in ("h", "f32") else self._nets(row.form)
+        shade_mode, shade_nets = half, f
+        if row.form == "h2" and fused:
+            shade_mode, shade_nets = "f16x2", sigma_nets
+
+        def sigma_mlp(feat):
+            return getattr(ops, row.sigma_mlp)(feat, sigma_nets["packed_sigma"])
+        return f, sigma_mlp, shade_mode, shade_nets
 
     def _aabb_list(self, training: bool):
         key = bool(training)
@@ -592,25 +637,12 @@ class SemanticNeRFRenderer(nn.Module):
 
     def _run_infer(self, o, d, nrm, aabb, T, t, rng_t, rng_u, min_near,
                    image_width=0):
-        if self.precision not in ("fp32", "fp16", "bf16x3", "f16x2"):
-            raise ValueError("precision must be fp32, bf16x3, f16x2 or fp16, got "
-                             f"{self.precision}")
-        if self.fp16_table and self.precision != "fp16":
-            raise ValueError("fp16_table needs precision='fp16' (its encoder emits "
-                             "fp16 features, which only the f16 sigma MLP reads)")
-        if self.precision == "fp16":
-            f, render = self._field_f16(), ops.render_fwd_f16
-            if self.fp16_table:
-                f = dict(f, table=self._table_half())
-                render = ops.render_fwd_f16_h16
-        elif self.precision == "bf16x3":
-            f, render = self._field_x3(), ops.render_fwd_x3
-        elif self.precision == "f16x2":
-            f, render = self._field_h2(), ops.render_fwd_h2
-            if self._h2_guard_mode() == "full":
-                self._h2_check_activations(o, d, aabb, T, min_near)
-        else:
-            f, render = self._field(), ops.render_fwd
+        row = self._arithmetic()
+        f = self._nets(row.form)
+        if row.half_table:
+            f["table"] = self._table_half()
+        if row.form == "h2" and self._h2_guard_mode() == "full":
+            self._h2_check_activations(o, d, aabb, T, min_near)
         N = o.shape[0]
         C = self.num_semantic_classes
         dev = o.device
@@ -622,11 +654,9 @@ class SemanticNeRFRenderer(nn.Module):
         if self.hip_pipeline and n_chunks >= 2 and int(self.hip_streams) <= 1:
             # ONE call for the whole batch: density half of chunk k+1 next to
             # the shading half of chunk k (ucsa_render_view; bit-identical)
-            mode = {"fp32": "fp32", "bf16x3": "bf16x3", "f16x2": "f16x2"}.get(
-                self.precision, "fp16_h16" if self.fp16_table else "fp16")
             ws = self._workspace(
                 ops.render_workspace_bytes(min(N, chunk), T, t, f["grid"].n_levels), dev, 2)
-            ops.render_view(mode, f["grid"], f["table"], f["packed_sigma"],
+            ops.render_view(row.view, f["grid"], f["table"], f["packed_sigma"],
                             f["packed_color"], f["packed_sem"], o, d, nrm, aabb, min_near,
                             rng_t, rng_u, T, t, C, float(self.density_scale), image, depth,
                             sem, chunk, ws[0], ws[1], image_width)
@@ -646,6 +676,7 @@ class SemanticNeRFRenderer(nn.Module):
                 st.wait_stream(main)  # inputs / packed weights are ready
         else:
             streams = [main]
+        render = getattr(ops, row.render)
         for k, head in enumerate(range(0, N, chunk)):
             tail = min(head + chunk, N)
             with torch.cuda.stream(streams[k % n_str]):

@@ -11,17 +11,12 @@ import torch
 from .. import _lib
 from .._lib import Grid, check, fvec, lib
 from ._args import _f32, _ptr, _raw_current_stream, _scratch_named, _stream
+from .render import _mlp_pack
 
 
 def mlp_pack_t(kind: int, params: torch.Tensor, n_classes: int = 0,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    params = _f32(params.detach(), "params")
-    n = int(lib().ucsa_mlp_pack_t_size(kind, n_classes))
-    if out is None:
-        out = torch.empty(n, device=params.device)
-    check(lib().ucsa_mlp_pack_t(kind, _ptr(params), _ptr(out), n_classes,
-                                _stream()), "ucsa_mlp_pack_t")
-    return out
+    return _mlp_pack("ucsa_mlp_pack_t", kind, params, n_classes, out, "ucsa_mlp_pack_t_size")
 
 
 def reduce_partials(partial: torch.Tensor, grad: torch.Tensor,
@@ -283,25 +278,15 @@ def hashgrid_bwd_points(grid: Grid, x, d_feat, grad_table, binned: bool = True):
 
 def mlp_pack_t_f16(kind: int, params: torch.Tensor, n_classes: int = 0,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    params = _f32(params.detach(), "params")
-    n = int(lib().ucsa_mlp_pack_t_f16_halves(kind, n_classes))
-    if out is None:
-        out = torch.empty(n, dtype=torch.float16, device=params.device)
-    check(lib().ucsa_mlp_pack_t_f16(kind, _ptr(params), _ptr(out), n_classes,
-                                    _stream()), "ucsa_mlp_pack_t_f16")
-    return out
+    return _mlp_pack("ucsa_mlp_pack_t_f16", kind, params, n_classes, out,
+                     "ucsa_mlp_pack_t_f16_halves", 1, torch.float16)
 
 
 def mlp_pack_t_x3(kind: int, params: torch.Tensor, n_classes: int = 0,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Transposed weight fragments (dX = W^T dY) as three bf16 terms."""
-    params = _f32(params.detach(), "params")
-    n = int(lib().ucsa_mlp_pack_t_x3_bytes(kind, n_classes))
-    if out is None:
-        out = torch.empty(n // 2, dtype=torch.bfloat16, device=params.device)
-    check(lib().ucsa_mlp_pack_t_x3(kind, _ptr(params), _ptr(out), n_classes,
-                                   _stream()), "ucsa_mlp_pack_t_x3")
-    return out
+    return _mlp_pack("ucsa_mlp_pack_t_x3", kind, params, n_classes, out,
+                     "ucsa_mlp_pack_t_x3_bytes", 2, torch.bfloat16)
 
 
 def shade_bwd_split() -> bool:

@@ -230,25 +230,40 @@ def hashgrid_encode_points(grid: Grid, table, x):
     return feat
 
 
+def _mlp_pack(symbol: str, kind: int, params, n_classes: int, out, size: str = "",
+              per: int = 1, dtype=torch.float32, extra=()):
+    """One launch of the library's pack ``symbol``.  ``out`` None: a new buffer of
+    ``size``(kind, n_classes) // ``per`` elements of ``dtype`` (no ``size``: like
+    ``params``).  ``extra``: arguments between n_classes and the stream."""
+    params = _f32(params.detach(), "params")
+    if out is None and not size:
+        out = torch.empty_like(params)
+    elif out is None:
+        n = int(getattr(lib(), size)(kind, n_classes)) // per
+        out = torch.empty(n, dtype=dtype, device=params.device)
+    check(getattr(lib(), symbol)(kind, _ptr(params), _ptr(out), n_classes, *extra,
+                                 _stream()), symbol)
+    return out
+
+
 def mlp_pack(kind: int, params: torch.Tensor, n_classes: int = 0,
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    params = _f32(params.detach(), "params")
-    if out is None:
-        out = torch.empty_like(params)
-    check(lib().ucsa_mlp_pack(kind, _ptr(params), _ptr(out), n_classes,
-                              _stream()), "ucsa_mlp_pack")
-    return out
+    return _mlp_pack("ucsa_mlp_pack", kind, params, n_classes, out)
+
+
+def _sigma_mlp_fwd(symbol: str, feat, packed_sigma):
+    """feat [L,M,2] -> h [M,16], sigma [M] through the library's ``symbol``."""
+    L, M, _ = feat.shape
+    h = torch.empty(M, 16, device=feat.device)
+    sigma = torch.empty(M, device=feat.device)
+    check(getattr(lib(), symbol)(_ptr(feat), _ptr(packed_sigma), M, L, _ptr(h),
+                                 _ptr(sigma), _stream()), symbol)
+    return h, sigma
 
 
 def sigma_mlp_fwd(feat, packed_sigma) -> Tuple[torch.Tensor, torch.Tensor]:
     """feat [L,M,2] -> h [M,16], sigma [M]."""
-    L, M, _ = feat.shape
-    h = torch.empty(M, 16, device=feat.device)
-    sigma = torch.empty(M, device=feat.device)
-    check(lib().ucsa_sigma_mlp_fwd(_ptr(feat), _ptr(packed_sigma), M, L,
-                                   _ptr(h), _ptr(sigma), _stream()),
-          "ucsa_sigma_mlp_fwd")
-    return h, sigma
+    return _sigma_mlp_fwd("ucsa_sigma_mlp_fwd", feat, packed_sigma)
 
 
 def resample(z, sigma, u, density_scale: float = 1.0):
@@ -270,18 +285,24 @@ def resample(z, sigma, u, density_scale: float = 1.0):
     return new_z
 
 
-def composite_fwd(rays_d, norms, z_c, sigma_c, h_c, z_f, sigma_f, h_f,
-                  packed_color, packed_sem, n_classes: int,
-                  density_scale: float = 1.0, want_aux: bool = False,
-                  half: bool = False):
+def _composite_frame(rays_d, norms, z_c, z_f, n_classes: int):
+    """What the composite forwards share: checked rays, the sizes and the three
+    outputs -> (rays_d, norms, N, T, t, dev, image, depth, sem)."""
     rays_d = _f32(rays_d, "rays_d").view(-1, 3)
     norms = _f32(norms, "norms").view(-1)
     N, T = z_c.shape
     t = 0 if z_f is None else z_f.shape[1]
     dev = z_c.device
-    image = torch.empty(N, 3, device=dev)
-    depth = torch.empty(N, device=dev)
-    sem = torch.empty(N, n_classes, device=dev)
+    return (rays_d, norms, N, T, t, dev, torch.empty(N, 3, device=dev),
+            torch.empty(N, device=dev), torch.empty(N, n_classes, device=dev))
+
+
+def composite_fwd(rays_d, norms, z_c, sigma_c, h_c, z_f, sigma_f, h_f,
+                  packed_color, packed_sem, n_classes: int,
+                  density_scale: float = 1.0, want_aux: bool = False,
+                  half: bool = False):
+    rays_d, norms, N, T, t, dev, image, depth, sem = _composite_frame(
+        rays_d, norms, z_c, z_f, n_classes)
     src = torch.empty(N, T + t, dtype=torch.int32, device=dev) if want_aux else None
     w = torch.empty(N, T + t, device=dev) if want_aux else None
     fn = lib().ucsa_composite_fwd_f16 if half else lib().ucsa_composite_fwd
@@ -301,14 +322,8 @@ def composite_train_fwd_x3(rays_d, norms, z_c, sigma_c, h_c, z_f, sigma_f, h_f,
     """Training forward of the colour / semantics stage on the split pair with
     the bf16x3 nets -> (image, depth, sem, src, w) like
     composite_fwd(want_aux=True)."""
-    rays_d = _f32(rays_d, "rays_d").view(-1, 3)
-    norms = _f32(norms, "norms").view(-1)
-    N, T = z_c.shape
-    t = 0 if z_f is None else z_f.shape[1]
-    dev = z_c.device
-    image = torch.empty(N, 3, device=dev)
-    depth = torch.empty(N, device=dev)
-    sem = torch.empty(N, n_classes, device=dev)
+    rays_d, norms, N, T, t, dev, image, depth, sem = _composite_frame(
+        rays_d, norms, z_c, z_f, n_classes)
     src = torch.empty(N, T + t, dtype=torch.int32, device=dev)
     w = torch.empty(N, T + t, device=dev)
     ws = _scratch_named("composite_infer",
@@ -332,14 +347,8 @@ def composite_infer(rays_d, norms, z_c, sigma_c, h_c, z_f, sigma_f, h_f,
     from mlp_pack_f16.  x3=True: bf16x3 nets (fp32-grade, weights from
     mlp_pack_x3; not bit-identical to the f32-input MFMA); h2=True: f16x2
     nets (mlp_pack_h2)."""
-    rays_d = _f32(rays_d, "rays_d").view(-1, 3)
-    norms = _f32(norms, "norms").view(-1)
-    N, T = z_c.shape
-    t = 0 if z_f is None else z_f.shape[1]
-    dev = z_c.device
-    image = torch.empty(N, 3, device=dev)
-    depth = torch.empty(N, device=dev)
-    sem = torch.empty(N, n_classes, device=dev)
+    rays_d, norms, N, T, t, dev, image, depth, sem = _composite_frame(
+        rays_d, norms, z_c, z_f, n_classes)
     ws = _scratch_named("composite_infer",
                         int(lib().ucsa_composite_infer_workspace_bytes(N, T, t)),
                         dev)
@@ -391,47 +400,44 @@ def render_workspace_bytes(N: int, T: int, t: int, n_levels: int) -> int:
     return int(lib().ucsa_render_workspace_bytes(N, T, t, n_levels))
 
 
+def _render_fwd(symbol: str, grid: Grid, table, packed_sigma, packed_color, packed_sem,
+                rays_o, rays_d, norms, aabb, min_near, t_rand, u, T, t, n_classes,
+                density_scale, image, depth, semantics, ws, image_width):
+    """One chunk of run() through the library's ``symbol``; the packs are the
+    ones that arithmetic reads."""
+    N = rays_o.shape[0]
+    check(getattr(lib(), symbol)(
+        C.byref(grid), _ptr(table), _ptr(packed_sigma), _ptr(packed_color),
+        _ptr(packed_sem), _ptr(rays_o), _ptr(rays_d), _ptr(norms), fvec(aabb),
+        float(min_near), _ptr(t_rand), _ptr(u), N, T, t, n_classes,
+        float(density_scale), int(image_width), _ptr(image), _ptr(depth),
+        _ptr(semantics), _ptr(ws), _stream()), symbol)
+
+
 def render_fwd(grid: Grid, table, packed_sigma, packed_color, packed_sem,
                rays_o, rays_d, norms, aabb, min_near: float, t_rand, u, T: int,
                t: int, n_classes: int, density_scale: float, image, depth,
                semantics, ws: torch.Tensor, image_width: int = 0):
     """All tensors already validated/contiguous; outputs written in place.
     image_width > 0: the rays are the pixels of full image rows."""
-    N = rays_o.shape[0]
-    check(lib().ucsa_render_fwd(C.byref(grid), _ptr(table), _ptr(packed_sigma),
-                                _ptr(packed_color), _ptr(packed_sem),
-                                _ptr(rays_o), _ptr(rays_d), _ptr(norms),
-                                fvec(aabb), float(min_near), _ptr(t_rand),
-                                _ptr(u), N, T, t, n_classes,
-                                float(density_scale), int(image_width),
-                                _ptr(image), _ptr(depth), _ptr(semantics),
-                                _ptr(ws), _stream()),
-          "ucsa_render_fwd")
+    _render_fwd("ucsa_render_fwd", grid, table, packed_sigma, packed_color, packed_sem,
+                rays_o, rays_d, norms, aabb, min_near, t_rand, u, T, t, n_classes,
+                density_scale, image, depth, semantics, ws, image_width)
 
 
 # ======================= fp16-MFMA inference option =========================
 def mlp_pack_f16(kind: int, params: torch.Tensor, n_classes: int = 0,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    params = _f32(params.detach(), "params")
-    n = int(lib().ucsa_mlp_pack_f16_halves(kind, n_classes))
-    if out is None:
-        out = torch.empty(n, dtype=torch.float16, device=params.device)
-    check(lib().ucsa_mlp_pack_f16(kind, _ptr(params), _ptr(out), n_classes,
-                                  _stream()), "ucsa_mlp_pack_f16")
-    return out
+    return _mlp_pack("ucsa_mlp_pack_f16", kind, params, n_classes, out,
+                     "ucsa_mlp_pack_f16_halves", 1, torch.float16)
 
 
 def mlp_pack_x3(kind: int, params: torch.Tensor, n_classes: int = 0,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Weights as three bf16 terms per value in MFMA fragment order
     (csrc/mfma_mlp_x3.h)."""
-    params = _f32(params.detach(), "params")
-    n = int(lib().ucsa_mlp_pack_x3_bytes(kind, n_classes))
-    if out is None:
-        out = torch.empty(n // 2, dtype=torch.bfloat16, device=params.device)
-    check(lib().ucsa_mlp_pack_x3(kind, _ptr(params), _ptr(out), n_classes,
-                                 _stream()), "ucsa_mlp_pack_x3")
-    return out
+    return _mlp_pack("ucsa_mlp_pack_x3", kind, params, n_classes, out,
+                     "ucsa_mlp_pack_x3_bytes", 2, torch.bfloat16)
 
 
 def mlp_pack_h2(kind: int, params: torch.Tensor, n_classes: int = 0,
@@ -443,30 +449,17 @@ def mlp_pack_h2(kind: int, params: torch.Tensor, n_classes: int = 0,
     pinned host or device memory, zeroed by the caller) accumulates the largest
     |value| converted to f16 as an fp32 bit pattern; ``scratch``: int32 [2] on
     the device, zeroed once (ucsa_mlp_pack_h2_checked)."""
-    params = _f32(params.detach(), "params")
-    n = int(lib().ucsa_mlp_pack_h2_bytes(kind, n_classes))
-    if out is None:
-        out = torch.empty(n // 2, dtype=torch.float16, device=params.device)
-    if range_bits is not None:
-        if scratch is None or not scratch.is_cuda or scratch.numel() < 2:
-            raise _lib.UcsaError("mlp_pack_h2: range_bits needs a 2-word int32 device scratch")
-        check(lib().ucsa_mlp_pack_h2_checked(kind, _ptr(params), _ptr(out), n_classes,
-                                             _ptr(range_bits), _ptr(scratch), _stream()),
-              "ucsa_mlp_pack_h2_checked")
-        return out
-    check(lib().ucsa_mlp_pack_h2(kind, _ptr(params), _ptr(out), n_classes,
-                                 _stream()), "ucsa_mlp_pack_h2")
-    return out
+    size = ("ucsa_mlp_pack_h2_bytes", 2, torch.float16)
+    if range_bits is None:
+        return _mlp_pack("ucsa_mlp_pack_h2", kind, params, n_classes, out, *size)
+    if scratch is None or not scratch.is_cuda or scratch.numel() < 2:
+        raise _lib.UcsaError("mlp_pack_h2: range_bits needs a 2-word int32 device scratch")
+    return _mlp_pack("ucsa_mlp_pack_h2_checked", kind, params, n_classes, out, *size,
+                     extra=(_ptr(range_bits), _ptr(scratch)))
 
 
 def sigma_mlp_fwd_h2(feat, packed_sigma_h2):
-    L, M, _ = feat.shape
-    h = torch.empty(M, 16, device=feat.device)
-    sigma = torch.empty(M, device=feat.device)
-    check(lib().ucsa_sigma_mlp_fwd_h2(_ptr(feat), _ptr(packed_sigma_h2), M, L,
-                                      _ptr(h), _ptr(sigma), _stream()),
-          "ucsa_sigma_mlp_fwd_h2")
-    return h, sigma
+    return _sigma_mlp_fwd("ucsa_sigma_mlp_fwd_h2", feat, packed_sigma_h2)
 
 
 def render_fwd_h2(grid: Grid, table, packed_sigma_h2, packed_color_h2,
@@ -476,28 +469,15 @@ def render_fwd_h2(grid: Grid, table, packed_sigma_h2, packed_color_h2,
                   ws: torch.Tensor, image_width: int = 0):
     """run() with the three nets as f16x2 (fp32-grade on the f16 MFMA pipe,
     three passes per product)."""
-    N = rays_o.shape[0]
-    check(lib().ucsa_render_fwd_h2(
-        C.byref(grid), _ptr(table), _ptr(packed_sigma_h2), _ptr(packed_color_h2),
-        _ptr(packed_sem_h2), _ptr(rays_o), _ptr(rays_d), _ptr(norms), fvec(aabb),
-        float(min_near), _ptr(t_rand), _ptr(u), N, T, t, n_classes,
-        float(density_scale), int(image_width), _ptr(image), _ptr(depth),
-        _ptr(semantics), _ptr(ws), _stream()), "ucsa_render_fwd_h2")
+    _render_fwd("ucsa_render_fwd_h2", grid, table, packed_sigma_h2, packed_color_h2,
+                packed_sem_h2, rays_o, rays_d, norms, aabb, min_near, t_rand, u, T, t,
+                n_classes, density_scale, image, depth, semantics, ws, image_width)
 
 
 def sigma_mlp_fwd_f16(feat, packed_sigma_half):
-    L, M, _ = feat.shape
-    h = torch.empty(M, 16, device=feat.device)
-    sigma = torch.empty(M, device=feat.device)
     if feat.dtype == torch.float16:   # features of the fp16-table encoder
-        check(lib().ucsa_sigma_mlp_fwd_f16_h(_ptr(feat), _ptr(packed_sigma_half),
-                                             M, L, _ptr(h), _ptr(sigma),
-                                             _stream()), "ucsa_sigma_mlp_fwd_f16_h")
-        return h, sigma
-    check(lib().ucsa_sigma_mlp_fwd_f16(_ptr(feat), _ptr(packed_sigma_half), M,
-                                       L, _ptr(h), _ptr(sigma), _stream()),
-          "ucsa_sigma_mlp_fwd_f16")
-    return h, sigma
+        return _sigma_mlp_fwd("ucsa_sigma_mlp_fwd_f16_h", feat, packed_sigma_half)
+    return _sigma_mlp_fwd("ucsa_sigma_mlp_fwd_f16", feat, packed_sigma_half)
 
 
 def render_fwd_f16(grid: Grid, table, packed_sigma_h, packed_color_h,
@@ -505,13 +485,9 @@ def render_fwd_f16(grid: Grid, table, packed_sigma_h, packed_color_h,
                    t_rand, u, T: int, t: int, n_classes: int,
                    density_scale: float, image, depth, semantics,
                    ws: torch.Tensor, image_width: int = 0):
-    N = rays_o.shape[0]
-    check(lib().ucsa_render_fwd_f16(
-        C.byref(grid), _ptr(table), _ptr(packed_sigma_h), _ptr(packed_color_h),
-        _ptr(packed_sem_h), _ptr(rays_o), _ptr(rays_d), _ptr(norms), fvec(aabb),
-        float(min_near), _ptr(t_rand), _ptr(u), N, T, t, n_classes,
-        float(density_scale), int(image_width), _ptr(image), _ptr(depth),
-        _ptr(semantics), _ptr(ws), _stream()), "ucsa_render_fwd_f16")
+    _render_fwd("ucsa_render_fwd_f16", grid, table, packed_sigma_h, packed_color_h,
+                packed_sem_h, rays_o, rays_d, norms, aabb, min_near, t_rand, u, T, t,
+                n_classes, density_scale, image, depth, semantics, ws, image_width)
 
 
 def table_to_half(table: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -530,24 +506,14 @@ def render_fwd_f16_h16(grid: Grid, table_half, packed_sigma_h, packed_color_h,
                        density_scale: float, image, depth, semantics,
                        ws: torch.Tensor, image_width: int = 0):
     """render_fwd_f16 reading the fp16 table (table_to_half)."""
-    N = rays_o.shape[0]
     assert table_half.dtype == torch.float16
-    check(lib().ucsa_render_fwd_f16_h16(
-        C.byref(grid), _ptr(table_half), _ptr(packed_sigma_h), _ptr(packed_color_h),
-        _ptr(packed_sem_h), _ptr(rays_o), _ptr(rays_d), _ptr(norms), fvec(aabb),
-        float(min_near), _ptr(t_rand), _ptr(u), N, T, t, n_classes,
-        float(density_scale), int(image_width), _ptr(image), _ptr(depth),
-        _ptr(semantics), _ptr(ws), _stream()), "ucsa_render_fwd_f16_h16")
+    _render_fwd("ucsa_render_fwd_f16_h16", grid, table_half, packed_sigma_h, packed_color_h,
+                packed_sem_h, rays_o, rays_d, norms, aabb, min_near, t_rand, u, T, t,
+                n_classes, density_scale, image, depth, semantics, ws, image_width)
 
 
 def sigma_mlp_fwd_x3(feat, packed_sigma_x3):
-    L, M, _ = feat.shape
-    h = torch.empty(M, 16, device=feat.device)
-    sigma = torch.empty(M, device=feat.device)
-    check(lib().ucsa_sigma_mlp_fwd_x3(_ptr(feat), _ptr(packed_sigma_x3), M, L,
-                                      _ptr(h), _ptr(sigma), _stream()),
-          "ucsa_sigma_mlp_fwd_x3")
-    return h, sigma
+    return _sigma_mlp_fwd("ucsa_sigma_mlp_fwd_x3", feat, packed_sigma_x3)
 
 
 def render_fwd_x3(grid: Grid, table, packed_sigma_x3, packed_color_x3,
@@ -556,13 +522,9 @@ def render_fwd_x3(grid: Grid, table, packed_sigma_x3, packed_color_x3,
                   density_scale: float, image, depth, semantics,
                   ws: torch.Tensor, image_width: int = 0):
     """run() with the three nets as bf16x3 (fp32-grade on the bf16 MFMA pipe)."""
-    N = rays_o.shape[0]
-    check(lib().ucsa_render_fwd_x3(
-        C.byref(grid), _ptr(table), _ptr(packed_sigma_x3), _ptr(packed_color_x3),
-        _ptr(packed_sem_x3), _ptr(rays_o), _ptr(rays_d), _ptr(norms), fvec(aabb),
-        float(min_near), _ptr(t_rand), _ptr(u), N, T, t, n_classes,
-        float(density_scale), int(image_width), _ptr(image), _ptr(depth),
-        _ptr(semantics), _ptr(ws), _stream()), "ucsa_render_fwd_x3")
+    _render_fwd("ucsa_render_fwd_x3", grid, table, packed_sigma_x3, packed_color_x3,
+                packed_sem_x3, rays_o, rays_d, norms, aabb, min_near, t_rand, u, T, t,
+                n_classes, density_scale, image, depth, semantics, ws, image_width)
 
 
 RENDER_MODES = {"fp32": 0, "fp16": 1, "bf16x3": 2, "fp16_h16": 3, "f16x2": 4}
