@@ -2300,6 +2300,83 @@ int32_t ucsa_mesh_tsdf(const float* records, const int32_t* offsets, uint32_t n_
                        const float* vol_origin, const float* vol_spacing, float trunc,
                        float weight_value, void* stream);
 
+/* ---- rays against a triangle mesh (not in the reference) ----
+ * "What does this ray hit on this mesh" and "is this segment free": the query
+ * the visibility-aware 3D scores need, exact where a depth-buffer test through
+ * the rasterizer is pixel-quantised.  tests/raycast_numpy.py states the contract
+ * as plain brute force over all faces and the outputs match it byte for byte,
+ * whatever the cell size, the grid's origin or the order of the rays.
+ * A ray is o, d (float32) with the parameter range [t_min, t_max]; t_max may be
+ * +inf and t_min -inf.  A face counts by the rule of the triangle grid (corner
+ * indices in [0, nv), finite corners A, B, C).  Nothing is fused.
+ *  1. A ray with a non-finite component, or d = 0, hits nothing.
+ *  2. kz = argmax |d| (the first on ties), kx = (kz+1)%3, ky = (kz+2)%3;
+ *     Sx = d[kx]/d[kz], Sy = d[ky]/d[kz] in float32.
+ *  3. Per corner P in float32: px = P[kx]-o[kx], py = P[ky]-o[ky],
+ *     pz = P[kz]-o[kz]; X = px - Sx*pz, Y = py - Sy*pz (the product, then the
+ *     difference).
+ *  4. In float64, on the converted X, Y: U = Cx*By - Cy*Bx, V = Ax*Cy - Ay*Cx,
+ *     W = Bx*Ay - By*Ax.  The products are exact, so the signs are exact and an
+ *     edge shared by two faces gives exactly negated values in the two: the
+ *     watertight test of Woop, Benthin and Wald (2013), its zero-case fallback
+ *     made unconditional.
+ *  5. The face is hit if U, V, W are all >= 0 or all <= 0, and
+ *     det = (U+V)+W != 0.  No back-face culling.
+ *  6. t = (float)(((U*pz_A + V*pz_B) + W*pz_C) / det / (double)d[kz]); t must be
+ *     finite and t_min <= t <= t_max (inclusive; a NaN bound admits nothing).
+ *  7. The box clause.  Per axis a, in float32: p = o[a] + t*d[a];
+ *     mn, mx = the corners' minimum and maximum on that axis;
+ *     S = 2^-20 * ((|o[a]| + |t*d[a]|) + max(|mn|, |mx|)); mn - S <= p <= mx + S
+ *     must hold.  t is a convex sum of the corners' depths and the weights put
+ *     the sheared ray through the sheared face, so p lies in the face's box up
+ *     to the rounding of the shear; the clause turns that into a statement
+ *     about computed numbers, which is what a traversal of the grid (a face is
+ *     registered in the cells of its box) needs to promise every hit.  It
+ *     rejects a hit only where the shear's rounding, about
+ *     2^-22 |S| (the face's reach from o along kz), exceeds S on a minor axis:
+ *     a face that reaches many times farther along the ray's major axis than
+ *     the coordinates on a minor axis are large (docs/DESIGN_NOTEBOOK.md,
+ *     section RC).
+ *  8. The hit with the smallest t wins, among equal t the smallest face index.
+ *     face [n] int32 (-1 on a miss), t [n] float32 (+inf on a miss), bary
+ *     [n][3] float32 = ((float)(U/det), (float)(V/det), (float)(W/det)), the
+ *     weights of A, B, C (a zero row on a miss).
+ * ucsa_mesh_occluded is the any-hit form: occluded [n] uint8, 1 if any face is
+ * hit in the range.
+ *
+ * records, offsets, n_pairs, origin, cell, dims are the grid of
+ * ucsa_nearest_triangle (all finite vertices inside its box).  origins, dirs
+ * [n_rays][3] float32; t_min, t_max [n_rays] float32, or NULL for t_min_all,
+ * t_max_all; order int32 [n_rays], a permutation, or NULL: lane t takes ray
+ * order[t] (an entry outside [0, n_rays) writes nothing) and writes that ray's
+ * slots.  One lane per ray walks the grid's layers along kz in ray order (a
+ * slab supercover): per layer the parameter interval between its walls, the
+ * ray's points at both ends on the two minor axes, and the cells between
+ * them; walls and ranges are grown by 2^-17 * (|o| + |origin| + |origin +
+ * dims*cell|) on their axis.  The walk ends when the best t lies before the
+ * next layer's entry (strictly) or that entry lies past t_max; the any-hit form
+ * ends at its first hit.  Why no hit is lost is argued at the head of
+ * csrc/mesh_raycast.hip.  A face registered in several cells is evaluated more
+ * than once, which does not change a minimum.  Every loop is bounded by dims or
+ * n_pairs; offsets are clamped into [0, n_pairs]; no atomics, no LDS, no lane
+ * waits for another.  The inputs are never modified.
+ * Limits: n_pairs <= 2^31-1 (argument 2), the grid as in ucsa_nearest_triangle
+ * (3..5), n_rays <= 2^31-1 (13), records 16-byte aligned (0).  An argument
+ * error comes before any launch and nothing is written.  n_pairs == 0: every
+ * ray misses (records and offsets may be NULL); n_rays == 0: returns 0,
+ * launches nothing. */
+int32_t ucsa_raycast_mesh(const float* records, const int32_t* offsets, uint32_t n_pairs,
+                          const float* origin, float cell, const uint32_t* dims,
+                          const float* origins, const float* dirs, const float* t_min,
+                          const float* t_max, float t_min_all, float t_max_all,
+                          const int32_t* order, uint32_t n_rays, int32_t* face, float* t,
+                          float* bary, void* stream);
+int32_t ucsa_mesh_occluded(const float* records, const int32_t* offsets, uint32_t n_pairs,
+                           const float* origin, float cell, const uint32_t* dims,
+                           const float* origins, const float* dirs, const float* t_min,
+                           const float* t_max, float t_min_all, float t_max_all,
+                           const int32_t* order, uint32_t n_rays, uint8_t* occluded, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

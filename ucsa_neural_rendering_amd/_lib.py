@@ -389,6 +389,11 @@ SIGNATURES = {
     "ucsa_mesh_tsdf": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _u32,
                                    _p, _u32, _p, _p, _p, _p, _p, _u32, _u32, _u32,
                                    C.POINTER(_f), C.POINTER(_f), _f, _f, _p]),
+    # ---- rays against a triangle mesh (nearest hit, any hit) ----
+    "ucsa_raycast_mesh": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _p,
+                                      _p, _p, _f, _f, _p, _u32, _p, _p, _p, _p]),
+    "ucsa_mesh_occluded": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _p,
+                                       _p, _p, _f, _f, _p, _u32, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

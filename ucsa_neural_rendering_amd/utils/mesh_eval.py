@@ -27,6 +27,14 @@ four corners, and a hole in the middle of it costs what it covers.
 distance threshold: both meshes are voxelized on one lattice
 (``ops.voxelize_mesh``) and the occupied voxel sets are compared.
 
+A scene fused from some of its frames has seen part of the room only.
+``visible_from`` (``mesh_distance``, ``score_labels_3d``) restricts the
+ground-truth side's points to those that at least ``min_views`` of the given
+cameras see (``utils.mesh_raycast.visible_points``: inside the image and the
+depth range, the segment from the camera free of the ground-truth mesh), so
+that completeness, recall and the label score no longer charge for surface no
+camera observed.
+
 All of these are unsigned.  ``mesh_distance(signed=True)`` and ``tsdf_bias`` say
 on which side of the ground-truth surface a mesh or a fused volume lies
 (``ops.signed_distance``, ``ops.mesh_tsdf``): an inflated surface and a deflated
@@ -55,6 +63,22 @@ def _labels(l, n, device):
 def _faces(f, device):
     t = torch.as_tensor(np.asarray(f) if not torch.is_tensor(f) else f)
     return t.to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def _seen(points, gt, gt_faces, visible_from, min_views):
+    """which of ``points`` at least ``min_views`` of the views of ``visible_from``
+    (a dict of poses, intrinsics, H, W, near, far, bias) see, the ground-truth
+    mesh being the occluder -> bool [N] on the device"""
+    from .mesh_raycast import visible_points
+    if gt_faces is None:
+        raise ValueError("visible_from needs gt_faces: the ground-truth mesh is the occluder")
+    try:
+        keys = {k: visible_from[k] for k in ("poses", "intrinsics", "H", "W", "near", "far",
+                                              "bias")}
+    except (TypeError, KeyError):
+        raise ValueError("visible_from must be a dict of poses, intrinsics, H, W, near, far, bias")
+    grid = ops.triangle_grid(gt, _faces(gt_faces, gt.device))
+    return visible_points(grid, points, **keys) >= int(min_views)
 
 
 def sample_surface(verts, faces, density, seed=0, labels=None, samples=None):
@@ -129,7 +153,8 @@ def _score(pred, index, gt_labels, C):
 
 
 def score_labels_3d(pred_verts, pred_labels, gt_verts, gt_labels, max_dist, C=40,
-                    pred_faces=None, gt_faces=None, sample_density=None, seed=0):
+                    pred_faces=None, gt_faces=None, sample_density=None, seed=0,
+                    visible_from=None, min_views=1):
     """The predicted labels at the ground-truth vertices (``transfer_labels``)
     scored through ``score_label_maps``: ground truth 0 or above ``C`` is ignored;
     a prediction of 0, or no predicted vertex within ``max_dist``, counts as
@@ -142,18 +167,35 @@ def score_labels_3d(pred_verts, pred_labels, gt_verts, gt_labels, max_dist, C=40
     from the ground-truth surface (``sample_surface``, ``seed``), each carrying
     the label of its face's nearest corner, and so weighs every class by its
     area; "vertices" is then the number of scored samples and "sampled" the
-    number of samples."""
+    number of samples.
+
+    ``visible_from`` (a dict of poses, intrinsics, H, W, near, far, bias; needs
+    ``gt_faces``, the occluder): only the ground-truth vertices or samples that at
+    least ``min_views`` of those views see (``visible_points``) are scored, and
+    the dict gains "visible": [kept, total]."""
+    if visible_from is not None and gt_faces is None:
+        raise ValueError("visible_from needs gt_faces: the ground-truth mesh is the occluder")
     if sample_density is None:
-        pred, index = transfer_labels(pred_verts, pred_labels, gt_verts, max_dist,
-                                      return_match=True, src_faces=pred_faces)[:2]
-        return _score(pred, index, gt_labels, C)
-    if gt_faces is None:
-        raise ValueError("sample_density needs gt_faces")
-    points, labels, res = sample_surface(gt_verts, gt_faces, sample_density, seed, gt_labels)
+        points, labels = gt_verts, gt_labels
+    else:
+        if gt_faces is None:
+            raise ValueError("sample_density needs gt_faces")
+        points, labels, res = sample_surface(gt_verts, gt_faces, sample_density, seed, gt_labels)
+    visible = None
+    if visible_from is not None:
+        gt = _verts(gt_verts)
+        points = _verts(points, gt.device)
+        labels = _labels(labels, points.shape[0], gt.device)
+        keep = _seen(points, gt, gt_faces, visible_from, min_views)
+        visible = [int(keep.sum()), int(keep.numel())]
+        points, labels = points[keep].contiguous(), labels[keep]
     pred, index = transfer_labels(pred_verts, pred_labels, points, max_dist,
                                   return_match=True, src_faces=pred_faces)[:2]
     out = _score(pred, index, labels, C)
-    out["sampled"] = res["n_samples"]
+    if sample_density is not None:
+        out["sampled"] = res["n_samples"]
+    if visible is not None:
+        out["visible"] = visible
     return out
 
 
@@ -183,7 +225,7 @@ def score_voxel_labels_3d(volume, voxel_labels, gt_verts, gt_labels, max_dist, C
 
 
 def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt_faces=None,
-                  sample_density=None, seed=0, signed=False):
+                  sample_density=None, seed=0, signed=False, visible_from=None, min_views=1):
     """Vertex-to-vertex distances both ways -> {"accuracy": mean pred -> gt,
     "completeness": mean gt -> pred, "chamfer": their mean, "precision": the share
     of pred vertices within ``threshold`` of gt, "recall": the share of gt
@@ -213,9 +255,18 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
     ground-truth faces' (B-A)x(C-A) points to: for a ground truth that is
     counter-clockwise seen from outside, a positive mean is an inflated
     prediction and a negative one a deflated one.  Every other entry is what it
-    is without the keyword."""
+    is without the keyword.
+
+    ``visible_from`` (a dict of poses, intrinsics, H, W, near, far, bias; needs
+    ``gt_faces``, the occluder): the gt -> pred direction (completeness, recall)
+    is measured only from the ground-truth vertices or samples that at least
+    ``min_views`` of those views see (``visible_points``); the dict gains
+    "visible": [kept, total].  The pred -> gt direction still has the whole
+    ground truth as its target."""
     pred = _verts(pred_verts)
     gt = _verts(gt_verts, pred.device)
+    if visible_from is not None and gt_faces is None:
+        raise ValueError("visible_from needs gt_faces: the ground-truth mesh is the occluder")
     if signed and gt_faces is None:
         raise ValueError("mesh_distance: signed needs gt_faces")
     signed_out = {}
@@ -227,6 +278,11 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
         if gt_faces is not None:
             gt_from, _, res = sample_surface(gt, gt_faces, sample_density, seed)
             sampled[1] = res["n_samples"]
+    visible = None
+    if visible_from is not None:
+        keep = _seen(gt_from, gt, gt_faces, visible_from, min_views)
+        visible = [int(keep.sum()), int(keep.numel())]
+        gt_from = gt_from[keep].contiguous()
 
     def one_way(a, b, b_faces, with_sign=False):
         if with_sign:
@@ -267,6 +323,8 @@ def mesh_distance(pred_verts, gt_verts, threshold, max_dist, pred_faces=None, gt
     if sample_density is not None:
         out["sampled"] = sampled
     out.update(signed_out)
+    if visible is not None:
+        out["visible"] = visible
     return out
 
 
