@@ -1036,6 +1036,13 @@ int32_t ucsa_compact_rays(uint32_t n_alive, int32_t* rays_alive,
  *        each sample's weight and ray parameter for the backward.  No early
  *        stop (raymarching.cu:363 is commented out in the reference as well);
  *        spans reaching M are skipped (:338).
+ *   span length: a rays row composites at most 1024 samples (the marcher's
+ *        MAX_STEPS; ucsa_march_rays_train writes no longer span).  A row with
+ *        count > 1024 is DROPPED by both passes exactly like one with
+ *        first + count >= M: its ray's outputs stay zero, its rows of w_out /
+ *        t_out / d_h stay zero, its rows of G are not written, and the spans
+ *        after it are composited as usual.  (The backward keeps one LDS float
+ *        per sample of a span, 1024 per wave.)
  *   bwd: d_image [N,3], d_depth [N] (wrt depth/norms[ray]), d_sem [N,C] ->
  *        d_h [M,16] (slot 0: d/d log-density incl. the trunc_exp backward),
  *        scratch G [M], per-wave dW partials

@@ -590,7 +590,7 @@ k_composite(CmpArgs a) {
       const uint32_t index = (uint32_t)a.rays_alive[(size_t)r * a.alive_stride];
       const uint32_t off = (uint32_t)a.span[(size_t)r * a.span_stride];
       uint32_t c = (uint32_t)a.span[(size_t)r * a.span_stride + 1];
-      if (a.train && off + c >= a.n_points) c = 0;
+      if (a.train && (off + c >= a.n_points || c > MARCH_TRAIN_MAX_SPAN)) c = 0;
       slot_off[i] = off;
       slot_cnt[i] = c;
       slot_idx[i] = index;
@@ -611,10 +611,10 @@ k_composite(CmpArgs a) {
           carry_sd = 0.0f;
     for (uint32_t p0 = p_begin; p0 < p_end; p0 += 64) {
       const uint32_t p = p0 + lane;
-      const bool live = p < p_end;
+      const bool inb = p < p_end;
       // slot of the point: last slot whose first point is <= p
       uint32_t lo = 0, hi = n_slots;
-      const uint32_t pq = live ? p : p_end - 1;
+      const uint32_t pq = inb ? p : p_end - 1;
       while (lo + 1 < hi) {
         const uint32_t mid = (lo + hi) >> 1;
         if (slot_off[mid] <= pq) lo = mid; else hi = mid;
@@ -622,6 +622,9 @@ k_composite(CmpArgs a) {
       const uint32_t si = lo;
       const uint32_t off = slot_off[si], c = slot_cnt[si];
       const uint32_t index = slot_idx[si];
+      // a point past its slot's count lies in a dropped span (training: a span
+      // longer than MARCH_TRAIN_MAX_SPAN in mid-stream): not a sample
+      const bool live = inb && p - off < c;
       const bool head = live && p == off;
       const bool tail = live && p == off + c - 1u;
       const size_t m = live ? p : p_end - 1;

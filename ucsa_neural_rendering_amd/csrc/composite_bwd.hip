@@ -681,7 +681,7 @@ k_shade_bwd(ShadeBwdArgs a) {
         const uint32_t index = (uint32_t)a.rays[3 * (size_t)r];
         const uint32_t offset = (uint32_t)a.rays[3 * (size_t)r + 1];
         uint32_t count = (uint32_t)a.rays[3 * (size_t)r + 2];
-        if (offset + count >= a.n_points) count = 0;
+        if (offset + count >= a.n_points || count > MARCH_TRAIN_MAX_SPAN) count = 0;
         for (uint32_t sbase = 0; sbase < count; sbase += 64) {
           const uint32_t s = sbase + lane;
           const bool in = s < count;
@@ -1062,13 +1062,13 @@ k_march_weights_bwd(const int32_t* __restrict__ rays, uint32_t N, uint32_t M,
                     const float* __restrict__ deltas,
                     const float* __restrict__ w_all, const float* __restrict__ G,
                     float* __restrict__ d_h) {
-  __shared__ float suf_s[MW_WAVES][1024];
+  __shared__ float suf_s[MW_WAVES][MARCH_TRAIN_MAX_SPAN];
   const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint32_t r = blockIdx.x * MW_WAVES + wid;
   if (r >= N) return;
   const uint32_t offset = (uint32_t)rays[3 * (size_t)r + 1];
   const uint32_t count = (uint32_t)rays[3 * (size_t)r + 2];
-  if (count == 0 || offset + count >= M) return;
+  if (count == 0 || offset + count >= M || count > MARCH_TRAIN_MAX_SPAN) return;
   float* suf = suf_s[wid];
   float carry = 0.0f;
   for (uint32_t rb = 0; rb < count; rb += 64) {

@@ -7,6 +7,12 @@
 
 #define ROW_FINE 0x80000000u
 
+// Longest span of a rays [N,3] row that ucsa_march_train_fwd / _bwd composite
+// (the marcher's RM_MAX_STEPS: it writes none longer).  k_march_weights_bwd
+// keeps one LDS float per sample of a span; both passes treat a longer span as
+// dropped, like one that reaches M.
+#define MARCH_TRAIN_MAX_SPAN 1024u
+
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
