@@ -2384,6 +2384,74 @@ int32_t ucsa_mesh_occluded(const float* records, const int32_t* offsets, uint32_
                            const float* t_max, float t_min_all, float t_max_all,
                            const int32_t* order, uint32_t n_rays, uint8_t* occluded, void* stream);
 
+/* ---- registration of points to a triangle mesh (not in the reference) ----
+ * One step of ICP in one call: move the source points by a rigid transform,
+ * find each moved point's closest point on the target mesh, and reduce the
+ * Gauss-Newton normal equations of the step to 29 float64 numbers on the device.
+ * The host solves the 6 x 6 system and composes the transform
+ * (utils/registration.py).  tests/register_numpy.py restates the contract over
+ * the brute-force search of tests/surface_numpy.py and the 29 sums match it byte
+ * for byte, whatever the cell size or the grid's origin.
+ *
+ * records, offsets, n_pairs, origin, cell, dims are the grid of
+ * ucsa_nearest_triangle; verts [nv][3] float32 and faces [nf][3] int32 the mesh
+ * it was built over; unit_normal [nf][3] float32 the output of
+ * ucsa_face_unit_normals; points [n][3] float32; transform 12 float32 on the
+ * host, the rows of [R | t]; mode 0 = point to plane, 1 = point to point;
+ * workspace: float64 on the device for the partial sums, workspace_doubles its
+ * size.  With c_1 = ceil(n / 256) and c_(k+1) = ceil(c_k / 256) it must hold
+ * 29 * (the sum of all c_k > 1) doubles; for n <= 256 that is none and it may be
+ * NULL.  Outputs: sums [29] float64 on the device; face [n] int32 and dist2 [n]
+ * float32, each optional (NULL: not written).
+ * Per point i, everything in float32 and nothing fused unless float64 is named:
+ *  1. q_k = ((R[k][0]*x + R[k][1]*y) + R[k][2]*z) + t[k] for k = 0, 1, 2.
+ *  2. From q runs exactly ucsa_nearest_triangle's search with max_dist: the
+ *     smallest dist2 within max_dist*max_dist (inclusive) wins, among equal ones
+ *     the smallest face index; a non-finite q matches nothing, an invalid face
+ *     matches nothing.  face[i] and dist2[i] receive what ucsa_nearest_triangle
+ *     writes for the query q (-1 and +inf without a match).
+ *  3. On a match the closest-point expressions of the nearest-triangle section
+ *     are evaluated again for (q, face) on the mesh's corners, as in
+ *     ucsa_mesh_sign: the same operands, so the same bits.  p is the closest
+ *     point with the query at the origin (the closest point minus q).
+ *  4. Mode 0 has one row with n = unit_normal[face]; mode 1 three rows with
+ *     n = (1,0,0), (0,1,0), (0,0,1).  Per row r = (n0*p0 + n1*p1) + n2*p2 and
+ *     J = (q1*n2 - q2*n1, q2*n0 - q0*n2, q0*n1 - q1*n0, n0, n1, n2), each of
+ *     the first three a product, a product, then the difference (the products
+ *     with the 0 and 1 of mode 1 are carried out like any other).  This
+ *     linearises q <- q + omega x q + upsilon: the step minimises
+ *     sum (r - J . xi)^2 over xi = (omega, upsilon).
+ *  5. In float64, on the converted floats (the products are exact): the 21
+ *     entries J_a*J_b for a <= b, row-major; the 6 entries J_a*r; r*r; 1.0: 29
+ *     terms.  In mode 1 a point's term is (x's + y's) + z's, the three rows in
+ *     that order, so the last sum counts rows: 3 per matched point.  A point
+ *     without a match contributes +0.0 to all 29, by a select, so that no NaN
+ *     leaks in.
+ *  6. The sum is a fixed tree.  The n rows of terms are padded with rows of +0.0
+ *     to a multiple of 256; every group of 256 consecutive rows is reduced by
+ *     eight levels of adjacent pairs (2j, 2j+1); the group results are rows
+ *     again, padded and reduced the same way, until one row is left: sums.  At
+ *     least one stage always runs, so n == 0 gives 29 times +0.0 and a lone
+ *     -0.0 term gives +0.0.  No atomics; the result depends on the order of the
+ *     points only through this tree and is the same bytes every run.
+ * One lane per point in work-groups of 256 (k_icp_sums), then a lane per group
+ * result (k_icp_reduce) while more than one row is left: at most four launches.
+ * Every lane of a work-group reaches its one barrier; every loop is bounded as
+ * in ucsa_nearest_triangle; no lane waits for another outside the barrier.
+ * Cost: that of the search.  The inputs are never modified.
+ * Limits: n_pairs <= 2^31-1 (argument 2), the grid as in ucsa_nearest_triangle
+ * (3..5), nv, nf, n <= 2^31-1 (7, 9, 12), max_dist > 0 with a finite float32
+ * square (14), mode 0 or 1 (15), the workspace (16, 17), records 16-byte aligned
+ * (0).  An argument error comes before any launch and nothing is written.
+ * n_pairs == 0 or nf == 0: no point matches (records and offsets may be NULL),
+ * sums is 29 times +0.0. */
+int32_t ucsa_icp_sums(const float* records, const int32_t* offsets, uint32_t n_pairs,
+                      const float* origin, float cell, const uint32_t* dims, const float* verts,
+                      uint32_t nv, const int32_t* faces, uint32_t nf, const float* unit_normal,
+                      const float* points, uint32_t n, const float* transform, float max_dist,
+                      int32_t mode, double* workspace, uint64_t workspace_doubles, double* sums,
+                      int32_t* face, float* dist2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,9 @@ and the geometry as accuracy, completeness, chamfer and F-score.
         [--gt_transform T.txt] [--num_classes C] [--surface] [--signed] \\
         [--sample_density D [--sample_seed S]] \\
         [--visible_from SCENE_ROOT [--visible_every N] [--visible_bias 0.01] \\
-         [--visible_far F] [--visible_min_views K]]
+         [--visible_far F] [--visible_min_views K]] \\
+        [--register [--register_max_dist M] [--register_iters N] \\
+         [--register_mode {plane,point}] [--register_samples N]]
 
 Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
 read a mesh in the frame of the JSON poses in metres (what the export and fusion
@@ -57,6 +59,16 @@ line of sight up to ``--visible_bias`` before the point
 (``utils.mesh_raycast.visible_points``).  A scene fused from part of its frames
 is then not charged for surface no camera observed.  Both lines carry a
 ``"visible"`` entry: ``[kept, total]`` ground-truth points.
+``--register`` (needs faces in the ground truth) aligns the prediction to the
+ground truth before any score: ICP of the predicted vertices -- or, with
+``--register_samples N``, of about N area-uniform samples of the predicted
+surface -- against the ground-truth surface
+(``utils.registration.register_meshes``), from the frames as loaded: a local
+refinement within ``--register_max_dist`` (default 0.5), not a search for a
+coarse alignment.  The predicted vertices are moved by the result, and one
+``register: {...}`` line carries the 4 x 4 ``transform``, ``rmse``, the
+``matched`` share of the source points, ``rank`` (below 6: the ground truth
+did not constrain the motion) and ``iterations``.
 Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
 import argparse
 import json
@@ -103,7 +115,45 @@ def parse_args(argv=None):
     p.add_argument("--visible_far", type=float, default=float("inf"),
                    help="the largest z-depth a camera sees, scene units")
     p.add_argument("--visible_min_views", type=int, default=1)
+    p.add_argument("--register", action="store_true",
+                   help="align the prediction to the ground-truth surface (ICP) before any score")
+    p.add_argument("--register_max_dist", type=float, default=0.5,
+                   help="the matching radius of the alignment, scene units")
+    p.add_argument("--register_iters", type=int, default=30)
+    p.add_argument("--register_mode", choices=("plane", "point"), default="plane")
+    p.add_argument("--register_samples", type=int, default=None, metavar="N",
+                   help="align about N area-uniform samples of the predicted surface, not its "
+                        "vertices")
     return p.parse_args(argv)
+
+
+def register(a, pred, gv, gt_faces):
+    """--register: move ``pred``'s vertices onto the ground-truth surface -> the
+    ``register:`` record"""
+    from ucsa_neural_rendering_amd.utils.registration import register_meshes
+    if gt_faces is None or not len(gt_faces):
+        raise SystemExit("--register needs faces in the ground-truth mesh")
+    if not (a.register_max_dist > 0 and a.register_iters >= 1):
+        raise SystemExit("--register_max_dist must be > 0 and --register_iters >= 1")
+    density = None
+    if a.register_samples is not None:
+        if a.register_samples < 1 or pred["faces"] is None or not len(pred["faces"]):
+            raise SystemExit("--register_samples must be >= 1 and needs faces in the prediction")
+        tri = pred["verts"][pred["faces"]].astype(np.float64)
+        area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]),
+                                    axis=1).sum()
+        if not area > 0:
+            raise SystemExit("--register_samples: the predicted surface has no area")
+        density = a.register_samples / area
+    out = register_meshes(pred, {"verts": gv, "faces": gt_faces}, sample_density=density,
+                          seed=a.sample_seed, max_dist=a.register_max_dist,
+                          iterations=a.register_iters, mode=a.register_mode)
+    T = out["transform"]
+    pred["verts"] = (pred["verts"].astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    return {"transform": [[float(x) for x in row] for row in T], "rmse": out["rmse"],
+            "matched": out["matched"] / max(out["n_points"], 1), "rank": out["rank"],
+            "iterations": out["iterations"], "converged": out["converged"],
+            "mode": a.register_mode, "points": out["n_points"]}
 
 
 def main(argv=None):
@@ -117,6 +167,9 @@ def main(argv=None):
         T = np.loadtxt(a.gt_transform, dtype=np.float64).reshape(4, 4)
         gv = (gv.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
     rec = {}
+    if a.register:
+        rec["register"] = register(a, pred, gv, gt["faces"])
+        print("register: " + json.dumps(rec["register"]))
     pf, gf = (pred["faces"], gt["faces"]) if a.surface else (None, None)
     if a.surface and (pf is None or gf is None or not len(pf) or not len(gf)):
         raise SystemExit("--surface needs faces in both meshes")

@@ -394,6 +394,10 @@ SIGNATURES = {
                                       _p, _p, _f, _f, _p, _u32, _p, _p, _p, _p]),
     "ucsa_mesh_occluded": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _p,
                                        _p, _p, _f, _f, _p, _u32, _p, _p]),
+    # ---- registration of points to a triangle mesh (one ICP step's normal equations) ----
+    "ucsa_icp_sums": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _u32, _p,
+                                  _u32, _p, _p, _u32, C.POINTER(_f), _f, C.c_int32, _p,
+                                  C.c_uint64, _p, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,254 @@
+// One step of ICP against a triangle mesh (not in the reference): ucsa_icp_sums.
+// The contract is stated in include/ucsa_hip.h; tests/register_numpy.py restates
+// it over the brute-force search of tests/surface_numpy.py and the 29 sums match
+// it byte for byte.
+//
+// k_icp_sums<MODE>  a lane per point in work-groups of 256: the point is moved by
+//                   [R | t], the nearest-triangle search of triangle_grid.hip
+//                   (pg_walk over FaceWalk with TG_KS) runs from the moved point,
+//                   the closest point of the face found is evaluated again on the
+//                   mesh's own corners (tri_closest.h: the same operands, the same
+//                   bits, as in mesh_sdf.hip), and the rows (J, r) follow.  Only
+//                   then are the 29 float64 terms formed, one after another from
+//                   those floats, each reduced over the work-group at once: no
+//                   term is live across the walk.  The work-group's 29 sums go to
+//                   its row of the workspace (or to `sums` if it is the only one).
+// k_icp_reduce      a lane per row of the previous stage, 256 rows per
+//                   work-group, the same reduction: repeated until one row is left.
+//
+// The reduction is the contract's tree of adjacent pairs.  Inside a wave six
+// exchange steps pair lane l with l^1, l^2, a lane of the neighbouring quad, a
+// lane of the neighbouring half row, l^16 and l^32: after step k every lane of
+// an aligned group of 2^k lanes holds the sum of that group's balanced tree
+// (a + b is commutative in IEEE, so both partners compute the same bits), and
+// any lane of the partner group will do as the source.  The first four steps
+// are DPP moves of the two halves of the double (quad_perm, row_half_mirror,
+// row_mirror: no LDS), the last two are __shfl_xor.  The four waves meet in LDS
+// as (w0 + w1) + (w2 + w3): levels seven and eight.  A lane without a point
+// (i >= n, no match) holds +0.0, which is the contract's padding.
+//
+// No atomics.  One barrier per work-group, which every lane reaches: a lane with
+// i >= n takes the unmatched path and does not return early.  Every loop is
+// bounded as in pg_walk (cell_grid.h); no lane waits for another outside that
+// barrier.  A lane writes its own slots of face / dist2, a work-group its own row
+// of the workspace; every index read from memory is checked before use.
+#include "tri_closest.h"
+
+namespace {
+
+constexpr uint32_t ICP_SUMS = 29;
+
+struct Rigid {
+  float m[12];  // the rows of [R | t]
+};
+
+template <int CTRL>
+__device__ __forceinline__ double icp_dpp(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
+// the balanced tree of adjacent pairs over the wave's 64 values, in every lane
+__device__ __forceinline__ double icp_wave_tree(double v) {
+  v = v + icp_dpp<0xB1>(v);   // quad_perm:[1,0,3,2]: l ^ 1
+  v = v + icp_dpp<0x4E>(v);   // quad_perm:[2,3,0,1]: l ^ 2
+  v = v + icp_dpp<0x141>(v);  // row_half_mirror: l -> 7 - l, the other quad of the eight
+  v = v + icp_dpp<0x140>(v);  // row_mirror: l -> 15 - l, the other eight of the row
+  v = v + __shfl_xor(v, 16, 64);
+  v = v + __shfl_xor(v, 32, 64);
+  return v;
+}
+
+// one of the 29 sums over the work-group: `sh` is [ICP_SUMS][4]
+__device__ __forceinline__ void icp_put(double v, uint32_t c, double* sh) {
+  v = icp_wave_tree(v);
+  if ((threadIdx.x & 63u) == 0u) sh[4u * c + (threadIdx.x >> 6)] = v;
+}
+
+__device__ __forceinline__ void icp_finish(const double* sh, double* __restrict__ out) {
+  __syncthreads();
+  const uint32_t c = threadIdx.x;
+  if (c < ICP_SUMS)
+    out[(uint64_t)blockIdx.x * ICP_SUMS + c] = (sh[4u * c] + sh[4u * c + 1u]) + (sh[4u * c + 2u] + sh[4u * c + 3u]);
+}
+
+// the row k of one normal: J, r and the row's 1, each entry of J a product, then the difference
+template <int ROWS>
+__device__ __forceinline__ void icp_row(float q0, float q1, float q2, float p0, float p1, float p2,
+                                        float n0, float n1, float n2, float (*V)[ROWS], int k) {
+  V[0][k] = q1 * n2 - q2 * n1;
+  V[1][k] = q2 * n0 - q0 * n2;
+  V[2][k] = q0 * n1 - q1 * n0;
+  V[3][k] = n0;
+  V[4][k] = n1;
+  V[5][k] = n2;
+  V[6][k] = tg_dot(n0, n1, n2, p0, p1, p2);
+  V[7][k] = 1.0f;
+}
+
+// a point's term of one sum: the products of the converted floats are exact in
+// float64; the rows' terms are added in order; no match is a select of +0.0
+template <int ROWS>
+__device__ __forceinline__ double icp_term(bool matched, const float* x, const float* y) {
+  double t = (double)x[0] * (double)y[0];
+  if constexpr (ROWS == 3)
+    t = (t + (double)x[1] * (double)y[1]) + (double)x[2] * (double)y[2];
+  return matched ? t : 0.0;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(PG_THREADS) k_icp_sums(const float4* __restrict__ rec,
+                                                         const int32_t* __restrict__ offsets,
+                                                         uint32_t n_pairs, GridArgs g,
+                                                         const float* __restrict__ verts,
+                                                         uint32_t nv,
+                                                         const int32_t* __restrict__ faces,
+                                                         uint32_t nf,
+                                                         const float* __restrict__ unit,
+                                                         const float* __restrict__ points,
+                                                         uint32_t n, Rigid T, float limit2,
+                                                         double* __restrict__ out,
+                                                         int32_t* __restrict__ face,
+                                                         float* __restrict__ dist2) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  constexpr int ROWS = MODE == 0 ? 1 : 3;
+  const uint32_t i = blockIdx.x * PG_THREADS + threadIdx.x;  // < 2^31 + 256
+  const bool live = i < n;
+  FaceWalk w;
+  w.rec = rec;
+  w.qx = w.qy = w.qz = NAN;  // no point, or no candidates: no ring is walked
+  if (live) {
+    const float x = points[3ull * i], y = points[3ull * i + 1u], z = points[3ull * i + 2u];
+    w.qx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    w.qy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    w.qz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+  }
+  w.best = limit2;
+  w.bidx = PG_NONE;
+  w.v = 0.0f;
+  w.w = 0.0f;
+  if (live && n_pairs != 0u) pg_walk(offsets, n_pairs, g, TG_KS, limit2, w);
+  const bool hit = w.bidx != PG_NONE;
+  if (live) {
+    if (face) face[i] = hit ? (int32_t)w.bidx : -1;
+    if (dist2) dist2[i] = hit ? w.best : INFINITY;
+  }
+  float V[8][ROWS];  // per row: J (0..5), r (6) and 1 (7)
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) V[a][k] = 0.0f;
+  }
+  bool matched = false;
+  if (hit && w.bidx < nf) {  // a record that names no face matches nothing
+    const Corners c = tg_corners(verts, nv, faces, w.bidx);
+    if (c.ok) {
+      matched = true;
+      const float4 A = make_float4(c.ax, c.ay, c.az, 0.0f), B = make_float4(c.bx, c.by, c.bz, 0.0f),
+                   C = make_float4(c.cx, c.cy, c.cz, 0.0f);
+      float v, wt, d2, px, py, pz;
+      int region;
+      tg_closest_point(A, B, C, w.qx, w.qy, w.qz, v, wt, d2, region, px, py, pz);
+      if constexpr (ROWS == 1) {
+        const float* nn = unit + 3ull * w.bidx;
+        icp_row<ROWS>(w.qx, w.qy, w.qz, px, py, pz, nn[0], nn[1], nn[2], V, 0);
+      } else {
+        icp_row<ROWS>(w.qx, w.qy, w.qz, px, py, pz, 1.0f, 0.0f, 0.0f, V, 0);
+        icp_row<ROWS>(w.qx, w.qy, w.qz, px, py, pz, 0.0f, 1.0f, 0.0f, V, 1);
+        icp_row<ROWS>(w.qx, w.qy, w.qz, px, py, pz, 0.0f, 0.0f, 1.0f, V, 2);
+      }
+    }
+  }
+  uint32_t col = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int b = a; b < 6; ++b) icp_put(icp_term<ROWS>(matched, V[a], V[b]), col++, sh);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) icp_put(icp_term<ROWS>(matched, V[a], V[6]), col++, sh);
+  icp_put(icp_term<ROWS>(matched, V[6], V[6]), col++, sh);
+  icp_put(icp_term<ROWS>(matched, V[7], V[7]), col++, sh);  // the rows that count
+  icp_finish(sh, out);
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_icp_reduce(const double* __restrict__ in,
+                                                           uint32_t count,
+                                                           double* __restrict__ out) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  const uint32_t row = blockIdx.x * PG_THREADS + threadIdx.x;
+  const bool live = row < count;
+#pragma unroll 1
+  for (uint32_t c = 0; c < ICP_SUMS; ++c)
+    icp_put(live ? in[(uint64_t)row * ICP_SUMS + c] : 0.0, c, sh);
+  icp_finish(sh, out);
+}
+
+// the rows of all stages but the last: what the workspace holds, in 29 doubles each
+uint64_t icp_workspace_rows(uint32_t n) {
+  uint64_t rows = 0;
+  uint32_t c = n ? ucsa_div_up(n, PG_THREADS) : 1u;
+  while (c > 1u) {
+    rows += c;
+    c = ucsa_div_up(c, PG_THREADS);
+  }
+  return rows;
+}
+
+}  // namespace
+
+extern "C" int32_t ucsa_icp_sums(const float* records, const int32_t* offsets, uint32_t n_pairs,
+                                 const float* origin, float cell, const uint32_t* dims,
+                                 const float* verts, uint32_t nv, const int32_t* faces,
+                                 uint32_t nf, const float* unit_normal, const float* points,
+                                 uint32_t n, const float* transform, float max_dist, int32_t mode,
+                                 double* workspace, uint64_t workspace_doubles, double* sums,
+                                 int32_t* face, float* dist2, void* stream) {
+  UCSA_CHECK_ARG(n_pairs <= 0x7FFFFFFFu, 2);
+  GridArgs g;
+  const int bad = pg_grid_args(origin, cell, dims, g);
+  UCSA_CHECK_ARG(bad != 1, 3);
+  UCSA_CHECK_ARG(bad != 2, 4);
+  UCSA_CHECK_ARG(bad != 3, 5);
+  UCSA_CHECK_ARG(nv <= 0x7FFFFFFFu, 7);
+  UCSA_CHECK_ARG(nf <= 0x7FFFFFFFu, 9);
+  UCSA_CHECK_ARG(nv == 0 || verts, 6);
+  UCSA_CHECK_ARG(nf == 0 || faces, 8);
+  UCSA_CHECK_ARG(nf == 0 || unit_normal, 10);
+  UCSA_CHECK_ARG(n <= 0x7FFFFFFFu, 12);
+  UCSA_CHECK_ARG(n == 0 || points, 11);
+  UCSA_CHECK_ARG(transform, 13);
+  const float limit2 = max_dist * max_dist;
+  UCSA_CHECK_ARG(max_dist > 0.0f && pg_host_finite(max_dist) && pg_host_finite(limit2), 14);
+  UCSA_CHECK_ARG(mode == 0 || mode == 1, 15);
+  const uint64_t ws_rows = icp_workspace_rows(n);
+  UCSA_CHECK_ARG(ws_rows == 0 || workspace, 16);
+  UCSA_CHECK_ARG(workspace_doubles >= ws_rows * ICP_SUMS, 17);
+  UCSA_CHECK_ARG(sums, 18);
+  UCSA_CHECK_ARG(n_pairs == 0 || (records && ((uintptr_t)records & 15u) == 0), 0);
+  UCSA_CHECK_ARG(n_pairs == 0 || offsets, 1);
+  Rigid T;
+  for (int k = 0; k < 12; ++k) T.m[k] = transform[k];
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t count = n ? ucsa_div_up(n, PG_THREADS) : 1u;  // at least one stage: n == 0 gives +0.0
+  double* out = count == 1u ? sums : workspace;
+  UCSA_CLEAR_ERR();
+  if (mode == 0)
+    hipLaunchKernelGGL(k_icp_sums<0>, dim3(count), dim3(PG_THREADS), 0, s, (const float4*)records,
+                       offsets, n_pairs, g, verts, nv, faces, nf, unit_normal, points, n, T, limit2,
+                       out, face, dist2);
+  else
+    hipLaunchKernelGGL(k_icp_sums<1>, dim3(count), dim3(PG_THREADS), 0, s, (const float4*)records,
+                       offsets, n_pairs, g, verts, nv, faces, nf, unit_normal, points, n, T, limit2,
+                       out, face, dist2);
+  // count shrinks by 256 per pass: at most three passes for n < 2^31
+  while (count > 1u) {
+    const uint32_t next = ucsa_div_up(count, PG_THREADS);
+    const double* in = out;
+    out = next == 1u ? sums : out + (uint64_t)count * ICP_SUMS;
+    hipLaunchKernelGGL(k_icp_reduce, dim3(next), dim3(PG_THREADS), 0, s, in, count, out);
+    count = next;
+  }
+  return ucsa_launch_status();
+}

@@ -1,0 +1,126 @@
+"""Registration of points to a triangle mesh: the fused step of ICP over the
+grid of ``ops.triangle_grid``.  Reached as ``ops.register.icp_sums``."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from .. import _lib
+from .._lib import check, fvec, lib
+from ._args import _gpu, _mesh, _points3, _positive, _ptr, _stream
+
+ICP_SUMS = 29
+MODES = {"plane": 0, "point": 1}
+
+
+def workspace_rows(n: int) -> int:
+    """the rows of 29 doubles ``ucsa_icp_sums`` keeps between its reduce stages"""
+    rows, c = 0, max(1, -(-int(n) // 256))
+    while c > 1:
+        rows += c
+        c = -(-c // 256)
+    return rows
+
+
+def _transform12(transform):
+    """a 3x4 or 4x4 array-like on the host -> the 12 floats of its first three rows"""
+    try:
+        t = torch.as_tensor(transform, dtype=torch.float64, device="cpu")
+    except (TypeError, ValueError, RuntimeError):
+        raise _lib.UcsaError(f"transform must be a 3x4 or 4x4 array on the host, got "
+                             f"{type(transform).__name__}")
+    if tuple(t.shape) not in ((3, 4), (4, 4)):
+        raise _lib.UcsaError(f"transform must be 3x4 or 4x4, got {tuple(t.shape)}")
+    return fvec(t[:3].to(torch.float32).reshape(-1).tolist())
+
+
+def face_unit_normals(verts, faces):
+    """The unit normals of a mesh's faces -> float32 [F,3] on its device: the
+    ``unit_normal`` of ``ops.mesh_pseudonormals`` without the vertex and edge
+    sums (ucsa_face_unit_normals: zeros for a degenerate or invalid face)."""
+    v, f = _mesh(verts, faces)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    unit = torch.zeros((nf, 3), dtype=torch.float32, device=v.device)
+    check(lib().ucsa_face_unit_normals(_ptr(v) if nv else None, nv, _ptr(f) if nf else None, nf,
+                                       _ptr(unit) if nf else None, _stream()),
+          "ucsa_face_unit_normals")
+    return unit
+
+
+def cell_order(grid, points, transform):
+    """The order that sorts ``points`` [N,3] by the cell of ``grid`` their moved
+    position q = R p + t falls in (ties by index) -> int32 [N] on the device.
+    The move is elementwise torch and the keys are ucsa_point_cell_keys, as for
+    the queries of ``nearest_triangle``: it orders lanes and changes no result
+    but, through the summation tree of ``icp_sums``, last bits."""
+    pts = _points3(points, "points")
+    n = int(pts.shape[0])
+    T = torch.as_tensor(transform, dtype=torch.float64)[:3].to(torch.float32).to(pts.device)
+    q = pts[:, 0:1] * T[:, 0] + pts[:, 1:2] * T[:, 1] + pts[:, 2:3] * T[:, 2] + T[:, 3]
+    q = q.contiguous()
+    try:
+        origin, cell, dims = grid["origin"], float(grid["cell"]), grid["dims"]
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("grid must be the dict of ops.triangle_grid")
+    keys = torch.empty(n, dtype=torch.int32, device=pts.device)
+    if n:
+        check(lib().ucsa_point_cell_keys(_ptr(q), n, fvec(origin), cell,
+                                         (C.c_uint32 * 3)(*[int(d) for d in dims]), 0, _ptr(keys),
+                                         _stream()), "ucsa_point_cell_keys")
+    return torch.sort(keys, stable=True).indices.to(torch.int32)
+
+
+def icp_sums(grid, verts, faces, unit_normal, points, transform, max_dist: float,
+             mode: str = "plane", return_matches: bool = False):
+    """The normal equations of one ICP step of ``points`` [N,3] (float32 on the
+    GPU) against the mesh ``verts`` / ``faces`` -> ``sums`` float64 [29] on the
+    device, or (``sums``, ``face`` int32 [N], ``dist2`` float32 [N]) with
+    ``return_matches``.  One call moves every point by ``transform`` (a 3x4 or
+    4x4 array-like on the host, converted to float32: q = R p + t), finds q's
+    closest point on the mesh within ``max_dist`` -- ``nearest_triangle``'s
+    search, whose ``face`` and ``dist2`` for q the matches are -- and sums over
+    the matched points, in float64 and in a fixed tree, the 21 entries of the
+    upper triangle of J^T J (row-major), the 6 of J^T r, r^2 and 1 (the count).
+    ``mode`` "plane": one row per point, r the distance to the closest point
+    along the face's unit normal n, J = (q x n, n); "point": three rows, n the
+    axes.  ``grid`` is ``triangle_grid``'s dict of the same mesh and
+    ``unit_normal`` [F,3] float32 the ``unit_normal`` of ``mesh_pseudonormals``
+    (ucsa_face_unit_normals).  The points are taken in the order given: the sums
+    are defined on it and no sort happens here.  ``utils.registration`` turns
+    the sums into a step.  Contract of ucsa_icp_sums (include/ucsa_hip.h)."""
+    v, f = _mesh(verts, faces)
+    dev = v.device
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    pts = _points3(points, "points")
+    if pts.device != dev:
+        raise _lib.UcsaError(f"the mesh is on {dev}, the points on {pts.device}")
+    n = int(pts.shape[0])
+    un = _gpu(unit_normal, "unit_normal (a different mesh?)", torch.float32, (nf, 3), device=dev)
+    try:
+        rec, offsets, P = grid["records"], grid["offsets"], int(grid["n_pairs"])
+        origin, cell, dims, grid_faces = grid["origin"], float(grid["cell"]), grid["dims"], \
+            int(grid["n_faces"])
+    except (TypeError, KeyError):
+        raise _lib.UcsaError("grid must be the dict of ops.triangle_grid")
+    ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
+    _gpu(rec, "grid: records", torch.float32, (P, 12), device=dev, fixed=True)
+    _gpu(offsets, "grid: offsets", torch.int32, numel=ncells + 1, device=dev, fixed=True)
+    if grid_faces != nf:
+        raise _lib.UcsaError(f"grid was built over {grid_faces} faces, the mesh has {nf}")
+    max_dist = _positive(max_dist, "max_dist")
+    if mode not in MODES:
+        raise _lib.UcsaError(f"mode must be 'plane' or 'point', got {mode!r}")
+    t12 = _transform12(transform)
+    ws_doubles = ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev) if return_matches else None
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    check(lib().ucsa_icp_sums(
+        _ptr(rec) if P else None, _ptr(offsets) if P else None, P, fvec(origin), cell,
+        (C.c_uint32 * 3)(*[int(d) for d in dims]), _ptr(v) if nv else None, nv,
+        _ptr(f) if nf else None, nf, _ptr(un) if nf else None, _ptr(pts) if n else None, n, t12,
+        max_dist, MODES[mode], _ptr(ws), ws_doubles, _ptr(sums), _ptr(face), _ptr(dist2),
+        _stream()), "ucsa_icp_sums")
+    return (sums, face, dist2) if return_matches else sums

@@ -1,0 +1,275 @@
+"""Rigid registration of points to a triangle mesh: iterated closest point over
+``ops.register.icp_sums``.
+
+One iteration is one fused launch on the device (transform, closest point on the
+mesh, the Gauss-Newton normal equations as 29 float64 sums in a fixed tree), one
+read of those 29 doubles and a 6 x 6 solve on the host.  The host half
+(``normal_equations``, ``solve_step``, ``compose``) is plain numpy float64 and
+needs no GPU; ``register_points`` and what sits on it do.
+
+The step: with q the moved point, p the vector from q to its closest point and
+n the row's normal (the face's unit normal in mode "plane", the three axes in
+mode "point"), r = n . p and J = (q x n, n) linearise the move
+q <- q + omega x q + upsilon, and the step minimises sum (r - J . xi)^2 over
+xi = (omega, upsilon): (sum J^T J) xi = sum J^T r.
+
+Both uses go through ``register_points``: mesh to mesh (``register_meshes``: align
+a fused or exported mesh to the ground truth before it is scored) and depth
+frame to mesh (``refine_pose``: the points are back-projected in the camera frame
+and the initial transform is the camera pose, so the result is a refined pose).
+
+Not here: scale, rejection of matches on open boundaries, normal compatibility
+gates, robust kernels beyond the ``max_dist`` schedule, global (coarse)
+alignment: the start must lie within ``max_dist`` and a few degrees of the
+answer."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+SUMS = 29
+_PAIRS = [(a, b) for a in range(6) for b in range(a, 6)]
+
+
+# ---------------------------------------------------------------------------
+# the host half: numpy float64, no GPU
+# ---------------------------------------------------------------------------
+def normal_equations(sums):
+    """``icp_sums``' 29 doubles -> (``A`` [6,6] = sum J^T J, ``b`` [6] = sum J^T r,
+    ``sse`` = sum r^2, ``count`` = the rows summed: the matched points in mode
+    "plane", three times as many in mode "point")."""
+    s = np.asarray(sums, np.float64).reshape(-1)
+    if s.size != SUMS:
+        raise ValueError(f"sums must have {SUMS} entries, got {s.size}")
+    A = np.zeros((6, 6), np.float64)
+    for k, (a, b) in enumerate(_PAIRS):
+        A[a, b] = A[b, a] = s[k]
+    return A, s[21:27].copy(), float(s[27]), float(s[28])
+
+
+def solve_step(sums, rcond: float = 1e-8):
+    """The Gauss-Newton step of one iteration -> (``xi`` [6] = (omega, upsilon),
+    ``rank``).  The rule: the rotation columns are divided by a characteristic
+    length L = sqrt(trace(A[:3,:3]) / trace(A[3:,3:])) -- the rms lever arm of the
+    rows, 1 if either trace is not positive -- so that rotation and translation
+    eigenvalues are comparable; the scaled matrix is decomposed by a symmetric
+    eigen-decomposition; eigen-directions whose eigenvalue is at most ``rcond``
+    times the largest are dropped, and the step has no component along them
+    (they stay at zero: a plane leaves its two in-plane shifts and the spin
+    about its normal free); the rest is solved exactly and scaled back.
+    ``rank`` is the number of directions kept; < 6 says the target does not
+    constrain the pose."""
+    A, b, _, _ = normal_equations(sums)
+    tr_rot, tr_trans = float(np.trace(A[:3, :3])), float(np.trace(A[3:, 3:]))
+    L = math.sqrt(tr_rot / tr_trans) if tr_rot > 0.0 and tr_trans > 0.0 else 1.0
+    if not (L > 0.0 and math.isfinite(L)):
+        L = 1.0
+    s = np.array([1.0 / L] * 3 + [1.0] * 3)
+    As, bs = A * s[:, None] * s[None, :], b * s
+    if not (np.isfinite(As).all() and np.isfinite(bs).all()):
+        return np.zeros(6), 0
+    w, U = np.linalg.eigh(As)
+    top = float(w[-1])
+    if not top > 0.0:
+        return np.zeros(6), 0
+    keep = w > float(rcond) * top
+    eta = (U[:, keep] * ((U[:, keep].T @ bs) / w[keep])[None, :]).sum(1)
+    return eta * s, int(keep.sum())
+
+
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def compose(T, xi):
+    """``exp(xi) . T`` -> 4x4 float64: the step applied on the left of ``T`` (3x4
+    or 4x4).  exp is the exponential of se(3): with theta = |omega| and
+    K = [omega]x, R = I + (sin theta / theta) K + ((1 - cos theta) / theta^2) K^2
+    (Rodrigues) and t = (I + ((1 - cos theta) / theta^2) K +
+    ((theta - sin theta) / theta^3) K^2) upsilon; below theta = 1e-6 the three
+    coefficients are their series 1 - theta^2/6, 1/2 - theta^2/24 and
+    1/6 - theta^2/120.  ``xi`` = 0 returns ``T`` unchanged, to the bit."""
+    T = np.asarray(T, np.float64)
+    out = np.eye(4)
+    out[:T.shape[0]] = T
+    xi = np.asarray(xi, np.float64).reshape(6)
+    if not xi.any():
+        return out
+    w, u = xi[:3], xi[3:]
+    th2 = float(w @ w)
+    th = math.sqrt(th2)
+    if th < 1e-6:
+        a, b, c = 1.0 - th2 / 6.0, 0.5 - th2 / 24.0, 1.0 / 6.0 - th2 / 120.0
+    else:
+        a, b, c = math.sin(th) / th, (1.0 - math.cos(th)) / th2, (th - math.sin(th)) / (th2 * th)
+    K = _hat(w)
+    K2 = K @ K
+    R = np.eye(3) + a * K + b * K2
+    V = np.eye(3) + b * K + c * K2
+    new = np.eye(4)
+    new[:3, :3] = R @ out[:3, :3]
+    new[:3, 3] = R @ out[:3, 3] + V @ u
+    return new
+
+
+def rotation_angle(R):
+    """the angle of a rotation matrix (radians), accurate near 0"""
+    R = np.asarray(R, np.float64)
+    s = 0.5 * math.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2
+                        + (R[1, 0] - R[0, 1]) ** 2)
+    return math.atan2(s, 0.5 * (float(np.trace(R)) - 1.0))
+
+
+# ---------------------------------------------------------------------------
+# the loop (GPU)
+# ---------------------------------------------------------------------------
+def _on_device(x, dtype, cols, device):
+    import torch
+    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    return t.to(device=device, dtype=dtype).reshape(-1, cols).contiguous()
+
+
+def register_points(points, verts, faces, init=None, max_dist: float = 0.5, iterations: int = 30,
+                    mode: str = "plane", max_dist_schedule=None, tol_rot: float = 1e-6,
+                    tol_trans: float = 1e-6, grid=None, sort_points: bool = True,
+                    rcond: float = 1e-8, device="cuda"):
+    """Align ``points`` [N,3] to the mesh ``verts`` / ``faces`` -> dict:
+    ``transform`` (4x4 float64: points -> mesh frame), ``rmse`` (sqrt of the mean
+    squared residual over the matched points at the last evaluated transform:
+    along the normal in mode "plane", the distance in mode "point"), ``matched``
+    (points with a closest point within ``max_dist`` there), ``rank`` (of the last
+    solve; < 6: the target did not constrain the pose, the free directions were
+    left alone and the result is still returned), ``iterations`` (solves done),
+    ``converged`` (a step with |omega| <= ``tol_rot`` and |upsilon| <=
+    ``tol_trans`` ended the loop) and ``history`` (per iteration a dict:
+    ``matched``, ``rmse``, ``omega``, ``upsilon`` -- the step's norms -- and
+    ``max_dist``, and ``sums``, the 29 doubles; the statistics are those of the
+    transform the iteration started from).  The default tolerances (radians,
+    scene units) sit a few float32 spacings of a room-sized coordinate above
+    the floor the float32 search leaves.  ``init`` (3x4 or 4x4, default the
+    identity) is where the loop starts; ``max_dist_schedule`` gives the ``max_dist`` of iteration k as its
+    entry min(k, len - 1), a coarse-to-fine gate.  The triangle grid (``grid``:
+    ``ops.triangle_grid``'s dict of the mesh, built here when None) and the unit
+    normals are made once.  ``sort_points`` orders the points once by the cell
+    of their initially moved position, so that a wave's lanes walk the same
+    cells: it changes time and, through the summation tree, last bits only.
+    Each iteration is ``ops.register.icp_sums``, one read of 29 doubles,
+    ``solve_step`` and ``compose``.  Arrays may be numpy or torch; they are moved
+    to ``device``."""
+    import torch
+
+    from .. import ops
+    v = _on_device(verts, torch.float32, 3, device)
+    f = _on_device(faces, torch.int32, 3, device)
+    pts = _on_device(points, torch.float32, 3, v.device)
+    if grid is None:
+        grid = ops.triangle_grid(v, f)
+    unit = ops.register.face_unit_normals(v, f)
+    T = compose(np.eye(4) if init is None else np.asarray(init, np.float64), np.zeros(6))
+    if sort_points and pts.shape[0]:
+        pts = pts[ops.register.cell_order(grid, pts, T).long()].contiguous()
+    rows = 3.0 if mode == "point" else 1.0
+    schedule = [float(max_dist)] if max_dist_schedule is None else \
+        [float(m) for m in max_dist_schedule]
+    history, rank, converged, done = [], 0, False, 0
+    for k in range(int(iterations)):
+        md = schedule[min(k, len(schedule) - 1)]
+        sums = ops.register.icp_sums(grid, v, f, unit, pts, T, md, mode).cpu().numpy()
+        _, _, sse, count = normal_equations(sums)
+        xi, rank = solve_step(sums, rcond)
+        T = compose(T, xi)
+        done = k + 1
+        om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
+        history.append({"matched": int(round(count / rows)),
+                        "rmse": math.sqrt(sse * rows / count) if count > 0 else float("nan"),
+                        "omega": om, "upsilon": up, "max_dist": md, "sums": sums})
+        if count > 0 and om <= tol_rot and up <= tol_trans:
+            converged = True
+            break
+    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
+    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
+            "iterations": done, "converged": converged, "history": history,
+            "n_points": int(pts.shape[0])}
+
+
+def _mesh_arrays(mesh):
+    return np.asarray(mesh["verts"], np.float32).reshape(-1, 3), \
+        np.asarray(mesh["faces"], np.int32).reshape(-1, 3)
+
+
+def register_meshes(src_mesh, dst_mesh, sample_density=None, seed: int = 0, device="cuda", **kw):
+    """Align the mesh ``src_mesh`` to ``dst_mesh`` (``load_mesh``'s dicts: ``verts``,
+    ``faces``) -> ``register_points``' dict; ``transform`` moves the source's
+    vertices into the target's frame.  The source points are the source's
+    vertices, or with ``sample_density`` (samples per unit area)
+    ``ops.sample_mesh_surface``'s area-uniform samples with ``seed``."""
+    import torch
+
+    from .. import ops
+    sv, sf = _mesh_arrays(src_mesh)
+    dv, df = _mesh_arrays(dst_mesh)
+    if sample_density is None:
+        pts = sv
+    else:
+        s = ops.sample_mesh_surface(torch.as_tensor(sv).to(device),
+                                    torch.as_tensor(sf).to(device), float(sample_density),
+                                    seed=int(seed))
+        pts = s["points"]
+    return register_points(pts, dv, df, device=device, **kw)
+
+
+def backproject(depth, intrinsics, stride: int = 1, depth_min: float = 0.0,
+                depth_max: float = math.inf):
+    """The valid pixels of a z-depth image [H,W] (a torch tensor) as points in the
+    camera frame -> float32 [N,3] on its device, row-major pixel order.  Pixel
+    (row i, column j) with depth z is ((j + 0.5 - cx) z / fx, (i + 0.5 - cy) z / fy,
+    z): the centre convention of ``ops.get_rays`` and the camera of
+    ``ops.integrate_tsdf`` (looking along +z).  Valid: finite, > 0 and within
+    [``depth_min``, ``depth_max``]; every ``stride``-th row and column."""
+    import torch
+    fx, fy, cx, cy = [float(x) for x in intrinsics]
+    d = depth.float()
+    H, W = int(d.shape[0]), int(d.shape[1])
+    ii = torch.arange(0, H, int(stride), device=d.device)
+    jj = torch.arange(0, W, int(stride), device=d.device)
+    z = d[ii][:, jj]
+    x = ((jj.float() + 0.5 - cx) / fx)[None, :] * z
+    y = ((ii.float() + 0.5 - cy) / fy)[:, None] * z
+    ok = torch.isfinite(z) & (z > 0) & (z >= float(depth_min)) & (z <= float(depth_max))
+    return torch.stack([x, y, z], -1)[ok].contiguous()
+
+
+def refine_pose(depth, pose, intrinsics, grid_or_mesh, stride: int = 1, depth_min: float = 0.0,
+                depth_max: float = math.inf, **kw):
+    """Refine the camera-to-world ``pose`` (4x4) of one z-depth frame ``depth``
+    [H,W] against a mesh -> ``register_points``' dict with ``pose`` (4x4 float64,
+    the refined camera-to-world pose; the same matrix as ``transform``).  The
+    valid pixels are back-projected into the camera frame (``backproject``; pose
+    and ``intrinsics`` (fx, fy, cx, cy) as ``ops.integrate_tsdf`` takes them) and
+    registered with ``init=pose``.  ``grid_or_mesh``: a mesh dict (``verts``,
+    ``faces``), optionally carrying ``grid`` (``ops.triangle_grid``'s dict of it)
+    so that a sequence of frames builds it once."""
+    import torch
+    device = kw.pop("device", "cuda")
+    d = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth, np.float32))
+    pts = backproject(d.to(device), intrinsics, stride, depth_min, depth_max)
+    out = register_points(pts, grid_or_mesh["verts"], grid_or_mesh["faces"], init=pose,
+                          grid=grid_or_mesh.get("grid"), device=device, **kw)
+    out["pose"] = out["transform"]
+    return out
+
+
+def refine_poses(depths, poses, intrinsics, grid_or_mesh, **kw):
+    """``refine_pose`` frame by frame -> list of its dicts.  The triangle grid is
+    built once."""
+    import torch
+
+    from .. import ops
+    device = kw.get("device", "cuda")
+    mesh = dict(grid_or_mesh)
+    if mesh.get("grid") is None:
+        mesh["verts"] = _on_device(mesh["verts"], torch.float32, 3, device)
+        mesh["faces"] = _on_device(mesh["faces"], torch.int32, 3, device)
+        mesh["grid"] = ops.triangle_grid(mesh["verts"], mesh["faces"])
+    return [refine_pose(d, p, intrinsics, mesh, **kw) for d, p in zip(depths, poses)]
