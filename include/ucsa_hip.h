@@ -2452,6 +2452,67 @@ int32_t ucsa_icp_sums(const float* records, const int32_t* offsets, uint32_t n_p
                       int32_t mode, double* workspace, uint64_t workspace_doubles, double* sums,
                       int32_t* face, float* dist2, void* stream);
 
+/* ---- registration of points to a TSDF volume (not in the reference) ----
+ * The tracking half of KinectFusion as one step: move the points by a rigid
+ * transform, sample the volume's signed distance and its gradient at each moved
+ * point (one trilinear cell: sixteen loads), and reduce the point-to-plane
+ * normal equations to the 29 float64 numbers of ucsa_icp_sums, mode 0, in the
+ * same order and the same tree, so that utils/registration.py's solve_step and
+ * compose take them unchanged.  No mesh, no grid, no search.
+ * tests/tsdf_register_numpy.py restates the contract; sums, value and matched
+ * equal it byte for byte.
+ *
+ * tsdf, weight: the state and lattice of ucsa_tsdf_integrate, float32
+ * [nx][ny][nz], tsdf in units of trunc; lattice point (i,j,k) sits at
+ * origin + (i,j,k)*spacing and is stored at (i*ny+j)*nz+k.  origin3, spacing3,
+ * transform (12 float32, the rows of [R | t]) are read on the host.  points
+ * [n][3] float32.  workspace, workspace_doubles and sums as for ucsa_icp_sums.
+ * value [n] float32 and matched [n] uint8 are optional (NULL: not written).
+ * Per point i < n, in float32, every operation as written, nothing fused,
+ * division and sqrt correctly rounded:
+ *  1. q_k = ((R[k][0]*x + R[k][1]*y) + R[k][2]*z) + t[k], as ucsa_icp_sums.
+ *  2. g_a = (q_a - origin_a) / spacing_a.  inside iff on every axis
+ *     g_a >= 0 && g_a <= (float)(n_a - 1); a NaN fails.  Nothing is converted
+ *     to an integer and no index is formed before inside holds; a point outside
+ *     the lattice is unmatched, not clamped into it (ucsa_tsdf_raycast clamps).
+ *  3. fl_a = min(floorf(g_a), (float)(n_a - 2)), c_a = (uint32_t)fl_a,
+ *     f_a = g_a - fl_a: exact, in [0, 1]; g_a = n_a - 1 is the last cell at
+ *     f_a = 1.  v[4i+2j+k] are the cell's eight corners (c0+i, c1+j, c2+k), of
+ *     both arrays, in ucsa_tsdf_raycast's order.
+ *  4. observed iff all eight weights >= min_weight (ucsa_tsdf_raycast's rule).
+ *  5. With lerp(x, y, f) = x + f*(y - x): c00 = lerp(v0, v1, f2),
+ *     c01 = lerp(v2, v3, f2), c10 = lerp(v4, v5, f2), c11 = lerp(v6, v7, f2),
+ *     c0 = lerp(c00, c01, f1), c1 = lerp(c10, c11, f1), F = lerp(c0, c1, f0);
+ *     G0 = c1 - c0, G1 = lerp(c01 - c00, c11 - c10, f0),
+ *     G2 = lerp(lerp(v1 - v0, v3 - v2, f1), lerp(v5 - v4, v7 - v6, f1), f0),
+ *     each divided by spacing_a; ln = sqrt((G0*G0 + G1*G1) + G2*G2),
+ *     n_a = G_a / ln: the value and the normal of ucsa_tsdf_raycast at a hit.
+ *  6. matched iff inside && observed && ln > 0 && ln finite &&
+ *     fabsf(F) <= max_tsdf (a NaN fails).  Free space in front of a surface
+ *     (eight corners at 1) has a zero gradient and never matches.
+ *  7. r = -(F * trunc), J = (q1*n2 - q2*n1, q2*n0 - q0*n2, q0*n1 - q1*n0, n0, n1,
+ *     n2).  n points toward free space and the surface point is
+ *     q - F*trunc*n, so r has the sign of ucsa_icp_sums' n.(c - q).
+ *  8. The 29 float64 terms and their tree are items 5 and 6 of ucsa_icp_sums in
+ *     mode 0: +0.0 by a select for an unmatched row, 256 rows per group, eight
+ *     levels of adjacent pairs, repeated on the group results; n == 0 gives 29
+ *     times +0.0.
+ *  9. value[i] = F where inside && observed, NaN otherwise; matched[i] is 0 or 1.
+ * One lane per point in work-groups of 256 (k_tsdf_icp_sums), then
+ * k_icp_reduce while more than one row is left.  Every lane reaches the one
+ * barrier; no atomics; the same bytes every run.  The inputs are never modified.
+ * Limits: tsdf, weight not NULL (0, 1); nx, ny, nz >= 2 and nx*ny*nz <= 2^31-1
+ * (2, 3, 4); origin finite (5); spacing finite and > 0 (6); n <= 2^31-1 (8),
+ * points not NULL unless n == 0 (7); transform (9); trunc > 0 and finite (10);
+ * min_weight > 0 (11); 0 < max_tsdf <= 1 (12); the workspace (13, 14); sums
+ * (15).  An argument error comes before any launch and nothing is written. */
+int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, uint32_t ny,
+                           uint32_t nz, const float* origin3, const float* spacing3,
+                           const float* points, uint32_t n, const float* transform, float trunc,
+                           float min_weight, float max_tsdf, double* workspace,
+                           uint64_t workspace_doubles, double* sums, float* value,
+                           uint8_t* matched, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,9 @@ first stage of the mapping-based pseudo-label baseline.
     python scripts/fuse_tsdf_mesh.py --scene_root <root>/<scene> --out M.ply \\
         [--voxel METRES] [--trunc METRES] [--aabb X0 Y0 Z0 X1 Y1 Z1] [--every N] \\
         [--min_weight K] [--no_color] [--pose_frame] \\
-        [--min_component N] [--component_connectivity {6,26}] [--simplify CELL]
+        [--min_component N] [--component_connectivity {6,26}] [--simplify CELL] \\
+        [--refine_poses [--refine_warmup K] [--refine_iters N] [--refine_stride S] \\
+         [--refine_min_matched SHARE] [--poses_out FILE.npy]]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
 ``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement; scene units as
@@ -26,8 +28,17 @@ that a few bad depth pixels leave in free space) and prints their statistics;
 simplifies the extracted mesh by vertex clustering on a grid of that edge
 (``utils.mesh_fusion.simplify_mesh``: normals and colours are carried) after
 ``--min_component`` has judged the floaters at full resolution, and prints one
-``simplify:`` line of statistics; without the flag nothing changes.  Prints one
-JSON line last."""
+``simplify:`` line of statistics; without the flag nothing changes.
+``--refine_poses`` tracks the camera against the model while it is fused
+(``utils.tsdf_fusion.track_depth_views``): the first ``--refine_warmup`` frames
+are integrated as given, every later one is refined against the volume as it
+then stands (``--refine_iters`` iterations over every ``--refine_stride``-th
+pixel) and integrated with the refined pose, unless it falls back to the given
+one (rank below 6, a matched share below ``--refine_min_matched``, a step beyond
+0.1 rad or the truncation distance).  It prints one ``refine:`` line: frames
+refined, fallbacks, median and maximum step in radians and scene units, median
+rmse (over the frames that matched at all); ``--poses_out`` writes the poses used, [N,4,4] float64 in the NGP frame,
+as .npy.  Without the flag nothing changes.  Prints one JSON line last."""
 import argparse
 import json
 import os
@@ -65,6 +76,15 @@ def parse_args(argv=None):
     p.add_argument("--simplify", type=float, default=None,
                    help="cluster the mesh's vertices on a grid of this edge, metres "
                         "(default: off)")
+    p.add_argument("--refine_poses", action="store_true",
+                   help="refine each frame's pose against the volume before integrating it")
+    p.add_argument("--refine_warmup", type=int, default=1,
+                   help="frames integrated with their given poses first")
+    p.add_argument("--refine_iters", type=int, default=30)
+    p.add_argument("--refine_stride", type=int, default=1, help="every S-th row and column")
+    p.add_argument("--refine_min_matched", type=float, default=0.25,
+                   help="a frame with a smaller matched share keeps its given pose")
+    p.add_argument("--poses_out", default=None, help="write the poses used (.npy, [N,4,4])")
     return p.parse_args(argv)
 
 
@@ -77,6 +97,10 @@ def main(argv=None):
         raise SystemExit("--min_component must be >= 0")
     if a.simplify is not None and not a.simplify > 0:
         raise SystemExit("--simplify must be > 0")
+    if a.refine_warmup < 1 or a.refine_iters < 1 or a.refine_stride < 1:
+        raise SystemExit("--refine_warmup, --refine_iters and --refine_stride must be >= 1")
+    if a.poses_out is not None and not a.refine_poses:
+        raise SystemExit("--poses_out needs --refine_poses")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -94,12 +118,33 @@ def main(argv=None):
         return png("color", i)[..., :3]
 
     voxel = a.voxel * uom
+    refine = {}
+    if a.refine_poses:
+        refine = {"refine_poses": True, "refine_warmup": a.refine_warmup,
+                  "refine_min_matched": a.refine_min_matched,
+                  "refine_kw": {"iterations": a.refine_iters, "stride": a.refine_stride}}
     mesh = fuse_depth_views(poses, fr["intrinsics"], H, W, depth,
                             color_maps=None if a.no_color else color, aabb=a.aabb,
                             voxel=voxel, trunc=None if a.trunc is None else a.trunc * uom,
                             min_weight=a.min_weight, batch=a.batch,
                             min_component=a.min_component,
-                            component_connectivity=a.component_connectivity)
+                            component_connectivity=a.component_connectivity, **refine)
+    tracked = None
+    if a.refine_poses:
+        recs = [r for r in mesh["refine"] if r is not None]
+        # a frame that matched nothing at its last iteration has no rmse: left out of the median
+        med = lambda x: float(np.median(x)) if len(x) else None
+        rmse = [r["rmse"] for r in recs if np.isfinite(r["rmse"])]
+        tracked = {"refined": len(recs), "fallbacks": sum(r["fallback"] for r in recs),
+                   "step_rad_median": med([r["step"][0] for r in recs]),
+                   "step_rad_max": max([r["step"][0] for r in recs], default=None),
+                   "step_units_median": med([r["step"][1] for r in recs]),
+                   "step_units_max": max([r["step"][1] for r in recs], default=None),
+                   "rmse_median": med(rmse)}
+        print("refine: " + json.dumps(tracked))
+        if a.poses_out is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(a.poses_out)), exist_ok=True)
+            np.save(a.poses_out, mesh["poses"])
     simplified = None
     if a.simplify is not None:
         from ucsa_neural_rendering_amd.utils.mesh_fusion import simplify_mesh
@@ -124,6 +169,8 @@ def main(argv=None):
         print("components: " + json.dumps(mesh["components"]))
     if simplified is not None:
         rec["simplify"] = simplified
+    if tracked is not None:
+        rec["refine"] = tracked
     print(json.dumps(rec))
     return rec
 

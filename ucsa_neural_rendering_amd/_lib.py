@@ -398,6 +398,10 @@ SIGNATURES = {
     "ucsa_icp_sums": (C.c_int32, [_p, _p, _u32, C.POINTER(_f), _f, C.POINTER(_u32), _p, _u32, _p,
                                   _u32, _p, _p, _u32, C.POINTER(_f), _f, C.c_int32, _p,
                                   C.c_uint64, _p, _p, _p, _p]),
+    # ---- registration of points to a TSDF volume (the same 29 sums, no mesh) ----
+    "ucsa_tsdf_icp_sums": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f), C.POINTER(_f), _p,
+                                       _u32, C.POINTER(_f), _f, _f, _f, _p, C.c_uint64, _p, _p,
+                                       _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,7 +1,8 @@
 // One step of ICP against a triangle mesh (not in the reference): ucsa_icp_sums.
 // The contract is stated in include/ucsa_hip.h; tests/register_numpy.py restates
 // it over the brute-force search of tests/surface_numpy.py and the 29 sums match
-// it byte for byte.
+// it byte for byte.  The same step against a TSDF volume, ucsa_tsdf_icp_sums
+// (k_tsdf_icp_sums, further down), shares the reduction and the reduce kernel.
 //
 // k_icp_sums<MODE>  a lane per point in work-groups of 256: the point is moved by
 //                   [R | t], the nearest-triangle search of triangle_grid.hip
@@ -196,7 +197,164 @@ uint64_t icp_workspace_rows(uint32_t n) {
   return rows;
 }
 
+// ---- one step of ICP against a TSDF volume: ucsa_tsdf_icp_sums ----
+// k_tsdf_icp_sums  a lane per point in work-groups of 256: the point is moved by
+//                  [R | t], its cell of the lattice is found, the cell's eight
+//                  weights and eight values are gathered (sixteen loads issued
+//                  together, before the first use), the trilinear value F and its
+//                  gradient follow in the ray-caster's expressions (restated
+//                  here: voxel_map.hip is not touched), and the row is
+//                  r = -(F * trunc), J = (q x n, n).  The 29 terms are formed
+//                  afterwards, one at a time, and reduced as in k_icp_sums:
+//                  icp_put / icp_finish, then k_icp_reduce on the group results.
+//
+// Why every index is in range: no float is converted to an integer and no index
+// is formed before `inside` holds, that is 0 <= g_a <= n_a - 1 on every axis (a
+// NaN fails both comparisons).  Then fl_a = min(floor(g_a), n_a - 2) is an
+// integer in [0, n_a - 2] (the host checks n_a >= 2), so c_a <= n_a - 2 and the
+// cell's far corner c_a + 1 <= n_a - 1 is a lattice point; its linear index is
+// at most nx*ny*nz - 1, and the host checks nx*ny*nz <= 2^31 - 1, so the uint32
+// products do not wrap.  A lane with i >= n, or outside the lattice, loads
+// nothing, holds +0.0 for all 29 terms and still reaches the one barrier.
+struct TsdfLattice {
+  uint32_t n[3];
+  float o[3], h[3];
+};
+
+__device__ __forceinline__ float ti_lerp(float x, float y, float f) { return x + f * (y - x); }
+
+__global__ void __launch_bounds__(PG_THREADS) k_tsdf_icp_sums(const float* __restrict__ tsdf,
+                                                              const float* __restrict__ weight,
+                                                              TsdfLattice L,
+                                                              const float* __restrict__ points,
+                                                              uint32_t n, Rigid T, float trunc,
+                                                              float min_weight, float max_tsdf,
+                                                              double* __restrict__ out,
+                                                              float* __restrict__ value,
+                                                              uint8_t* __restrict__ match) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  const uint32_t i = blockIdx.x * PG_THREADS + threadIdx.x;  // < 2^31 + 256
+  const bool live = i < n;
+  float q[3] = {NAN, NAN, NAN};
+  if (live) {
+    const float x = points[3ull * i], y = points[3ull * i + 1u], z = points[3ull * i + 2u];
+    q[0] = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    q[1] = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    q[2] = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+  }
+  float g[3];
+  bool inside = live;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    g[a] = (q[a] - L.o[a]) / L.h[a];
+    inside = inside && g[a] >= 0.0f && g[a] <= (float)(L.n[a] - 1u);
+  }
+  float f[3] = {0.0f, 0.0f, 0.0f};
+  float w[8], v[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) w[c] = v[c] = 0.0f;
+  if (inside) {
+    uint32_t c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float fl = fminf(floorf(g[a]), (float)(L.n[a] - 2u));
+      c[a] = (uint32_t)fl;
+      f[a] = g[a] - fl;
+    }
+    const uint32_t sj = L.n[2], si = L.n[1] * L.n[2];
+    const uint32_t base = (c[0] * L.n[1] + c[1]) * L.n[2] + c[2];
+    // v[4i + 2j + k]: both arrays, all sixteen loads before the first use
+#pragma unroll
+    for (uint32_t c8 = 0; c8 < 8u; ++c8) {
+      const uint32_t at = base + ((c8 & 4u) ? si : 0u) + ((c8 & 2u) ? sj : 0u) + (c8 & 1u);
+      w[c8] = weight[at];
+      v[c8] = tsdf[at];
+    }
+  }
+  bool observed = inside;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) observed = observed && w[c] >= min_weight;
+  const float c00 = ti_lerp(v[0], v[1], f[2]), c01 = ti_lerp(v[2], v[3], f[2]);
+  const float c10 = ti_lerp(v[4], v[5], f[2]), c11 = ti_lerp(v[6], v[7], f[2]);
+  const float c_0 = ti_lerp(c00, c01, f[1]), c_1 = ti_lerp(c10, c11, f[1]);
+  const float F = ti_lerp(c_0, c_1, f[0]);
+  float G[3];
+  G[0] = c_1 - c_0;
+  G[1] = ti_lerp(c01 - c00, c11 - c10, f[0]);
+  G[2] = ti_lerp(ti_lerp(v[1] - v[0], v[3] - v[2], f[1]), ti_lerp(v[5] - v[4], v[7] - v[6], f[1]),
+                 f[0]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) G[a] = G[a] / L.h[a];
+  const float ln = sqrtf((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+  const bool matched = observed && ln > 0.0f && isfinite(ln) && fabsf(F) <= max_tsdf;
+  if (live) {
+    if (value) value[i] = observed ? F : NAN;
+    if (match) match[i] = matched ? 1 : 0;
+  }
+  float V[8][1];  // J (0..5), r (6) and 1 (7); unused bits of an unmatched row are selected away
+  icp_row<1>(q[0], q[1], q[2], 0.0f, 0.0f, 0.0f, G[0] / ln, G[1] / ln, G[2] / ln, V, 0);
+  V[6][0] = -(F * trunc);
+  uint32_t col = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int b = a; b < 6; ++b) icp_put(icp_term<1>(matched, V[a], V[b]), col++, sh);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) icp_put(icp_term<1>(matched, V[a], V[6]), col++, sh);
+  icp_put(icp_term<1>(matched, V[6], V[6]), col++, sh);
+  icp_put(icp_term<1>(matched, V[7], V[7]), col++, sh);
+  icp_finish(sh, out);
+}
+
 }  // namespace
+
+extern "C" int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx,
+                                      uint32_t ny, uint32_t nz, const float* origin3,
+                                      const float* spacing3, const float* points, uint32_t n,
+                                      const float* transform, float trunc, float min_weight,
+                                      float max_tsdf, double* workspace,
+                                      uint64_t workspace_doubles, double* sums, float* value,
+                                      uint8_t* matched, void* stream) {
+  UCSA_CHECK_ARG(tsdf, 0);
+  UCSA_CHECK_ARG(weight, 1);
+  UCSA_CHECK_ARG(nx >= 2 && ny >= 1 && nz >= 1 && (uint64_t)nx * ny * nz <= 0x7FFFFFFFull, 2);
+  UCSA_CHECK_ARG(ny >= 2, 3);
+  UCSA_CHECK_ARG(nz >= 2, 4);
+  UCSA_CHECK_ARG(origin3 && pg_host_finite(origin3[0]) && pg_host_finite(origin3[1]) &&
+                     pg_host_finite(origin3[2]), 5);
+  UCSA_CHECK_ARG(spacing3, 6);
+  for (int a = 0; a < 3; ++a) UCSA_CHECK_ARG(spacing3[a] > 0.0f && pg_host_finite(spacing3[a]), 6);
+  UCSA_CHECK_ARG(n <= 0x7FFFFFFFu, 8);
+  UCSA_CHECK_ARG(n == 0 || points, 7);
+  UCSA_CHECK_ARG(transform, 9);
+  UCSA_CHECK_ARG(trunc > 0.0f && pg_host_finite(trunc), 10);
+  UCSA_CHECK_ARG(min_weight > 0.0f, 11);
+  UCSA_CHECK_ARG(max_tsdf > 0.0f && max_tsdf <= 1.0f, 12);
+  const uint64_t ws_rows = icp_workspace_rows(n);
+  UCSA_CHECK_ARG(ws_rows == 0 || workspace, 13);
+  UCSA_CHECK_ARG(workspace_doubles >= ws_rows * ICP_SUMS, 14);
+  UCSA_CHECK_ARG(sums, 15);
+  TsdfLattice L;
+  L.n[0] = nx, L.n[1] = ny, L.n[2] = nz;
+  for (int a = 0; a < 3; ++a) L.o[a] = origin3[a], L.h[a] = spacing3[a];
+  Rigid T;
+  for (int k = 0; k < 12; ++k) T.m[k] = transform[k];
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t count = n ? ucsa_div_up(n, PG_THREADS) : 1u;  // at least one stage: n == 0 gives +0.0
+  double* out = count == 1u ? sums : workspace;
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_tsdf_icp_sums, dim3(count), dim3(PG_THREADS), 0, s, tsdf, weight, L, points,
+                     n, T, trunc, min_weight, max_tsdf, out, value, matched);
+  while (count > 1u) {  // as in ucsa_icp_sums: at most three passes for n < 2^31
+    const uint32_t next = ucsa_div_up(count, PG_THREADS);
+    const double* in = out;
+    out = next == 1u ? sums : out + (uint64_t)count * ICP_SUMS;
+    hipLaunchKernelGGL(k_icp_reduce, dim3(next), dim3(PG_THREADS), 0, s, in, count, out);
+    count = next;
+  }
+  return ucsa_launch_status();
+}
 
 extern "C" int32_t ucsa_icp_sums(const float* records, const int32_t* offsets, uint32_t n_pairs,
                                  const float* origin, float cell, const uint32_t* dims,

@@ -8,7 +8,8 @@ The wrappers live in one module per family (``render``, ``backward``, ``train``,
 ``march``, ``volume``, ``mesh``, ``search``) over the shared argument checks of
 ``_args``; this file only re-exports them, so ``ops.NAME`` is the way in.
 ``raycast`` came after the surface of ``ops`` was frozen and is reached as a
-module: ``ops.raycast.raycast_mesh``; so is ``register``: ``ops.register.icp_sums``.
+module: ``ops.raycast.raycast_mesh``; so is ``register``: ``ops.register.icp_sums``,
+``ops.register.tsdf_sums``.
 """
 from .. import _lib
 from .._lib import Grid, check, fvec, lib

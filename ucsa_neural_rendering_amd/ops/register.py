@@ -1,5 +1,6 @@
 """Registration of points to a triangle mesh: the fused step of ICP over the
-grid of ``ops.triangle_grid``.  Reached as ``ops.register.icp_sums``."""
+grid of ``ops.triangle_grid``.  Reached as ``ops.register.icp_sums``.  The same
+step against a TSDF volume, without a mesh: ``ops.register.tsdf_sums``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,7 +9,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, fvec, lib
-from ._args import _gpu, _mesh, _points3, _positive, _ptr, _stream
+from ._args import _gpu, _mesh, _origin_spacing, _points3, _positive, _ptr, _stream, volume_lattice
 
 ICP_SUMS = 29
 MODES = {"plane": 0, "point": 1}
@@ -124,3 +125,52 @@ def icp_sums(grid, verts, faces, unit_normal, points, transform, max_dist: float
         max_dist, MODES[mode], _ptr(ws), ws_doubles, _ptr(sums), _ptr(face), _ptr(dist2),
         _stream()), "ucsa_icp_sums")
     return (sums, face, dist2) if return_matches else sums
+
+
+def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
+              max_tsdf: float = 1.0, return_matches: bool = False):
+    """The normal equations of one point-to-plane ICP step of ``points`` [N,3]
+    (float32 on the GPU) against the TSDF ``volume`` (``ops.tsdf_volume``'s dict,
+    as ``ops.integrate_tsdf`` leaves it) -> ``sums`` float64 [29] on the device,
+    or (``sums``, ``value`` float32 [N], ``matched`` uint8 [N]) with
+    ``return_matches``.  One call moves every point by ``transform`` (a 3x4 or
+    4x4 array-like on the host, converted to float32: q = R p + t), samples the
+    volume at q -- the trilinear value F and the gradient that
+    ``ops.raycast_tsdf`` writes as its normal n, from the cell's sixteen loads --
+    and sums over the matched points r = -(F * trunc) and J = (q x n, n) as
+    ``icp_sums`` does in mode "plane": the same 29 float64 numbers in the same
+    tree, so ``utils.registration.solve_step`` and ``compose`` take them
+    unchanged.  A point matches when it lies inside the lattice (it is not
+    clamped into it), all eight corners of its cell have weight >=
+    ``min_weight``, the gradient is not zero and |F| <= ``max_tsdf`` (in units
+    of ``trunc``, at most 1: the coarse-to-fine gate).  ``trunc`` is the
+    truncation distance the volume was integrated with.  ``value`` is F where
+    the cell is observed and NaN elsewhere.  Contract of ucsa_tsdf_icp_sums
+    (include/ucsa_hip.h)."""
+    (nx, ny, nz), dev = volume_lattice(volume)
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
+                             f"{(nx, ny, nz)}")
+    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
+    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
+    n = int(pts.shape[0])
+    if n > 0x7FFFFFFF:
+        raise _lib.UcsaError("points must have at most 2^31-1 rows")
+    t12 = _transform12(transform)
+    trunc = _positive(trunc, "trunc")
+    min_weight = float(min_weight)
+    if not min_weight > 0:
+        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
+    max_tsdf = float(max_tsdf)
+    if not 0 < max_tsdf <= 1:
+        raise _lib.UcsaError(f"max_tsdf must be in (0, 1], got {max_tsdf!r}")
+    ws_doubles = ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    value = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    matched = torch.empty(n, dtype=torch.uint8, device=dev) if return_matches else None
+    check(lib().ucsa_tsdf_icp_sums(
+        _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
+        _ptr(pts) if n else None, n, t12, trunc, min_weight, max_tsdf, _ptr(ws), ws_doubles,
+        _ptr(sums), _ptr(value), _ptr(matched), _stream()), "ucsa_tsdf_icp_sums")
+    return (sums, value, matched) if return_matches else sums

@@ -18,6 +18,12 @@ a fused or exported mesh to the ground truth before it is scored) and depth
 frame to mesh (``refine_pose``: the points are back-projected in the camera frame
 and the initial transform is the camera pose, so the result is a refined pose).
 
+``register_points_tsdf`` / ``refine_pose_tsdf`` run the same loop against a TSDF
+volume instead of a mesh (``ops.register.tsdf_sums``: the residual is the
+volume's signed distance at the moved point, the normal its gradient), for a
+pose already within the truncation distance of the answer: frame-to-model
+tracking while a scene is fused (``utils.tsdf_fusion.track_depth_views``).
+
 Not here: scale, rejection of matches on open boundaries, normal compatibility
 gates, robust kernels beyond the ``max_dist`` schedule, global (coarse)
 alignment: the start must lie within ``max_dist`` and a few degrees of the
@@ -273,3 +279,83 @@ def refine_poses(depths, poses, intrinsics, grid_or_mesh, **kw):
         mesh["faces"] = _on_device(mesh["faces"], torch.int32, 3, device)
         mesh["grid"] = ops.triangle_grid(mesh["verts"], mesh["faces"])
     return [refine_pose(d, p, intrinsics, mesh, **kw) for d, p in zip(depths, poses)]
+
+
+# ---------------------------------------------------------------------------
+# against a TSDF volume: frame-to-model tracking
+# ---------------------------------------------------------------------------
+def register_points_tsdf(points, volume, trunc: float, init=None, iterations: int = 30,
+                         min_weight: float = 1.0, max_tsdf: float = 1.0, max_tsdf_schedule=None,
+                         tol_rot: float = 1e-6, tol_trans: float = 1e-6, rcond: float = 1e-8,
+                         device="cuda"):
+    """Align ``points`` [N,3] to the surface a TSDF ``volume`` holds
+    (``ops.tsdf_volume``'s dict on the device, integrated with the truncation
+    distance ``trunc``) -> ``register_points``' dict with the same keys
+    (``history`` entries carry ``max_tsdf`` in place of ``max_dist``).  No mesh
+    is extracted and nothing is searched: the residual of a moved point q is the
+    volume's trilinear signed distance there, r = -(F * trunc), and its normal
+    n the normalised gradient, pointing toward free space; the surface point is
+    q - F trunc n, so r has the sign of the mesh route's n . (c - q) and
+    ``solve_step`` / ``compose`` are used unchanged.  Each iteration is
+    ``ops.register.tsdf_sums``, one read of 29 doubles, ``solve_step`` and
+    ``compose``.  A point matches where all eight corners of its cell have
+    weight >= ``min_weight`` and |F| <= ``max_tsdf`` (units of ``trunc``, at
+    most 1); ``max_tsdf_schedule`` gives the gate of iteration k as its entry
+    min(k, len - 1), coarse to fine, like ``max_dist_schedule``.
+
+    The basin: the volume carries signal only within ``trunc`` of a surface --
+    beyond it F is clamped to +-1, the gradient is zero and nothing matches --
+    so the pose error, measured at the surface (translation plus angle times
+    the distance to the surface), must stay below ``trunc``.  Anything coarser
+    is the mesh route's job (``register_points`` with a ``max_dist_schedule``)
+    or global alignment, which is not here."""
+    import torch
+
+    from .. import ops
+    pts = _on_device(points, torch.float32, 3, device)
+    T = compose(np.eye(4) if init is None else np.asarray(init, np.float64), np.zeros(6))
+    schedule = [float(max_tsdf)] if max_tsdf_schedule is None else \
+        [float(m) for m in max_tsdf_schedule]
+    history, rank, converged, done = [], 0, False, 0
+    for k in range(int(iterations)):
+        mt = schedule[min(k, len(schedule) - 1)]
+        sums = ops.register.tsdf_sums(volume, pts, T, trunc, min_weight, mt).cpu().numpy()
+        _, _, sse, count = normal_equations(sums)
+        xi, rank = solve_step(sums, rcond)
+        T = compose(T, xi)
+        done = k + 1
+        om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
+        history.append({"matched": int(round(count)),
+                        "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
+                        "omega": om, "upsilon": up, "max_tsdf": mt, "sums": sums})
+        if count > 0 and om <= tol_rot and up <= tol_trans:
+            converged = True
+            break
+    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
+    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
+            "iterations": done, "converged": converged, "history": history,
+            "n_points": int(pts.shape[0])}
+
+
+def refine_pose_tsdf(depth, pose, intrinsics, volume, trunc: float, stride: int = 1,
+                     depth_min: float = 0.0, depth_max: float = math.inf, **kw):
+    """Refine the camera-to-world ``pose`` (4x4) of one z-depth frame ``depth``
+    [H,W] against the TSDF ``volume`` as it stands -> ``register_points_tsdf``'s
+    dict with ``pose`` (4x4 float64, the same matrix as ``transform``).  The
+    valid pixels are back-projected into the camera frame (``backproject``) and
+    registered with ``init=pose``: frame-to-model tracking, for a pose whose
+    error at the surface is below ``trunc`` (see ``register_points_tsdf``)."""
+    import torch
+    device = kw.pop("device", "cuda")
+    d = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth, np.float32))
+    pts = backproject(d.to(device), intrinsics, stride, depth_min, depth_max)
+    out = register_points_tsdf(pts, volume, trunc, init=pose, device=device, **kw)
+    out["pose"] = out["transform"]
+    return out
+
+
+def pose_step(a, b):
+    """the difference of two 4x4 poses -> (radians, units): the angle of the
+    relative rotation and the distance of the camera centres"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return rotation_angle(a[:3, :3] @ b[:3, :3].T), float(np.linalg.norm(a[:3, 3] - b[:3, 3]))

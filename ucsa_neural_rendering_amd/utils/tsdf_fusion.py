@@ -12,8 +12,9 @@ voxel state is read and written once per batch); ``ops.marching_cubes`` with
 with an unobserved corner (no second sheet one truncation distance behind the
 walls).  Per-voxel class votes and the ray-cast model view of the volume are in
 ``utils/voxel_map.py``.  Out of scope: sparse / hashed voxel blocks, bilinear
-depth lookup, distance- or angle-dependent weights, pose refinement, anything in
-the training loop.
+depth lookup, distance- or angle-dependent weights, anything in the training
+loop.  ``fuse_depth_views(refine_poses=True)`` refines each frame's pose against
+the volume before it is integrated (``track_depth_views``).
 
 ``remove_small_components`` drops the floaters first: the specks of truncation
 band that a few bad depth pixels leave in observed free space.  The band
@@ -124,7 +125,8 @@ def remove_small_components(volume, min_voxels, connectivity=26, min_weight=1):
 def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=None,
                      voxel=0.05, trunc=None, min_weight=1, batch=16, max_weight=65504.0,
                      depth_min=1e-6, depth_max=3.0e38, device="cuda", min_component=0,
-                     component_connectivity=26):
+                     component_connectivity=26, refine_poses=False, refine_warmup=1,
+                     refine_kw=None, refine_min_matched=0.25, refine_max_step=None):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps``: a sequence
     or a callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), read
     batch by batch; ``color_maps`` likewise ``i -> [H,W,3]`` uint8 or None;
@@ -138,7 +140,13 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     split ``integrate_ms`` / ``extract_ms`` (device-synchronised host clock).
     ``min_component`` > 0 runs ``remove_small_components`` with that voxel count
     (and ``component_connectivity``) before the mesh is extracted and adds its
-    statistics as ``components``."""
+    statistics as ``components``.  ``refine_poses`` tracks the camera against the
+    model while it is fused (``track_depth_views``, which the ``refine_*``
+    arguments go to): the box is still computed from the given poses, the views
+    are integrated one per call, and the dict gains ``poses`` [N,4,4] float64
+    (the poses used), ``refine`` (the per-frame records) and ``refine_ms``.
+    With ``refine_poses=False`` nothing of that is entered and every byte of the
+    result is what it was."""
     dev = torch.device(device)
     voxel = float(voxel)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
@@ -159,7 +167,17 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     vol = ops.tsdf_volume(dims, box[0].tolist(), voxel, with_color=color_maps is not None,
                           device=dev)
     t_i = 0.0
-    for a in range(0, N, batch):
+    tracked = None
+    if refine_poses:
+        tracked = track_depth_views(vol, poses, intrinsics, H, W, depth_maps, trunc,
+                                    color_maps=color_maps, min_weight=min_weight,
+                                    max_weight=max_weight, depth_min=depth_min,
+                                    depth_max=depth_max, refine_warmup=refine_warmup,
+                                    refine_kw=refine_kw, refine_min_matched=refine_min_matched,
+                                    refine_max_step=refine_max_step)
+        t_i = 1e-3 * tracked["integrate_ms"]
+    # tracked: every view is in the volume already; otherwise a batch of views per call
+    for a in ([] if tracked is not None else range(0, N, batch)):
         b = min(a + batch, N)
         z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
         col = None
@@ -187,11 +205,80 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     t_e = time.perf_counter() - t0
     observed = float((vol["weight"] >= float(min_weight)).float().mean())
     extra = {} if stats is None else {"components": stats}
+    if tracked is not None:
+        extra.update(poses=tracked["poses"], refine=tracked["refine"],
+                     refine_ms=tracked["refine_ms"])
     return {**extra, "verts": verts.cpu().numpy(), "faces": faces.cpu().numpy(),
             "normals": normals.cpu().numpy(),
             "rgb": None if rgb is None else rgb.cpu().numpy(), "labels": None,
             "dims": tuple(dims), "origin": vol["origin"], "spacing": vol["spacing"],
             "observed": observed, "integrate_ms": 1e3 * t_i, "extract_ms": 1e3 * t_e}
+
+
+def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_maps=None,
+                      min_weight=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
+                      refine_warmup=1, refine_kw=None, refine_min_matched=0.25,
+                      refine_max_step=None):
+    """Frame-to-model tracking, the other half of KinectFusion: integrate the
+    views into ``volume`` (in place) one per call, each with a pose refined
+    against the volume as it then stands.  The first ``refine_warmup`` frames
+    are integrated with their given poses; each later frame goes through
+    ``utils.registration.refine_pose_tsdf`` with ``init`` = its given pose
+    (``refine_kw``: its keyword arguments, ``stride``, ``iterations``,
+    ``max_tsdf_schedule`` ...; ``min_weight`` defaults to this call's) and is
+    integrated with the refined pose.  A frame keeps its given pose and counts
+    as a fallback when the last solve's rank is below 6, when the matched share
+    of its back-projected points is below ``refine_min_matched``, or when the
+    refined pose differs from the given one by more than ``refine_max_step`` =
+    (radians, units), default (0.1, ``trunc``): a larger step has left the basin
+    in which the volume carries signal.  -> dict: ``poses`` [N,4,4] float64 (the
+    poses used), ``refine`` (per frame None during the warm-up, else a dict
+    ``matched`` -- the share --, ``rmse``, ``rank``, ``iterations``, ``step``
+    (radians, units) from the given pose and ``fallback``), ``integrate_ms``,
+    ``refine_ms`` (device-synchronised host clock)."""
+    from .registration import pose_step, refine_pose_tsdf
+    dev = volume["tsdf"].device
+    poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
+    kw = dict(refine_kw or {})
+    kw.setdefault("min_weight", float(min_weight))
+    max_rot, max_trans = (0.1, float(trunc)) if refine_max_step is None else refine_max_step
+    used, records, t_i, t_r = [], [], 0.0, 0.0
+    for i in range(poses.shape[0]):
+        z = _batch(depth_maps, i, i + 1, np.float32, H, W, "depth_maps").to(dev)
+        col = None
+        if color_maps is not None:
+            col = np.asarray(color_maps(i) if callable(color_maps) else color_maps[i])
+            if col.shape != (H, W, 3):
+                raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape}")
+            col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))[None])
+            col = col.to(dev)
+        given = poses[i].astype(np.float64)
+        pose, rec = given, None
+        if i >= int(refine_warmup):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = refine_pose_tsdf(z[0], given, intrinsics, volume, trunc, depth_min=depth_min,
+                                   depth_max=depth_max, device=dev, **kw)
+            t_r += time.perf_counter() - t0
+            rot, trans = pose_step(out["pose"], given)
+            share = out["matched"] / out["n_points"] if out["n_points"] else 0.0
+            fallback = bool(out["rank"] < 6 or share < refine_min_matched or rot > max_rot
+                            or trans > max_trans)
+            rec = {"matched": share, "rmse": out["rmse"], "rank": out["rank"],
+                   "iterations": out["iterations"], "step": (rot, trans), "fallback": fallback}
+            if not fallback:
+                pose = out["pose"]
+        used.append(pose)
+        records.append(rec)
+        P = torch.from_numpy(pose.astype(np.float32)[None]).to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ops.integrate_tsdf(volume, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
+                           depth_min=depth_min, depth_max=depth_max)
+        torch.cuda.synchronize()
+        t_i += time.perf_counter() - t0
+    return {"poses": np.stack(used), "refine": records, "integrate_ms": 1e3 * t_i,
+            "refine_ms": 1e3 * t_r}
 
 
 def volume_from_mesh(verts, faces, voxel, trunc, aabb=None, max_voxels=1 << 28):
