@@ -906,9 +906,12 @@ int32_t ucsa_seg_tail(const float* logits, const int64_t* labels, uint32_t B,
  * forward:  y = relu?( (x - mean) * invstd * gamma + beta (+ residual) )
  *   training != 0: batch statistics (biased variance); running_mean /
  *     running_var (may both be NULL) updated as torch.nn.BatchNorm2d does
- *     (momentum, unbiased variance); save_mean / save_invstd [C] written for
- *     the backward.
+ *     (momentum, unbiased variance = biased * M / (M - 1), and the biased one
+ *     itself when M = 1); save_mean / save_invstd [C] written for the backward.
+ *     Without running statistics the variance is summed around 0: its
+ *     accuracy falls with (mean / std)^2 (table in csrc/batchnorm.hip).
  *   training == 0: the running statistics normalise; save_* untouched.
+ *   The fused ReLU keeps NaN (y = pre < 0 ? 0 : pre), as torch.relu does.
  * backward: g = dy * (y > 0) when relu (y = the forward's output), else dy;
  *   dresidual (may be NULL) = g; dbeta = sum g; dgamma = sum g * xhat;
  *   dx = gamma * invstd * (g - dbeta / M - xhat * dgamma / M)   (training mode).
