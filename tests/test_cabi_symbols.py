@@ -127,27 +127,51 @@ def test_ctypes_structures_match_the_header_layout(built_lib, tmp_path):
 
 
 def test_every_environment_switch_of_the_library_is_in_its_table_and_documented():
-    """the library reads its UCSA_* switches from ONE table, once
-    per process (csrc/render.hip kEnvNames / ucsa_getenv; an unknown name asserts).
-    Every name the sources look up is in the table, every table entry is looked up,
-    and INTEGRATION.md's "Environment variables" section names each of them."""
+    """the library reads its UCSA_* switches from ONE table, parsed
+    once into a typed snapshot (csrc/env.h UCSA_ENV_TABLE / ucsa_env(); a field that is
+    not a row does not compile).  Every field the sources read is a row, every row is
+    read outside the env unit, and INTEGRATION.md's "Environment variables" section
+    names each of them.  No consumer caches an env-derived value in a static
+    (ucsa_env_reload() must reach it), and the retired switches stay retired."""
     import glob
     import re
     src = os.path.join(ROOT, "ucsa_neural_rendering_amd", "csrc")
+    rows = dict(re.findall(r'X\("(UCSA_[A-Z0-9_]+)",\s*\w+,\s*(\w+),',
+                           open(os.path.join(src, "env.h")).read()))
+    assert len(rows) == 14 and len(set(rows.values())) == 14, rows
+    fields = set(rows.values())
     used = set()
-    for f in glob.glob(os.path.join(src, "*.hip")) + glob.glob(os.path.join(src, "*.h")):
+    for f in glob.glob(os.path.join(src, "*.hip")) + glob.glob(os.path.join(src, "*.h")) + \
+            glob.glob(os.path.join(src, "*.cpp")):
         text = open(f).read()
-        assert not re.search(r"(?<![_A-Za-z])getenv\(", text.replace("ucsa_getenv(", "")) \
-            or f.endswith("render.hip"), f"{f}: a plain getenv() outside the table"
-        used |= set(re.findall(r'(?:ucsa_getenv|env_u|simple_gather_below)\(\s*"(UCSA_[A-Z0-9_]+)"', text))
-    r = open(os.path.join(src, "render.hip")).read()
-    table = set(re.findall(r'"(UCSA_[A-Z0-9_]+)"',
-                           r[r.index("kEnvNames[] = {"):r.index("constexpr int kEnvCount")]))
-    assert used == table, (used - table, table - used)
+        if os.path.basename(f) in ("env.h", "env.cpp"):
+            continue
+        assert not re.search(r"(?<![_A-Za-z])getenv\(", text), \
+            f"{f}: a plain getenv() outside the table"
+        # a field is read as ucsa_env().field, or through `const UcsaEnv& env = ucsa_env();`
+        used |= set(re.findall(r"ucsa_env\(\)\.(\w+)", text))
+        if re.search(r"const UcsaEnv& env = ucsa_env\(\);", text):
+            used |= set(re.findall(r"(?<![\w.])env\.(?!h\b|cpp\b)(\w+)", text))
+        for m in re.finditer(r"\bstatic\b[^;{}]*=[^;]*", text):
+            assert "ucsa_env(" not in m.group(0), \
+                f"{f}: a static initialised from ucsa_env(): {m.group(0)[:80]!r}"
+    assert used == fields, (used - fields, fields - used)
+    table = set(rows)
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     sec = doc[doc.index("### Environment variables"):doc.index("## 7. Entry-point index")]
-    missing = [n for n in sorted(table) if n not in sec
-               and not any(n.startswith(p.rstrip("*")) for p in re.findall(r"`(UCSA_[A-Z_]+)=", sec) if False)]
     # (INTEGRATION abbreviates the UCSA_ENC_SIMPLE family as `UCSA_ENC_SIMPLE=n` / `_H` / `_RAYS`)
-    missing = [n for n in missing if not n.startswith("UCSA_ENC_SIMPLE")]
+    missing = [n for n in sorted(table) if n not in sec and not n.startswith("UCSA_ENC_SIMPLE")]
     assert not missing, missing
+    retired = ["UCSA_" + n for n in ("SHADE_VARIANT", "SPLIT_COMPOSITE", "ENC_LDS_PAD",
+                                     "ENC_SORTED_LEAN", "SORT_BINS")]
+    assert not [n for n in retired if n in sec], "a retired switch is documented as live"
+    here = os.path.abspath(__file__)
+    for top in ("ucsa_neural_rendering_amd", "tools", "tests"):
+        for dirpath, _, names in os.walk(os.path.join(ROOT, top)):
+            for name in names:
+                path = os.path.join(dirpath, name)
+                if path == here or not name.endswith((".py", ".hip", ".h", ".cpp", ".sh", ".md",
+                                                      "Makefile")):
+                    continue
+                text = open(path, errors="replace").read()
+                assert not [n for n in retired if n in text], f"{path}: names a retired switch"

@@ -305,6 +305,76 @@ def test_binned_grid_backward_with_a_dirty_oversized_workspace(ops):
         test_binned_grid_backward_equals_direct_atomics(ops, spread)
 
 
+def test_bin_scale_switch_reaches_the_grid_backward_after_a_reload(ops, monkeypatch):
+    """UCSA_BWD_BIN_SCALE flipped inside one process (setenv + ops.env_reload()) must
+    reach hashgrid_bwd_launch: it used to keep the value in a function-local static,
+    so the flip compared the default with itself.  The clustered-samples case of the
+    test above (same inputs, same tolerance), on the grid whose levels 0-2 are dense
+    and whose hashed levels start at scale 127:
+      1e9   no level reaches the bins: the poisoned workspace stays untouched, every
+            level through the run-combining atomics kernel
+      0     every hashed level through the bins -- on this grid the default split
+            (the first hashed level has scale 127 >= 100), workspace written
+      unset the default again, workspace written.
+    The gradient is the default's each time (same records, another summation order)."""
+    from ucsa_neural_rendering_amd import ops as uops
+    from ucsa_neural_rendering_amd._lib import make_grid
+    dev = torch.device("cuda:0")
+    grid = make_grid(4.0)
+    g = torch.Generator().manual_seed(23)
+    N, T = 300, 128
+    o = ((torch.rand(N, 3, generator=g) * 2 - 1) * 2.0)
+    d = torch.nn.functional.normalize(torch.randn(N, 3, generator=g), dim=-1)
+    centres = torch.rand(N, 3, generator=g) * 3.0 + 0.3
+    width = 10.0 ** (-(torch.rand(N, 3, generator=g) * 2 + 1.7))
+    z = (centres[:, :, None] + width[:, :, None] * torch.rand(N, 3, 43, generator=g)).reshape(N, -1)
+    z = z[:, :T].sort(-1).values
+    z[:, 1::16] = z[:, 0::16]
+    z[::7] = z[0]
+    o[::7], d[::7] = o[0], d[0]
+    aabb = [-4.0, -4.0, -4.0, 4.0, 4.0, 4.0]
+    d_feat = torch.randn(grid.n_levels, N * T, 2, generator=g)
+    d_feat[:, 5::9] = 0.0
+    o, d, z, d_feat = o.to(dev).contiguous(), d.to(dev).contiguous(), z.to(dev).contiguous(), d_feat.to(dev)
+    total = int(grid.total_entries)
+
+    def backward():
+        """(gradient, did the call write the poisoned bin workspace)"""
+        for ws in uops._bwd_ws.values():
+            ws.fill_(0xA5)
+        gt = torch.zeros(total, 2, device=dev)
+        ops.hashgrid_bwd_rays(grid, o, d, z, aabb, d_feat, gt, binned=True)
+        torch.cuda.synchronize()
+        return gt, any(bool((ws != 0xA5).any()) for ws in uops._bwd_ws.values())
+
+    def same(got, ref):
+        scale = float(ref.abs().max())
+        assert scale > 0
+        assert float((got - ref).abs().max()) <= 2e-4 * scale
+        assert float((got - ref).abs().sum()) <= 1e-5 * float(ref.abs().sum())
+
+    monkeypatch.delenv("UCSA_BWD_BIN_SCALE", raising=False)
+    ops.env_reload()
+    backward()                                   # (allocates the workspace if this test runs alone)
+    g_def, wrote = backward()
+    assert wrote
+    monkeypatch.setenv("UCSA_BWD_BIN_SCALE", "1e9")
+    ops.env_reload()
+    g_off, wrote = backward()
+    assert not wrote, "UCSA_BWD_BIN_SCALE=1e9 + env_reload() did not reach the grid backward"
+    same(g_off, g_def)
+    monkeypatch.setenv("UCSA_BWD_BIN_SCALE", "0")
+    ops.env_reload()
+    g_all, wrote = backward()
+    assert wrote
+    same(g_all, g_def)
+    monkeypatch.delenv("UCSA_BWD_BIN_SCALE")
+    ops.env_reload()
+    g_again, wrote = backward()
+    assert wrote
+    same(g_again, g_def)
+
+
 def test_adam_kernel_on_misaligned_slices(ops):
     """ShardedHipAdam hands ucsa_adam_step[_scaled] SLICES of the parameter /
     moment tensors.  A slice that does not start on a 16-byte boundary must

@@ -119,8 +119,6 @@ n_views = int(os.environ.get("UCSA_EXP_VIEWS", 10))
 with torch.no_grad():
     ref = serial()
     ms = timed(serial, n_views)
-    print(f"UCSA_ENC_LDS_PAD={os.environ.get('UCSA_ENC_LDS_PAD', '0')}: encoder workgroups of 4 waves, "
-          "13 KB LDS + the pad; 74 VGPRs -> at most 6 waves / SIMD")
     print(f"serial: {ms:.2f} ms/view = {H * W / ms / 1e3:.2f} M rays/s")
     da, sa = stage_alone()
     print(f"  per chunk, alone: density half {da:.2f} ms, shading half {sa:.2f} ms")

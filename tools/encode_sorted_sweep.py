@@ -1,6 +1,6 @@
 """Round 5: the depth-ordered fine pass (csrc/hashgrid_sorted.hip) against the
 image-ordered one on the bench's 61 440-ray chunk: sort, encode (by
-UCSA_ENC_SORTED_ML / _LEAN) and sigma MLP with the scatter, event-timed; h / sigma
+UCSA_ENC_SORTED_ML) and sigma MLP with the scatter, event-timed; h / sigma
 compared bit for bit with the staged pair."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,16 +45,14 @@ for name, zz in (("coarse", z), ("fine", zf)):
     print(f"{name:6s} image-ordered: encode {t_enc:.3f} ms + sigma(f16x2) {t_sig:.3f} ms = {t_enc + t_sig:.3f} ms")
     zs, pix, slot = ops.tile_depth_order(zz, W)
     t_sort = timed(lambda: ops.tile_depth_order(zz, W))
-    for lean in (1, 0):
-        os.environ["UCSA_ENC_SORTED_LEAN"] = str(lean)
-        for ml in [int(x) for x in os.environ.get("KS", "0,4,8,9,10,12").split(",")]:
-            os.environ["UCSA_ENC_SORTED_ML"] = str(ml)
-            ops.lib().ucsa_env_reload()      # the library reads its switches once
-            got = ops.hashgrid_encode_sorted(f["grid"], f["table"], o, d, zs, pix, aabb, T, W)
-            same = bool(torch.equal(got, ref[:, slot.long()]))
-            t_e = timed(lambda: ops.hashgrid_encode_sorted(f["grid"], f["table"], o, d, zs, pix, aabb, T, W))
-            h1, s1 = ops.sigma_mlp_fwd_scatter(3, got, f2["packed_sigma"], slot)
-            same = same and bool(torch.equal(h0, h1) and torch.equal(s0, s1))
-            t_s = timed(lambda: ops.sigma_mlp_fwd_scatter(3, got, f2["packed_sigma"], slot))
-            print(f"{name:6s} depth-ordered lean={lean} ml={ml:2d}: sort {t_sort:.3f} + encode {t_e:.3f} + sigma/scatter {t_s:.3f} = "
-                  f"{t_sort + t_e + t_s:.3f} ms  bit-identical {same}", flush=True)
+    for ml in [int(x) for x in os.environ.get("KS", "0,4,8,9,10,12").split(",")]:
+        os.environ["UCSA_ENC_SORTED_ML"] = str(ml)
+        ops.lib().ucsa_env_reload()      # the library reads its switches once
+        got = ops.hashgrid_encode_sorted(f["grid"], f["table"], o, d, zs, pix, aabb, T, W)
+        same = bool(torch.equal(got, ref[:, slot.long()]))
+        t_e = timed(lambda: ops.hashgrid_encode_sorted(f["grid"], f["table"], o, d, zs, pix, aabb, T, W))
+        h1, s1 = ops.sigma_mlp_fwd_scatter(3, got, f2["packed_sigma"], slot)
+        same = same and bool(torch.equal(h0, h1) and torch.equal(s0, s1))
+        t_s = timed(lambda: ops.sigma_mlp_fwd_scatter(3, got, f2["packed_sigma"], slot))
+        print(f"{name:6s} depth-ordered ml={ml:2d}: sort {t_sort:.3f} + encode {t_e:.3f} + sigma/scatter {t_s:.3f} = "
+              f"{t_sort + t_e + t_s:.3f} ms  bit-identical {same}", flush=True)

@@ -1,5 +1,5 @@
-"""bf16x3 shading (ucsa_composite_infer_x3) on the bench's chunk: time per
-launch shape, and distance to the f32-input MFMA kernel / the f16 one.
+"""bf16x3 shading (ucsa_composite_infer_x3) on the bench's chunk: its time
+and its distance to the f32-input MFMA kernel / the f16 one.
    python tools/x3_bench.py"""
 import os
 import sys
@@ -51,23 +51,9 @@ ref = ops.composite_fwd(d, nrm, zc, sc, hc, zf, sf, hf, f["packed_color"], f["pa
 print("fp32 fused: %.3f ms" % timed(lambda: ops.composite_fwd(d, nrm, zc, sc, hc, zf, sf, hf, f["packed_color"], f["packed_sem"], 40)), flush=True)
 h16 = ops.composite_infer(d, nrm, zc, sc, hc, zf, sf, hf, fh["packed_color"], fh["packed_sem"], 40, half=True)
 print("f16 split: %.3f ms" % timed(lambda: ops.composite_infer(d, nrm, zc, sc, hc, zf, sf, hf, fh["packed_color"], fh["packed_sem"], 40, half=True)), flush=True)
-for v in ("0", "1", "2", "3"):
-    os.environ["UCSA_SHADE_VARIANT"] = v
-    ops.env_reload()   # the library snapshots its switches once per process
-    fn = lambda: ops.composite_infer(d, nrm, zc, sc, hc, zf, sf, hf, pc3, ps3, 40, x3=True)
-    out = fn()
-    torch.cuda.synchronize()
-    ms = timed(fn)
-    print("x3 variant %s: %.3f ms; max |x3 - fp32| image %.3e depth %.3e sem %.3e ; f16: image %.3e sem %.3e" % (
-        v, ms, (out[0] - ref[0]).abs().max(), (out[1] - ref[1]).abs().max(), (out[2] - ref[2]).abs().max(),
-        (h16[0] - ref[0]).abs().max(), (h16[2] - ref[2]).abs().max()), flush=True)
-for v in ("0", "1", "2", "3"):
-    os.environ["UCSA_SHADE_VARIANT"] = v
-    ops.env_reload()   # the library snapshots its switches once per process
-    fn = lambda: ops.composite_infer(d, nrm, zc, sc, hc, zf, sf, hf, fh["packed_color"], fh["packed_sem"], 40, half=True)
-    out = fn()
-    torch.cuda.synchronize()
-    print("f16 variant %s: %.3f ms; identical to variant 0: %s" % (
-        v, timed(fn), torch.equal(out[0], h16[0]) and torch.equal(out[2], h16[2])), flush=True)
-os.environ.pop("UCSA_SHADE_VARIANT")
-ops.env_reload()   # the library snapshots its switches once per process
+fn = lambda: ops.composite_infer(d, nrm, zc, sc, hc, zf, sf, hf, pc3, ps3, 40, x3=True)
+out = fn()
+torch.cuda.synchronize()
+print("x3 split: %.3f ms; max |x3 - fp32| image %.3e depth %.3e sem %.3e ; f16: image %.3e sem %.3e" % (
+    timed(fn), (out[0] - ref[0]).abs().max(), (out[1] - ref[1]).abs().max(), (out[2] - ref[2]).abs().max(),
+    (h16[0] - ref[0]).abs().max(), (h16[2] - ref[2]).abs().max()), flush=True)

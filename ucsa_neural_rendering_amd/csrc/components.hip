@@ -259,10 +259,7 @@ bool cc_overlap(const void* p, uint64_t pn, const void* q, uint64_t qn) {
   return a < b + qn && b < a + pn;
 }
 
-bool cc_no_lds() {
-  const char* e = ucsa_getenv("UCSA_COMPONENTS_NO_LDS");
-  return e && e[0] == '1';
-}
+bool cc_no_lds() { return ucsa_env().components_no_lds; }
 
 }  // namespace
 

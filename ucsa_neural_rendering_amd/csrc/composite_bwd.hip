@@ -775,13 +775,8 @@ static void shade_bwd_geometry(uint32_t N, uint32_t& rpw, uint32_t& blocks,
 }
 
 // fp32 kernel as a per-net pair (NET = 1 then 2, two waves per SIMD each):
-// UCSA_SHADE_BWD_SPLIT=0 keeps the single kernel (one wave per SIMD).  Read
-// from the env table on every call (no cache of its own), so the switch
-// follows ucsa_env_reload() like the table's other switches.
-static bool shade_bwd_split() {
-  const char* e = ucsa_getenv("UCSA_SHADE_BWD_SPLIT");
-  return !(e && e[0] == '0');
-}
+// UCSA_SHADE_BWD_SPLIT=0 keeps the single kernel (one wave per SIMD).
+static bool shade_bwd_split() { return ucsa_env().shade_bwd_split; }
 
 // number of per-wave partial slots the caller must provide
 extern "C" uint32_t ucsa_composite_bwd_parts(uint32_t N) {

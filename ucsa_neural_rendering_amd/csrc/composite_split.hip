@@ -1110,12 +1110,8 @@ static int32_t launch_shade16(const ShArgs& a, uint32_t n_waves, bool off32,
 
 // Launch shapes (waves per workgroup, column blocks per group).  The register
 // budget follows from the workgroup size: 16 waves -> 128 VGPRs, 12 -> 168,
-// 8 -> 256.  UCSA_SHADE_VARIANT selects another shape for experiments
-// (tools/composite_split_bench.py); results do not depend on it.
-static int shade_variant() {
-  const char* v = ucsa_getenv("UCSA_SHADE_VARIANT");
-  return v ? atoi(v) : 0;
-}
+// 8 -> 256.  One shape per precision: the measured winner (table in
+// composite_infer; the losing shapes are no longer compiled).
 
 static int32_t composite_infer(int prec, const float* rays_d,
                                const float* norms, const float* z_c,
@@ -1150,13 +1146,10 @@ static int32_t composite_infer(int prec, const float* rays_d,
                        : (void*)((char*)counts + (((size_t)N * 4 + 255) & ~(size_t)255));
   const uint32_t nrb = cs_pad16(n_classes) / 16;
   const uint32_t cstride = 16 * nrb + 4;  // k_shade_dense's CSTRIDE
-  const int variant = shade_variant();
-  // (waves per workgroup, column blocks per group) of the shading kernel;
-  // UCSA_SHADE_VARIANT picks another shape for experiments
-  // (tools/composite_split_bench.py), results do not depend on it.
-  //   fp32 (k_shade_dense): 0 = (16, 1), 1 = (12, 2), 2 = (8, 2) -- all behind
-  //     the fused k_composite, which ucsa_render_fwd keeps for fp32
-  //   f16 / bf16x3 (k_shade16): see launch table below
+  // (waves per workgroup, column blocks per group) of the shading kernel:
+  //   fp32 (k_shade_dense): (16, 1) -- behind the fused k_composite, which
+  //     ucsa_render_fwd keeps for fp32
+  //   f16 / bf16x3 / f16x2 (k_shade16): see launch table below
   // both kernels use the same ranges of whole rays per wave: enough waves to
   // fill the chip twice over
   const uint64_t total_waves = 256ull * 16 * 2;
@@ -1186,17 +1179,12 @@ static int32_t composite_infer(int prec, const float* rays_d,
            list_w, list_row, list_ray, counts, N, S, n_classes, rpw, image,
            semantics, sh};
   if (prec == 0) {
-    const uint32_t waves = variant == 0 ? 16u : (variant == 1 ? 12u : 8u);
+    const uint32_t waves = 16u;
     const size_t w_floats = 7168 + 1024 + (size_t)nrb * 1024;
     const size_t per_wave = 16 * (size_t)cstride + 64;
     const size_t smem = (w_floats + waves * per_wave) * 4;
     const uint32_t blocks = ucsa_div_up(n_waves, waves);
-#define SH_GO(NRB)                                                         \
-  do {                                                                     \
-    if (variant == 0) return launch_shade<NRB, 1, 16>(b, blocks, smem, s); \
-    if (variant == 1) return launch_shade<NRB, 2, 12>(b, blocks, smem, s); \
-    return launch_shade<NRB, 2, 8>(b, blocks, smem, s);                    \
-  } while (0)
+#define SH_GO(NRB) return launch_shade<NRB, 1, 16>(b, blocks, smem, s)
     switch (nrb) {
       case 1: SH_GO(1);
       case 2: SH_GO(2);
@@ -1210,8 +1198,8 @@ static int32_t composite_infer(int prec, const float* rays_d,
   // makes; the 64-bit form covers the rest of the C API's range
   const uint64_t rows = (uint64_t)N * (T > t ? T : t);
   const bool off32 = rows * 64 < (1ull << 32) && (uint64_t)N * 96 < (1ull << 32);
-  // measured on the bench's 61 440-ray chunk (ms, k_weights_compact's 0.14
-  // included; round 3, tools/x3_bench.py):
+  // the shapes tried, measured on the bench's 61 440-ray chunk (ms,
+  // k_weights_compact's 0.14 included; round 3, tools/x3_bench.py); 0 stayed:
   //   f16:    0 = (16 waves, 1 block) 0.55 <- default   1 = (8, 2) 0.61
   //           2 = (8, 1) 0.55   3 = (12, 1) 0.57
   //   bf16x3: 0 = (8 waves, 1 block) 1.43 <- default   1 = (16, 1) 1.50
@@ -1220,24 +1208,11 @@ static int32_t composite_infer(int prec, const float* rays_d,
   //           17.87 <- default   1 = (16, 1) 17.25   2 = (12, 1) 17.31
   //           3 = (8, 1) 17.25: with half the MFMAs a weight fragment read from
   //           LDS is worth sharing between two column blocks
-#define SH_GO16(NRB)                                                                \
-  do {                                                                              \
-    if (prec == 3) {                                                                \
-      if (variant == 1) return launch_shade16<NRB, 1, 3, 16>(b, n_waves, off32, s); \
-      if (variant == 2) return launch_shade16<NRB, 1, 3, 12>(b, n_waves, off32, s); \
-      if (variant == 3) return launch_shade16<NRB, 1, 3, 8>(b, n_waves, off32, s);  \
-      return launch_shade16<NRB, 2, 3, 8>(b, n_waves, off32, s);                    \
-    }                                                                               \
-    if (prec == 2) {                                                                \
-      if (variant == 1) return launch_shade16<NRB, 1, 2, 16>(b, n_waves, off32, s); \
-      if (variant == 2) return launch_shade16<NRB, 1, 2, 12>(b, n_waves, off32, s); \
-      if (variant == 3) return launch_shade16<NRB, 2, 2, 8>(b, n_waves, off32, s);  \
-      return launch_shade16<NRB, 1, 2, 8>(b, n_waves, off32, s);                    \
-    }                                                                               \
-    if (variant == 1) return launch_shade16<NRB, 2, 1, 8>(b, n_waves, off32, s);    \
-    if (variant == 2) return launch_shade16<NRB, 1, 1, 8>(b, n_waves, off32, s);    \
-    if (variant == 3) return launch_shade16<NRB, 1, 1, 12>(b, n_waves, off32, s);   \
-    return launch_shade16<NRB, 1, 1, 16>(b, n_waves, off32, s);                     \
+#define SH_GO16(NRB)                                                            \
+  do {                                                                          \
+    if (prec == 3) return launch_shade16<NRB, 2, 3, 8>(b, n_waves, off32, s);   \
+    if (prec == 2) return launch_shade16<NRB, 1, 2, 8>(b, n_waves, off32, s);   \
+    return launch_shade16<NRB, 1, 1, 16>(b, n_waves, off32, s);                 \
   } while (0)
   switch (nrb) {
     case 1: SH_GO16(1);

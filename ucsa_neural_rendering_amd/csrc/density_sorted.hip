@@ -164,10 +164,6 @@ int32_t ucsa_hashgrid_encode_sorted_from(const ucsa_grid* grid, const float* tab
                                          uint32_t image_width, uint32_t first_level,
                                          float* feat, void* stream);
 
-#ifndef UCSA_DENSITY_LEVELS_DEFAULT
-#define UCSA_DENSITY_LEVELS_DEFAULT 12
-#endif
-
 extern "C" int32_t ucsa_density_sorted(
     int32_t mode, const ucsa_grid* grid, const float* table, const float* rays_o,
     const float* rays_d, const float* z_sorted, const uint8_t* pix,
@@ -189,9 +185,7 @@ extern "C" int32_t ucsa_density_sorted(
   // measured on the cfg2 view: 15.68 ms with 8, 15.07 ms with 12 (20.4 M rays/s): with
   // levels 8-11 inside as well only the four levels bound by line fills keep their own
   // launch, and three quarters of the feature round trip are gone
-  const char* lv = ucsa_getenv("UCSA_DENSITY_LEVELS");
-  const int lvn = lv ? atoi(lv) : UCSA_DENSITY_LEVELS_DEFAULT;
-  const uint32_t nenc = lvn >= 16 ? 16u : (lvn >= 12 ? 12u : 8u);
+  const uint32_t nenc = ucsa_env().density_levels;
   if (nenc < 16u) {
     const int32_t rc = ucsa_hashgrid_encode_sorted_from(grid, table, rays_o, rays_d, z_sorted,
                                                         pix, aabb_host, N, T, image_width,

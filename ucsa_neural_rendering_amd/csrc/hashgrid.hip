@@ -312,12 +312,9 @@ static uint32_t coarse_levels(const ucsa_grid* grid) {
 // gather is FASTER on every level -- coarse pass 0.80 -> 0.64 ms, fine pass
 // 1.41 -> 1.23 ms -- the x-pair trick of rounds 1-2 (then a gain on the
 // ray-ordered kernel) costs more VALU issue than the accesses it saves now
-// that the lanes of a tile share their cache lines.  `env` overrides the
-// default for experiments; results do not depend on it.
-static uint32_t simple_gather_below(const char* env, uint32_t dflt) {
-  const char* v = ucsa_getenv(env);
-  return v && *v ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
-}
+// that the lanes of a tile share their cache lines.  UCSA_ENC_SIMPLE / _H /
+// _RAYS (env.h: per kernel and table type) override the default for
+// experiments; results do not depend on them.
 
 template <bool FROM_RAYS, typename TT = float2, typename FT = float2>
 static int32_t launch_encode(const ucsa_grid* grid, const void* table,
@@ -337,7 +334,7 @@ static int32_t launch_encode(const ucsa_grid* grid, const void* table,
     hipLaunchKernelGGL((k_hashgrid_encode<FROM_RAYS, TT, FT>),
                        dim3(ucsa_div_up(M, 256), grid->n_levels - nc), blk, 0,
                        (hipStream_t)stream, gd, nc,
-                       simple_gather_below("UCSA_ENC_SIMPLE_RAYS", 0u),
+                       ucsa_env().enc_simple_rays,
                        (const TT*)table, a, b, z, bb, T, M, (FT*)feat);
   return ucsa_launch_status();
 }
@@ -367,13 +364,13 @@ extern "C" int32_t ucsa_hashgrid_encode_rays(
 // profiles/r03_encode_level_order.txt).  UCSA_ENC_ORDER (experiments only;
 // results do not depend on it): "k:l0,l1,..." = k levels per grid row in the
 // given order.
-static LevelMap level_map(uint32_t L) {
+static LevelMap level_map(uint32_t L, const UcsaEnvText& order) {
   LevelMap lm;
   lm.k = 1;
   lm.simple_below = 0u;   // set per table type by the caller
   for (uint32_t i = 0; i < UCSA_MAX_LEVELS; ++i) lm.lv[i] = (uint8_t)(i < L ? L - 1 - i : 0);
-  const char* e = ucsa_getenv("UCSA_ENC_ORDER");
-  if (e && *e) {
+  if (order.present) {
+    const char* e = order.value;
     const uint32_t k = (uint32_t)strtoul(e, nullptr, 10);
     const char* c = strchr(e, ':');
     if (k >= 1 && L % k == 0 && c) {
@@ -422,25 +419,16 @@ static int32_t launch_encode_image(const ucsa_grid* grid, const void* table,
     const uint32_t rows = ucsa_div_up(N, image_width);
     const uint32_t tiles = ((image_width + 7u) / 8u) * ((rows + 7u) / 8u);
     const uint32_t s_blocks = ucsa_div_up(T, TILE_S);
-    LevelMap lm = level_map(grid->n_levels);
-    // fp32 table: plain gather on every level (measured faster, see
-    // simple_gather_below); half2 table: its group-of-four form stays
-    lm.simple_below = sizeof(TT) == 8
-                          ? simple_gather_below("UCSA_ENC_SIMPLE", UCSA_MAX_LEVELS)
-                          : simple_gather_below("UCSA_ENC_SIMPLE_H", 0u);
-    // UCSA_ENC_LDS_PAD (experiments only, tools/coresident_exp.py): extra
-    // dynamic LDS per workgroup = fewer encoder workgroups per CU, i.e. free
-    // registers / wave slots for a co-resident kernel.  Results do not change.
-    static const uint32_t lds_pad = []() {
-      const char* v = ucsa_getenv("UCSA_ENC_LDS_PAD");
-      return v && *v ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
-    }();
+    const UcsaEnv& env = ucsa_env();
+    LevelMap lm = level_map(grid->n_levels, env.enc_order);
+    // fp32 table: plain gather on every level (measured faster, see above
+    // launch_encode); half2 table: its group-of-four form stays
+    lm.simple_below = sizeof(TT) == 8 ? env.enc_simple : env.enc_simple_h;
     // levels [0, n_ml) through the several-levels-per-workgroup kernel (see
     // k_hashgrid_encode_tiled_ml); UCSA_ENC_ML overrides (experiments only:
     // the features do not depend on it), 0 = every level through the
     // per-level kernel as in rounds 3-4.  Only for the default level order.
-    const char* ml_v = ucsa_getenv("UCSA_ENC_ML");
-    const int ml_env = ml_v && *ml_v ? (int)strtol(ml_v, nullptr, 10) : -1;
+    const int ml_env = env.enc_ml;
     // measured on the bench's chunk (tools/encode_ml_sweep.py, ms by n_ml):
     //   fp32 table  coarse pass 0: 0.702  4: 0.620  8: 0.607  9: 0.603  10: 0.600  12: 0.603  16: 0.824
     //               fine pass   0: 1.283  4: 1.259  8: 1.248  9: 1.247  10: 1.254  12: 1.298  16: 1.686
@@ -448,12 +436,12 @@ static int32_t launch_encode_image(const ucsa_grid* grid, const void* table,
     //   (its per-level kernel has the group-of-four gather on the hashed levels)
     uint32_t n_ml = ml_env >= 0 ? (uint32_t)ml_env : (sizeof(TT) == 8 ? 9u : 6u);
     if (n_ml > grid->n_levels) n_ml = grid->n_levels;
-    if (lm.k != 1 || ucsa_getenv("UCSA_ENC_ORDER")) n_ml = 0;
+    if (lm.k != 1 || env.enc_order.present) n_ml = 0;
     const uint32_t n_fine = grid->n_levels - n_ml;
     if (n_fine > 0)   // lm.lv = finest level first: its first n_fine rows
       hipLaunchKernelGGL((k_hashgrid_encode_tiled<TT, FT>),
                          dim3(tiles * s_blocks * lm.k, n_fine / lm.k),
-                         dim3(256), lds_pad, (hipStream_t)stream, gd, lm,
+                         dim3(256), 0, (hipStream_t)stream, gd, lm,
                          (const TT*)table, rays_o, rays_d, z, bb, T, N,
                          image_width, s_blocks, (FT*)feat);
     if (n_ml > 0)

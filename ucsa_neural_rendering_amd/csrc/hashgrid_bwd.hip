@@ -103,7 +103,7 @@ struct RunPlan {
 // The scans run on the DPP data path (round 6; rounds 2-5 used __shfl_up, i.e.
 // ds_bpermute_b32 -- an LDS instruction with its latency in a dependent chain, two
 // per live step for each of the 16 values of a sample; a DPP step is one VALU
-// instruction.  Measured in round 6, tools/bwd_switches_ab.py: merged grid backward
+// instruction.  Measured in round 6, profiles/r06_bwd_switches_ab.txt: merged grid backward
 // 1.420 -> 1.361 ms with the 8-byte records, 1.205 -> 1.162 ms with x-pair records;
 // rel L2 5e-8 against the shuffle ladder, tests/test_dpp_run_scan_model_cpu.py is
 // its numpy model).  Ladder: row_shr 1 / 2 / 4 / 8 inside the 16-lane rows, row_bcast15 into
@@ -656,7 +656,7 @@ k_grid_bwd_accum(GridDev g, BinGeom bg, uint32_t level0,
 // x-PAIR records: the packed ("p64") records of ucsa_hashgrid_bwd_rays_p64 /
 // _merged_p64 (written at the end of round 5, timed and made the default in round 6:
 // merged grid backward 1.420 -> 1.162 ms, training step 3.41 -> 3.16 ms,
-// tools/bwd_switches_ab.py; the one-record-per-corner kernels they replace are gone).
+// profiles/r06_bwd_switches_ab.txt; the one-record-per-corner kernels they replace are gone).
 //
 // The bin kernel is issue- and LDS-atomic-bound (~82 VALU instructions per
 // record, profiles/r04_train_sq_counters.txt), not byte-bound: what costs is the
@@ -936,13 +936,9 @@ struct BwdSide {
 static BwdSide* bwd_side(hipStream_t caller) {
   static std::mutex mu;
   static BwdSide slots[64];
-  static int enabled = -1;
+  // (read per call: streams made while the switch was on stay, unused, when it goes off)
+  if (!ucsa_env().bwd_overlap) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
-  if (enabled < 0) {
-    const char* e = ucsa_getenv("UCSA_BWD_OVERLAP");
-    enabled = !(e && e[0] == '0');
-  }
-  if (!enabled) return nullptr;
   int dev = -1;
   hipDevice_t sdev;
   if (caller && hipStreamGetDevice(caller, &sdev) == hipSuccess) dev = (int)sdev;
@@ -987,10 +983,7 @@ static int32_t hashgrid_bwd_launch(const ucsa_grid* grid, const float* rays_o,
     n_lo = 0;
     // UCSA_BWD_BIN_SCALE (tuning only; the result does not depend on it):
     // hashed levels with scale >= this go through the bins
-    static const float bin_scale = []() {
-      const char* v = ucsa_getenv("UCSA_BWD_BIN_SCALE");
-      return v && *v ? (float)atof(v) : 100.0f;  // measured: 160 -> 4.81, 100 -> 4.76, 60 -> 5.04 ms per step
-    }();
+    const float bin_scale = ucsa_env().bwd_bin_scale;  // measured: 160 -> 4.81, 100 -> 4.76, 60 -> 5.04 ms per step
     while (n_lo < grid->n_levels && (!grid->level[n_lo].hashed ||
                                      grid->level[n_lo].scale < bin_scale)) ++n_lo;
   }

@@ -314,7 +314,7 @@ __device__ __noinline__ void dense_corners_wrapped(const TT* __restrict__ tab,
 }
 
 // base_off: byte offset of the level inside `tab` when the level is not
-// wave-uniform (encode_sigma_sorted.hip: one scalar base for the whole table,
+// wave-uniform (density_sorted.hip: one scalar base for the whole table,
 // the level's offset per lane); 0 with `tab` already at the level.
 template <typename TT>
 __device__ __forceinline__ float2 encode_cell(const TT* __restrict__ tab,

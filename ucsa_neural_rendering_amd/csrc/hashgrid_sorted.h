@@ -1,5 +1,5 @@
 // Tile geometry and per-sample position of the depth-ordered kernels
-// (hashgrid_sorted.hip, encode_sigma_sorted.hip).
+// (hashgrid_sorted.hip, density_sorted.hip).
 #pragma once
 #include "hashgrid_common.h"
 

@@ -272,7 +272,7 @@ k_tile_depth_order2(const float* __restrict__ z, uint32_t rows, uint32_t T,
 
 // One level per grid row (finest level first: level = l_top - blockIdx.y), a
 // workgroup = 1024 consecutive samples of a tile's depth order.
-template <typename TT, typename FT, bool LEAN>
+template <typename TT, typename FT>
 __global__ void __launch_bounds__(256)
 k_hashgrid_encode_sorted(GridDev g, uint32_t l_top, const TT* __restrict__ table,
                          const float* __restrict__ rays_o,
@@ -303,8 +303,7 @@ k_hashgrid_encode_sorted(GridDev g, uint32_t l_top, const TT* __restrict__ table
     const uint32_t p = pix[tg.base + rank];
     float ux, uy, uz;
     unit_position(ray_s, p, zz, bb, g.bound, two_b, inv, ux, uy, uz);
-    const float2 f = LEAN ? encode_cell(tab, ux, uy, uz, scale, res, res * res, entries, hashed)
-                          : encode_level(tab, ux, uy, uz, scale, res, entries, hashed);
+    const float2 f = encode_cell(tab, ux, uy, uz, scale, res, res * res, entries, hashed);
     FT o;
     to_feat(o, f);
     feat_store(feat_level + rank, o);
@@ -434,15 +433,9 @@ extern "C" int32_t ucsa_tile_depth_order(const float* z, uint32_t N, uint32_t T,
   // (128 slabs x 64 pixels x 4 B = 32 KiB of LDS)
   uint32_t nbins = 16u;
   while (nbins < T && nbins < 128u) nbins <<= 1;
-  const char* nb = ucsa_getenv("UCSA_SORT_BINS");   // experiments only
-  if (nb && *nb) {
-    const uint32_t v = (uint32_t)strtoul(nb, nullptr, 10);
-    if (v >= 1u && v <= 128u) nbins = v;
-  }
-  const char* sv = ucsa_getenv("UCSA_SORT_EXACT");   // experiments only; default on
-  const bool exact = T <= 256u && !(sv && sv[0] == '0');
+  const bool exact = T <= 256u && ucsa_env().sort_exact;   // (experiments only; default on)
   UCSA_CLEAR_ERR();
-  if (exact && !(nb && *nb)) {
+  if (exact) {
     // hist + depths (4 B) + rank and inverse map (2 B each) per sample: 52 KiB at
     // T = 96, 144 KiB at T = 256 (a workgroup may hold all 160 KiB of a CU)
     const uint32_t lds = SORT_BINS1 * (uint32_t)sizeof(uint32_t) + 64u * T * 8u;
@@ -472,31 +465,19 @@ static int32_t launch_sorted(const ucsa_grid* grid, const float* table,
   const uint32_t s_blocks = ucsa_div_up(64u * T, 1024u);
   const uint32_t M = N * T;
   // levels [0, n_ml) through the several-levels kernel (UCSA_ENC_SORTED_ML:
-  // experiments only); UCSA_ENC_SORTED_LEAN=0: the fine levels' gather as
-  // hashgrid.hip's encode_level instead of encode_cell.  Same features.
-  auto env_u = [](const char* name, uint32_t dflt) {
-    const char* v = ucsa_getenv(name);
-    return v && *v ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
-  };
-  uint32_t n_ml = env_u("UCSA_ENC_SORTED_ML", 9u);
+  // experiments only).  Same features.
+  uint32_t n_ml = ucsa_env().enc_sorted_ml;
   if (n_ml > grid->n_levels) n_ml = grid->n_levels;
   // first_level > 0: only levels [first_level, L), one level per grid row (the
-  // levels below are computed by the consumer, encode_sigma_sorted.hip)
+  // levels below are computed by the consumer, density_sorted.hip)
   if (first_level > 0u) n_ml = first_level;
-  const bool lean = env_u("UCSA_ENC_SORTED_LEAN", 1u) != 0u;
   UCSA_CLEAR_ERR();
   if (n_ml < grid->n_levels) {
     const dim3 g(tiles * s_blocks, grid->n_levels - n_ml);
-    if (lean)
-      hipLaunchKernelGGL((k_hashgrid_encode_sorted<float2, FT, true>), g, dim3(256), 0,
-                         (hipStream_t)stream, gd, grid->n_levels - 1u,
-                         (const float2*)table, rays_o, rays_d, z_sorted, pix, bb, T,
-                         rows, image_width, s_blocks, M, (FT*)feat);
-    else
-      hipLaunchKernelGGL((k_hashgrid_encode_sorted<float2, FT, false>), g, dim3(256), 0,
-                         (hipStream_t)stream, gd, grid->n_levels - 1u,
-                         (const float2*)table, rays_o, rays_d, z_sorted, pix, bb, T,
-                         rows, image_width, s_blocks, M, (FT*)feat);
+    hipLaunchKernelGGL((k_hashgrid_encode_sorted<float2, FT>), g, dim3(256), 0,
+                       (hipStream_t)stream, gd, grid->n_levels - 1u,
+                       (const float2*)table, rays_o, rays_d, z_sorted, pix, bb, T,
+                       rows, image_width, s_blocks, M, (FT*)feat);
   }
   if (n_ml > 0 && first_level == 0u)
     hipLaunchKernelGGL((k_hashgrid_encode_sorted_ml<float2, FT>), dim3(tiles * s_blocks),
@@ -548,7 +529,7 @@ extern "C" int32_t ucsa_hashgrid_encode_sorted_hf(
                                    stream);
 }
 
-// levels [first_level, L) only (see encode_sigma_sorted.hip)
+// levels [first_level, L) only (see density_sorted.hip)
 int32_t ucsa_hashgrid_encode_sorted_from(const ucsa_grid* grid, const float* table,
                                          const float* rays_o, const float* rays_d,
                                          const float* z_sorted, const uint8_t* pix,

@@ -8,62 +8,6 @@
 
 #include "ucsa_common.h"
 
-#include <cassert>
-#include <cstring>
-
-// ---------------------------------------------------------------------------
-// Environment switches: ONE table, snapshotted once per process (VERDICT r5 item
-// 10: they used to be getenv() calls on every C call).  None of them changes a
-// result; INTEGRATION.md lists what each selects.
-// ---------------------------------------------------------------------------
-namespace {
-const char* const kEnvNames[] = {
-    // launch shapes / kernel choices of the render path
-    "UCSA_SHADE_VARIANT", "UCSA_SPLIT_COMPOSITE", "UCSA_ENC_SORTED", "UCSA_ENC_ML",
-    "UCSA_DENSITY_FUSED", "UCSA_DENSITY_LEVELS",
-    "UCSA_ENC_SORTED_ML", "UCSA_ENC_SORTED_LEAN",
-    // ... of the training path
-    "UCSA_SHADE_BWD_SPLIT", "UCSA_BWD_OVERLAP", "UCSA_BWD_BIN_SCALE",
-    // lab only (tools/encode_*.py, tools/coresident_exp.py)
-    "UCSA_ENC_ORDER", "UCSA_ENC_SIMPLE", "UCSA_ENC_SIMPLE_H", "UCSA_ENC_SIMPLE_RAYS",
-    "UCSA_ENC_LDS_PAD", "UCSA_SORT_BINS", "UCSA_SORT_EXACT",
-    // lab only (tools/components_time.py): the lattice labelling without its LDS stage
-    "UCSA_COMPONENTS_NO_LDS"};
-constexpr int kEnvCount = (int)(sizeof(kEnvNames) / sizeof(kEnvNames[0]));
-struct EnvTable {
-  char value[kEnvCount][64];
-  bool set[kEnvCount];
-  void load() {
-    for (int i = 0; i < kEnvCount; ++i) {
-      const char* v = getenv(kEnvNames[i]);
-      set[i] = v && *v && strlen(v) < sizeof(value[i]);
-      if (set[i]) strcpy(value[i], v);
-    }
-  }
-};
-std::mutex env_mu;
-EnvTable* env_table() {
-  static EnvTable t = []() { EnvTable x; x.load(); return x; }();   // once, thread-safe
-  return &t;
-}
-}  // namespace
-
-const char* ucsa_getenv(const char* name) {
-  EnvTable* t = env_table();
-  for (int i = 0; i < kEnvCount; ++i)
-    if (strcmp(name, kEnvNames[i]) == 0) return t->set[i] ? t->value[i] : nullptr;
-  assert(!"ucsa_getenv: a name that is not in kEnvNames");
-  return nullptr;
-}
-
-// lab tools and tests that flip a switch inside one process (tools/bwd_switches_ab.py,
-// tests of the alternative kernels); not for production code, not thread-safe
-// against concurrent calls into the library
-extern "C" void ucsa_env_reload(void) {
-  std::lock_guard<std::mutex> lk(env_mu);
-  env_table()->load();
-}
-
 namespace {
 struct Ws {
   float *nears, *fars, *z_c, *z_f, *feat, *h_c, *sigma_c, *h_f, *sigma_f;
@@ -138,26 +82,12 @@ static int32_t encode(const ucsa_grid* grid, const void* table_any,
                                    T, feat, stream);
 }
 
-#ifndef UCSA_ENC_SORTED_DEFAULT
-#define UCSA_ENC_SORTED_DEFAULT 2
-#endif
-
-static bool density_fused() {
-  const char* v = ucsa_getenv("UCSA_DENSITY_FUSED");
-  return !(v && v[0] == '0');
-}
-
 // Which composite: the f32-input MFMA is bound by the matrix pipe itself (352
 // MFMAs per 32 samples = 1.62 ms per 61 440-ray chunk at 100 % of the pipe)
 // and the fused k_composite (2.25 ms) beats the split pair there (2.5-2.8 ms);
-// the split pair wins once the nets run on the 16-bit MFMA pipe (f16, bf16x3).
-// UCSA_SPLIT_COMPOSITE=0/1 overrides (bf16x3 exists as the split pair only).
-static bool split_composite(int prec) {
-  if (prec >= 2) return true;
-  const char* v = ucsa_getenv("UCSA_SPLIT_COMPOSITE");
-  if (v && (v[0] == '0' || v[0] == '1')) return v[0] == '1';
-  return prec == 1;
-}
+// the split pair wins once the nets run on the 16-bit MFMA pipe (f16, bf16x3;
+// bf16x3 and f16x2 exist as the split pair only).
+static bool split_composite(int prec) { return prec >= 1; }
 
 // prec: 0 = f32-input MFMA nets (packed by ucsa_mlp_pack), 1 = f16 MFMA
 // (ucsa_mlp_pack_f16), 2 = bf16x3 (ucsa_mlp_pack_x3), 3 = f16x2
@@ -203,8 +133,9 @@ static int32_t render_impl(int prec, const ucsa_grid* grid,
   // than it brings (cfg3's joint step 178.7 ms sorted) while the index order wins
   // (171.8 ms with that pass image-ordered -> 168.0).  Same h / sigma bits whatever the
   // mode (profiles/r06_density_fused_ab.txt).
-  const char* es = ucsa_getenv("UCSA_ENC_SORTED");
-  const int sorted_mode = es && es[0] >= '0' && es[0] <= '4' ? es[0] - '0' : UCSA_ENC_SORTED_DEFAULT;
+  const UcsaEnv& env = ucsa_env();
+  const int sorted_mode = env.enc_sorted;
+  const bool density_fused = env.density_fused;
   // encode + sigma MLP of one pass (z [N,n] -> h, sigma)
   auto density = [&](const float* z, uint32_t n, float* h, float* sigma) -> int32_t {
     const bool fine = z == w.z_f;
@@ -218,7 +149,7 @@ static int32_t render_impl(int prec, const ucsa_grid* grid,
               // (the coarse pass only where the fused kernel takes it: with the staged
               // encoder + sigma-MLP pair -- fp32 / fp16 nets -- an ordered coarse pass is
               // slower than the image-ordered tiled one, 16.70 against 16.18 ms per view)
-              : (sorted_mode == 3 || (sorted_mode >= 2 && prec >= 2 && density_fused()))) &&
+              : (sorted_mode == 3 || (sorted_mode >= 2 && prec >= 2 && density_fused))) &&
         !(coarse_long && sorted_mode == 4)) {
       if (coarse_long && sorted_mode == 2)
         UCSA_TRY(ucsa_tile_index_order(z, N, n, image_width, w.zs_sorted, w.pix,
@@ -229,7 +160,7 @@ static int32_t render_impl(int prec, const ucsa_grid* grid,
       // bf16x3 / f16x2 nets: levels 0-11 are encoded INSIDE the sigma MLP (their
       // features never travel through HBM: density_sorted.hip; same h / sigma
       // bits; UCSA_DENSITY_FUSED=0 keeps the staged pair for A/B runs)
-      if (prec >= 2 && density_fused())
+      if (prec >= 2 && density_fused)
         return ucsa_density_sorted(prec, grid, table, rays_o, rays_d, w.zs_sorted,
                                    w.pix, w.slot, aabb_host, N, n, image_width,
                                    packed_sigma, w.feat, h, sigma, stream);
