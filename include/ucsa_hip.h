@@ -2516,6 +2516,102 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
                            uint64_t workspace_doubles, double* sums, float* value,
                            uint8_t* matched, void* stream);
 
+/* ---- The depth front end: bilateral filter, points, normals, edge rejection
+ * (not in the reference) -----------------------------------------------------
+ * What KinectFusion does to a depth frame before it integrates or tracks it
+ * (utils/depth_frontend.py): everything above reads depth[v][u] as the sensor
+ * gave it.  Three entry points over depth [B,H,W] fp32 z-depth on the device;
+ * fx, fy, cx, cy, depth_min, depth_max and every threshold are HOST scalars.
+ * All arithmetic is fp32, every operation as written, no contraction, division
+ * and sqrt correctly rounded; tests/depth_numpy.py restates the three contracts
+ * and every output equals it bit for bit.  One thread per pixel, a work-group
+ * per 16 x 16 tile, the tile and its halo in LDS; no atomics, no scratch, the
+ * same bytes every run.  The input is never written and must not alias an
+ * output.
+ *
+ * measured(z) iff z is finite and depth_min <= z <= depth_max: the validity
+ * rule of ucsa_tsdf_integrate.  A pixel outside the image is not measured.
+ *
+ * ucsa_depth_filter: a bilateral filter whose weights come from two tables on
+ * the device, so that no exp is evaluated here and the result can be restated
+ * exactly: w_space [(2r+1)^2] fp32, row-major over the window, 1 <= r <= 4,
+ * and w_range [Q] fp32 with Q = UCSA_DEPTH_RANGE_BINS = 256, bin q covering
+ * |z_n - z| in [q, q+1) * 3 sigma / Q.  Per pixel (i, j) with depth z:
+ *   not measured: filtered = 0.  Otherwise
+ *   sigma = sigma_depth + sigma_z2 * (z*z);  scale = 256.0f / (3.0f * sigma);
+ *   num = den = 0; for dy = -r..r, for dx = -r..r (row-major), z_n the depth at
+ *   (i+dy, j+dx), taken iff measured (the centre is):
+ *     d = z_n - z;  t = fabsf(d) * scale;  skipped unless t < 256.0f (NaN skips);
+ *     w = w_space[(dy+r)*(2r+1) + (dx+r)] * w_range[(int)t];
+ *     num = num + w*d;  den = den + w;
+ *   filtered = z + num / den.
+ * The value is an offset from the centre: a constant image comes back with its
+ * own bits and the rounding error does not grow with z.  The tables are the
+ * caller's (ops.depth.bilateral_tables): where they leave den at 0 the result
+ * is a NaN of unspecified payload.
+ * Arguments: depth (0), B >= 1 (1), 1 <= H <= 16384 (2), 1 <= W <= 16384 (3),
+ * w_space (4), r (5), w_range (6), sigma_depth > 0 finite (7), sigma_z2 >= 0
+ * finite (8), depth_min not NaN (9), depth_max >= depth_min (10), filtered
+ * [B,H,W], not depth (11).
+ *
+ * ucsa_depth_normals: per pixel (i, j) with depth z, P(i', j') the point of a
+ * pixel with depth z':
+ *   P = ((((float)j' + 0.5f) - cx) / fx) * z', ((((float)i' + 0.5f) - cy) / fy) * z', z'
+ *   (utils/registration.backproject's expression and order).
+ *   not measured: points = normals = 0, mask = 0.  Otherwise mask bit 1,
+ *   points = p = P(i, j), thr = max_jump + max_jump_z2 * (z*z);
+ *   a neighbour with depth z_n is usable iff measured and fabsf(z_n - z) <= thr;
+ *   mask bit 4 (depth edge) iff one of the eight neighbours is measured and not
+ *   usable;
+ *   du = P(i,j+1) - P(i,j-1) when both are usable, else P(i,j+1) - p, else
+ *   p - P(i,j-1), else there is no normal; dv likewise along i
+ *   (P(i+1,j) - P(i-1,j), ...);
+ *   c = dv x du = (dv1*du2 - dv2*du1, dv2*du0 - dv0*du2, dv0*du1 - dv1*du0);
+ *   nn = (c0*c0 + c1*c1) + c2*c2; no normal unless nn > 0 and finite;
+ *   n = c / sqrtf(nn); dot = (n0*p0 + n1*p1) + n2*p2; if dot > 0: n = -n,
+ *   dot = -dot (the normal faces the camera at the origin);
+ *   cosv = (-dot) / sqrtf((p0*p0 + p1*p1) + p2*p2);
+ *   mask bit 2 (has a normal), bit 8 (grazing) iff cosv < min_cos;
+ *   normals = n, or 0 without a normal.
+ * Arguments: depth (0), B (1), H (2), W (3), fx > 0 finite (4), fy (5), cx
+ * finite (6), cy (7), max_jump >= 0 finite (8), max_jump_z2 >= 0 finite (9),
+ * -1 <= min_cos <= 1 (10), depth_min not NaN (11), depth_max >= depth_min (12),
+ * points [B,H,W,3] (13), normals [B,H,W,3] (14), mask [B,H,W] uint8 (15).
+ *
+ * ucsa_depth_frontend: both in one launch.  filtered is ucsa_depth_filter's
+ * output; points, normals and mask are ucsa_depth_normals' of it, with the same
+ * depth_min / depth_max (with depth_min <= 0 the filter's 0 is a measurement
+ * there, as it would be for the two calls); clean = 0 where mask & reject,
+ * filtered elsewhere: an image ucsa_tsdf_integrate and the vote kernels take.
+ * reject is a set of UCSA_DEPTH_EDGE | UCSA_DEPTH_GRAZING.  A work-group filters
+ * its tile and a halo of one pixel (18 x 18) from a (18 + 2r)^2 load and keeps
+ * the values in LDS; the five outputs are the bytes of the two calls.
+ * Arguments: depth (0), B (1), H (2), W (3), w_space (4), r (5), w_range (6),
+ * sigma_depth (7), sigma_z2 (8), fx (9), fy (10), cx (11), cy (12), max_jump
+ * (13), max_jump_z2 (14), min_cos (15), reject (16), depth_min (17), depth_max
+ * (18), filtered (19), clean (20), points (21), normals (22), mask (23).
+ * An argument error returns UCSA_ERR_ARG - index before any launch. */
+#define UCSA_DEPTH_RANGE_BINS 256u
+#define UCSA_DEPTH_MEASURED 1u
+#define UCSA_DEPTH_NORMAL 2u
+#define UCSA_DEPTH_EDGE 4u
+#define UCSA_DEPTH_GRAZING 8u
+int32_t ucsa_depth_filter(const float* depth, uint32_t B, uint32_t H, uint32_t W,
+                          const float* w_space, uint32_t radius, const float* w_range,
+                          float sigma_depth, float sigma_z2, float depth_min, float depth_max,
+                          float* filtered, void* stream);
+int32_t ucsa_depth_normals(const float* depth, uint32_t B, uint32_t H, uint32_t W, float fx,
+                           float fy, float cx, float cy, float max_jump, float max_jump_z2,
+                           float min_cos, float depth_min, float depth_max, float* points,
+                           float* normals, uint8_t* mask, void* stream);
+int32_t ucsa_depth_frontend(const float* depth, uint32_t B, uint32_t H, uint32_t W,
+                            const float* w_space, uint32_t radius, const float* w_range,
+                            float sigma_depth, float sigma_z2, float fx, float fy, float cx,
+                            float cy, float max_jump, float max_jump_z2, float min_cos,
+                            uint32_t reject, float depth_min, float depth_max, float* filtered,
+                            float* clean, float* points, float* normals, uint8_t* mask,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

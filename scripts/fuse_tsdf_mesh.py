@@ -9,7 +9,7 @@ first stage of the mapping-based pseudo-label baseline.
         [--min_weight K] [--no_color] [--pose_frame] \\
         [--min_component N] [--component_connectivity {6,26}] [--simplify CELL] \\
         [--refine_poses [--refine_warmup K] [--refine_iters N] [--refine_stride S] \\
-         [--refine_min_matched SHARE] [--poses_out FILE.npy]]
+         [--refine_min_matched SHARE] [--poses_out FILE.npy]] [--depth_filter SPEC]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
 ``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement; scene units as
@@ -38,7 +38,14 @@ one (rank below 6, a matched share below ``--refine_min_matched``, a step beyond
 0.1 rad or the truncation distance).  It prints one ``refine:`` line: frames
 refined, fallbacks, median and maximum step in radians and scene units, median
 rmse (over the frames that matched at all); ``--poses_out`` writes the poses used, [N,4,4] float64 in the NGP frame,
-as .npy.  Without the flag nothing changes.  Prints one JSON line last."""
+as .npy.  Without the flag nothing changes.  ``--depth_filter SPEC`` sends every
+frame through the depth front end (``utils.depth_frontend``: bilateral filter,
+normals, rejection of depth-edge and grazing pixels) before it is integrated or
+tracked; SPEC is ``default`` or a comma-separated list of ``DepthFilter``'s
+fields, lengths in metres (``radius=3,sigma_space=1.5,sigma_depth=0.01,
+sigma_z2=0.002,max_jump=0.05,min_cos=0.1,reject_grazing=0``).  It prints one
+``depth_filter:`` line with the share of pixels rejected per bit; without the
+flag nothing changes.  Prints one JSON line last."""
 import argparse
 import json
 import os
@@ -85,6 +92,9 @@ def parse_args(argv=None):
     p.add_argument("--refine_min_matched", type=float, default=0.25,
                    help="a frame with a smaller matched share keeps its given pose")
     p.add_argument("--poses_out", default=None, help="write the poses used (.npy, [N,4,4])")
+    p.add_argument("--depth_filter", default=None, metavar="SPEC",
+                   help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
+                        "lengths in metres (default: off)")
     return p.parse_args(argv)
 
 
@@ -123,12 +133,17 @@ def main(argv=None):
         refine = {"refine_poses": True, "refine_warmup": a.refine_warmup,
                   "refine_min_matched": a.refine_min_matched,
                   "refine_kw": {"iterations": a.refine_iters, "stride": a.refine_stride}}
+    if a.depth_filter is not None:
+        from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
+        refine["depth_filter"] = DepthFilter.from_string(a.depth_filter).scaled(uom)
     mesh = fuse_depth_views(poses, fr["intrinsics"], H, W, depth,
                             color_maps=None if a.no_color else color, aabb=a.aabb,
                             voxel=voxel, trunc=None if a.trunc is None else a.trunc * uom,
                             min_weight=a.min_weight, batch=a.batch,
                             min_component=a.min_component,
                             component_connectivity=a.component_connectivity, **refine)
+    if a.depth_filter is not None:
+        print(stats_line(mesh["depth_filter"]))
     tracked = None
     if a.refine_poses:
         recs = [r for r in mesh["refine"] if r is not None]

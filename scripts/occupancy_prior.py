@@ -4,7 +4,7 @@ fusion on the GPU, then ``ops.tsdf_occupancy`` (``utils/occupancy_prior.py``).
 
     python scripts/occupancy_prior.py --scene_root <root>/<scene> --out prior.npz \\
         [--bound 4] [--voxel METRES] [--trunc METRES] [--dilate METRES] \\
-        [--unknown {keep,empty}] [--every N]
+        [--unknown {keep,empty}] [--every N] [--depth_filter SPEC]
 
 Reads the frames of transforms_train.json (every ``--every``-th) as
 ``scripts/fuse_tsdf_mesh.py`` does: the poses in the field's (NGP) frame and
@@ -15,7 +15,11 @@ the space the sensor saw to be empty; ``empty`` also carves what no view
 observed and everything outside the volume.  Writes the mask and its parameters
 (``utils.occupancy_prior.save_prior``); ``nerf: {cuda_ray: true,
 occupancy_prior: prior.npz}`` in an experiment YAML makes the training loop load
-it.  Prints one ``occupancy_prior:`` line of statistics.
+it.  Prints one ``occupancy_prior:`` line of statistics.  ``--depth_filter SPEC``
+sends every frame through the depth front end (``utils.depth_frontend``) before
+it is integrated; SPEC as for ``scripts/fuse_tsdf_mesh.py`` (``default`` or
+``field=value,...``, lengths in metres).  It prints one ``depth_filter:`` line
+with the share of pixels rejected per bit; without the flag nothing changes.
 
     python scripts/occupancy_prior.py --mesh M.ply [--mesh_pose_frame] --out prior.npz \\
         [--bound 4] [--dilate UNITS] [--H 128]
@@ -58,6 +62,9 @@ def parse_args(argv=None):
     p.add_argument("--dilate", type=float, default=None, help="metres (default: one voxel)")
     p.add_argument("--unknown", choices=("keep", "empty"), default="keep")
     p.add_argument("--every", type=int, default=1, help="use every N-th frame")
+    p.add_argument("--depth_filter", default=None, metavar="SPEC",
+                   help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
+                        "lengths in metres (default: off)")
     a = p.parse_args(argv)
     if (a.scene_root is None) == (a.mesh is None):
         p.error("one of --scene_root (the depth route) and --mesh (the mesh route) is required")
@@ -97,10 +104,16 @@ def main(argv=None):
 
     voxel = a.voxel * uom
     dilate = None if a.dilate is None else a.dilate * uom
+    extra = {}
+    if a.depth_filter is not None:
+        from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
+        extra["depth_filter"] = DepthFilter.from_string(a.depth_filter).scaled(uom)
     mask, st = prior_from_depth_views(poses, fr["intrinsics"], fr["H"], fr["W"], depth, a.bound,
                                       voxel=voxel,
                                       trunc=None if a.trunc is None else a.trunc * uom,
-                                      dilate=dilate, unknown=a.unknown)
+                                      dilate=dilate, unknown=a.unknown, **extra)
+    if a.depth_filter is not None:
+        print(stats_line(st["depth_filter"]))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     save_prior(a.out, mask, a.bound, voxel=np.float32(voxel), trunc=np.float32(st["trunc"]),
                dilate=np.float32(voxel if dilate is None else dilate), unknown=a.unknown,

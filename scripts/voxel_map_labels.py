@@ -46,7 +46,12 @@ more) and prints their statistics; 0 (the default) changes nothing.
 frame, or with ``--gt_pose_frame`` the frame of the JSON poses in metres) takes
 the label of the nearest labelled voxel's centre within ``--gt_max_dist`` scene
 units (default 0.2), and one ``3d: {...}`` line is printed.  Without the flag
-the output is unchanged."""
+the output is unchanged.
+``--depth_filter SPEC`` sends every frame through the depth front end
+(``utils.depth_frontend``) before it is integrated and voted with; SPEC as for
+``scripts/fuse_tsdf_mesh.py`` (``default`` or ``field=value,...``, lengths in
+metres).  It prints one ``depth_filter:`` line with the share of pixels rejected
+per bit; without the flag nothing changes."""
 import argparse
 import json
 import os
@@ -83,6 +88,9 @@ def parse_args(argv=None):
     p.add_argument("--min_component", type=int, default=0,
                    help="drop band components with fewer voxels than this (default 0: off)")
     p.add_argument("--component_connectivity", type=int, choices=(6, 26), default=26)
+    p.add_argument("--depth_filter", default=None, metavar="SPEC",
+                   help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
+                        "lengths in metres (default: off)")
     p.add_argument("--gt_mesh", default=None,
                    help="score the voxel map in 3D at this labelled mesh's vertices (.ply)")
     p.add_argument("--gt_pose_frame", action="store_true",
@@ -175,6 +183,10 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     soft = {} if ssrc is None else {"score_maps": codes, "min_margin": a.min_margin}
+    front = {}
+    if a.depth_filter is not None:
+        from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
+        front = {"depth_filter": DepthFilter.from_string(a.depth_filter).scaled(uom)}
     fused = fuse_semantic_views(poses, fr["intrinsics"], H, W, depth,
                                 None if soft else (lambda i: png(src, i)),
                                 aabb=a.aabb, voxel=a.voxel * uom,
@@ -183,9 +195,12 @@ def main(argv=None):
                                 min_votes=a.min_votes, smooth=a.smooth,
                                 smooth_neighbourhood=a.smooth_neighbourhood,
                                 min_component=a.min_component,
-                                component_connectivity=a.component_connectivity, **soft)
+                                component_connectivity=a.component_connectivity, **soft,
+                                **front)
     torch.cuda.synchronize()
     t_fuse = time.perf_counter() - t0
+    if a.depth_filter is not None:
+        print(stats_line(fused["depth_filter"]))
     vol = fused["volume"]
     far = a.far
     if far is None:

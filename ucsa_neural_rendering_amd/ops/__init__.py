@@ -9,11 +9,11 @@ The wrappers live in one module per family (``render``, ``backward``, ``train``,
 ``_args``; this file only re-exports them, so ``ops.NAME`` is the way in.
 ``raycast`` came after the surface of ``ops`` was frozen and is reached as a
 module: ``ops.raycast.raycast_mesh``; so is ``register``: ``ops.register.icp_sums``,
-``ops.register.tsdf_sums``.
+``ops.register.tsdf_sums``; and ``depth``: ``ops.depth.depth_frontend``.
 """
 from .. import _lib
 from .._lib import Grid, check, fvec, lib
-from . import _args, backward, march, mesh, raycast, register, render, search, train, volume
+from . import _args, backward, depth, march, mesh, raycast, register, render, search, train, volume
 from ._args import (_march_ws, _named_ws, _ptr, _scratch, _scratch_named, _stream,
                     volume_lattice)
 from .backward import *          # noqa: F401,F403  (the modules define no __all__:

@@ -33,9 +33,13 @@ from .tsdf_fusion import depth_points_aabb
 
 def volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel=0.05, trunc=None,
                             aabb=None, batch=16, max_weight=65504.0, depth_min=1e-6,
-                            depth_max=3.0e38, device="cuda"):
+                            depth_max=3.0e38, device="cuda", depth_filter=None,
+                            depth_filter_stats=None):
     """The TSDF volume (``ops.tsdf_volume``, no colour) of the views, chosen and
-    integrated as ``fuse_depth_views`` does -> (volume, trunc, integrate_ms)."""
+    integrated as ``fuse_depth_views`` does -> (volume, trunc, integrate_ms).
+    ``depth_filter`` / ``depth_filter_stats`` as for ``track_depth_views``."""
+    if depth_filter is not None:
+        from . import depth_frontend
     dev = torch.device(device)
     voxel = float(voxel)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
@@ -59,6 +63,9 @@ def volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel=0.05, tru
         b = min(a + batch, N)
         z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
         P = poses[a:b].to(dev)
+        if depth_filter is not None:
+            z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
+                                           stats=depth_filter_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ops.integrate_tsdf(vol, z, P, intrinsics, trunc, max_weight=max_weight,
@@ -69,7 +76,7 @@ def volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel=0.05, tru
 
 
 def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.05, trunc=None,
-                           aabb=None, batch=16, **occupancy_kw):
+                           aabb=None, batch=16, depth_filter=None, **occupancy_kw):
     """``poses`` [N,4,4] camera-to-world (NGP frame), ``depth_maps`` a sequence
     or callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), ``bound``
     the renderer's; ``voxel`` / ``trunc`` (default 4 voxels) / ``aabb`` (None =
@@ -80,9 +87,16 @@ def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.0
     ``observed`` / ``band`` / ``free`` the shares of the volume's voxels with
     weight >= min_weight / observed and not free / observed and free, ``dims``,
     ``origin``, ``spacing``, ``trunc`` and the wall time ``integrate_ms`` /
-    ``occupancy_ms`` (device-synchronised host clock)."""
+    ``occupancy_ms`` (device-synchronised host clock).  ``depth_filter`` (a
+    ``utils.depth_frontend.DepthFilter``) integrates the frames as the depth
+    front end cleans them and adds the rejection counts to the stats as
+    ``depth_filter``; None enters none of it."""
+    df_kw = {}
+    if depth_filter is not None:
+        from . import depth_frontend
+        df_kw = {"depth_filter": depth_filter, "depth_filter_stats": depth_frontend.new_stats()}
     vol, trunc, t_i = volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel, trunc,
-                                              aabb, batch)
+                                              aabb, batch, **df_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     mask = ops.tsdf_occupancy(vol, bound, **occupancy_kw)
@@ -95,6 +109,8 @@ def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.0
              "free": float(free.float().mean()), "dims": tuple(vol["tsdf"].shape),
              "origin": vol["origin"], "spacing": vol["spacing"], "trunc": trunc,
              "integrate_ms": t_i, "occupancy_ms": 1e3 * t_o}
+    if depth_filter is not None:
+        stats["depth_filter"] = df_kw["depth_filter_stats"]
     return mask, stats
 
 

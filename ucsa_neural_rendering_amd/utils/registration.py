@@ -246,8 +246,19 @@ def backproject(depth, intrinsics, stride: int = 1, depth_min: float = 0.0,
     return torch.stack([x, y, z], -1)[ok].contiguous()
 
 
+def _frame_points(d, intrinsics, stride, depth_min, depth_max, depth_filter):
+    """the camera-frame points a frame is registered with: ``backproject``'s, or
+    with a ``depth_filter`` those of the pixels the depth front end keeps"""
+    if depth_filter is None:
+        return backproject(d, intrinsics, stride, depth_min, depth_max)
+    from .depth_frontend import frame_points
+    # the front end's validity rule has no "> 0" of its own: keep backproject's
+    return frame_points(d, intrinsics, depth_filter, stride, max(float(depth_min), 1e-6),
+                        min(float(depth_max), 3.0e38))[0]
+
+
 def refine_pose(depth, pose, intrinsics, grid_or_mesh, stride: int = 1, depth_min: float = 0.0,
-                depth_max: float = math.inf, **kw):
+                depth_max: float = math.inf, depth_filter=None, **kw):
     """Refine the camera-to-world ``pose`` (4x4) of one z-depth frame ``depth``
     [H,W] against a mesh -> ``register_points``' dict with ``pose`` (4x4 float64,
     the refined camera-to-world pose; the same matrix as ``transform``).  The
@@ -255,11 +266,13 @@ def refine_pose(depth, pose, intrinsics, grid_or_mesh, stride: int = 1, depth_mi
     and ``intrinsics`` (fx, fy, cx, cy) as ``ops.integrate_tsdf`` takes them) and
     registered with ``init=pose``.  ``grid_or_mesh``: a mesh dict (``verts``,
     ``faces``), optionally carrying ``grid`` (``ops.triangle_grid``'s dict of it)
-    so that a sequence of frames builds it once."""
+    so that a sequence of frames builds it once.  ``depth_filter`` (a
+    ``utils.depth_frontend.DepthFilter``): the points are those of the filtered
+    frame's pixels that the depth front end keeps; None: ``backproject``'s."""
     import torch
     device = kw.pop("device", "cuda")
     d = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth, np.float32))
-    pts = backproject(d.to(device), intrinsics, stride, depth_min, depth_max)
+    pts = _frame_points(d.to(device), intrinsics, stride, depth_min, depth_max, depth_filter)
     out = register_points(pts, grid_or_mesh["verts"], grid_or_mesh["faces"], init=pose,
                           grid=grid_or_mesh.get("grid"), device=device, **kw)
     out["pose"] = out["transform"]
@@ -338,17 +351,19 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
 
 
 def refine_pose_tsdf(depth, pose, intrinsics, volume, trunc: float, stride: int = 1,
-                     depth_min: float = 0.0, depth_max: float = math.inf, **kw):
+                     depth_min: float = 0.0, depth_max: float = math.inf, depth_filter=None,
+                     **kw):
     """Refine the camera-to-world ``pose`` (4x4) of one z-depth frame ``depth``
     [H,W] against the TSDF ``volume`` as it stands -> ``register_points_tsdf``'s
     dict with ``pose`` (4x4 float64, the same matrix as ``transform``).  The
     valid pixels are back-projected into the camera frame (``backproject``) and
     registered with ``init=pose``: frame-to-model tracking, for a pose whose
-    error at the surface is below ``trunc`` (see ``register_points_tsdf``)."""
+    error at the surface is below ``trunc`` (see ``register_points_tsdf``).
+    ``depth_filter`` as for ``refine_pose``."""
     import torch
     device = kw.pop("device", "cuda")
     d = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth, np.float32))
-    pts = backproject(d.to(device), intrinsics, stride, depth_min, depth_max)
+    pts = _frame_points(d.to(device), intrinsics, stride, depth_min, depth_max, depth_filter)
     out = register_points_tsdf(pts, volume, trunc, init=pose, device=device, **kw)
     out["pose"] = out["transform"]
     return out

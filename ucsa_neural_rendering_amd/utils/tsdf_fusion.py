@@ -126,7 +126,8 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                      voxel=0.05, trunc=None, min_weight=1, batch=16, max_weight=65504.0,
                      depth_min=1e-6, depth_max=3.0e38, device="cuda", min_component=0,
                      component_connectivity=26, refine_poses=False, refine_warmup=1,
-                     refine_kw=None, refine_min_matched=0.25, refine_max_step=None):
+                     refine_kw=None, refine_min_matched=0.25, refine_max_step=None,
+                     depth_filter=None):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps``: a sequence
     or a callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), read
     batch by batch; ``color_maps`` likewise ``i -> [H,W,3]`` uint8 or None;
@@ -146,8 +147,17 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     are integrated one per call, and the dict gains ``poses`` [N,4,4] float64
     (the poses used), ``refine`` (the per-frame records) and ``refine_ms``.
     With ``refine_poses=False`` nothing of that is entered and every byte of the
-    result is what it was."""
+    result is what it was.  ``depth_filter`` (a ``utils.depth_frontend.DepthFilter``)
+    sends every frame through the depth front end first: the volume is
+    integrated with the filtered frames without their rejected pixels, tracking
+    takes the kept pixels' points, and the dict gains ``depth_filter``, the
+    rejection counts (``depth_frontend.stats_line`` prints them).  The box is
+    still that of the raw frames.  None enters none of it."""
     dev = torch.device(device)
+    df_stats = None
+    if depth_filter is not None:
+        from . import depth_frontend
+        df_stats = depth_frontend.new_stats()
     voxel = float(voxel)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
     if not (voxel > 0 and trunc > 0):
@@ -174,7 +184,9 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                                     max_weight=max_weight, depth_min=depth_min,
                                     depth_max=depth_max, refine_warmup=refine_warmup,
                                     refine_kw=refine_kw, refine_min_matched=refine_min_matched,
-                                    refine_max_step=refine_max_step)
+                                    refine_max_step=refine_max_step,
+                                    **({} if depth_filter is None else
+                                       {"depth_filter": depth_filter, "depth_filter_stats": df_stats}))
         t_i = 1e-3 * tracked["integrate_ms"]
     # tracked: every view is in the volume already; otherwise a batch of views per call
     for a in ([] if tracked is not None else range(0, N, batch)):
@@ -188,6 +200,9 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                 raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape[1:]}")
             col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))).to(dev)
         P = poses[a:b].to(dev)
+        if depth_filter is not None:
+            z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
+                                           stats=df_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
@@ -208,6 +223,8 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     if tracked is not None:
         extra.update(poses=tracked["poses"], refine=tracked["refine"],
                      refine_ms=tracked["refine_ms"])
+    if df_stats is not None:
+        extra["depth_filter"] = df_stats
     return {**extra, "verts": verts.cpu().numpy(), "faces": faces.cpu().numpy(),
             "normals": normals.cpu().numpy(),
             "rgb": None if rgb is None else rgb.cpu().numpy(), "labels": None,
@@ -218,7 +235,7 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
 def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_maps=None,
                       min_weight=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
                       refine_warmup=1, refine_kw=None, refine_min_matched=0.25,
-                      refine_max_step=None):
+                      refine_max_step=None, depth_filter=None, depth_filter_stats=None):
     """Frame-to-model tracking, the other half of KinectFusion: integrate the
     views into ``volume`` (in place) one per call, each with a pose refined
     against the volume as it then stands.  The first ``refine_warmup`` frames
@@ -235,8 +252,17 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
     poses used), ``refine`` (per frame None during the warm-up, else a dict
     ``matched`` -- the share --, ``rmse``, ``rank``, ``iterations``, ``step``
     (radians, units) from the given pose and ``fallback``), ``integrate_ms``,
-    ``refine_ms`` (device-synchronised host clock)."""
+    ``refine_ms`` (device-synchronised host clock).  With ``depth_filter`` (a
+    ``utils.depth_frontend.DepthFilter``) a frame is tracked with the points of
+    the pixels the front end keeps and integrated with its cleaned depth;
+    ``depth_filter_stats`` (``depth_frontend.new_stats()``) gains the counts of
+    the integrated frames."""
     from .registration import pose_step, refine_pose_tsdf
+    if depth_filter is not None:
+        from . import depth_frontend
+        kw_filter = {"depth_filter": depth_filter}
+    else:
+        kw_filter = {}
     dev = volume["tsdf"].device
     poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
     kw = dict(refine_kw or {})
@@ -258,7 +284,7 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             out = refine_pose_tsdf(z[0], given, intrinsics, volume, trunc, depth_min=depth_min,
-                                   depth_max=depth_max, device=dev, **kw)
+                                   depth_max=depth_max, device=dev, **kw_filter, **kw)
             t_r += time.perf_counter() - t0
             rot, trans = pose_step(out["pose"], given)
             share = out["matched"] / out["n_points"] if out["n_points"] else 0.0
@@ -271,6 +297,9 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
         used.append(pose)
         records.append(rec)
         P = torch.from_numpy(pose.astype(np.float32)[None]).to(dev)
+        if depth_filter is not None:
+            z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
+                                           stats=depth_filter_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ops.integrate_tsdf(volume, z, P, intrinsics, trunc, color=col, max_weight=max_weight,

@@ -34,7 +34,8 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
                         aabb=None, voxel=0.05, trunc=None, batch=16, num_classes=40,
                         min_votes=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
                         device="cuda", score_maps=None, min_margin=0, smooth=0,
-                        smooth_neighbourhood=26, min_component=0, component_connectivity=26):
+                        smooth_neighbourhood=26, min_component=0, component_connectivity=26,
+                        depth_filter=None):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps`` /
     ``label_maps`` / ``color_maps``: sequences or callables ``i -> [H,W]`` fp32
     z-depth in scene units (0 = none), ``[H,W]`` uint8 class ids (0 = no vote),
@@ -65,7 +66,16 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
     26), before the table is pooled and resolved and before any ray-cast: the
     floaters carry no label and no ray hits them; the dict then has their
     statistics as ``components``.  The table itself is not cleared: a removed
-    voxel's column is never read again."""
+    voxel's column is never read again.
+    ``depth_filter`` (a ``utils.depth_frontend.DepthFilter``) sends every frame
+    through the depth front end first: the volume is integrated and the votes
+    or the evidence are cast with the filtered frames without their rejected
+    pixels, and the dict gains ``depth_filter``, the rejection counts.  None
+    enters none of it."""
+    df_stats = None
+    if depth_filter is not None:
+        from . import depth_frontend
+        df_stats = depth_frontend.new_stats()
     smooth = int(smooth)
     if smooth < 0:
         raise ValueError("smooth must be >= 0")
@@ -108,6 +118,9 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
                 raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape[1:]}")
             col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))).to(dev)
         P = poses[a:b].to(dev)
+        if depth_filter is not None:
+            z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
+                                           stats=df_stats)
         ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
                            depth_min=depth_min, depth_max=depth_max)
         if soft:
@@ -116,7 +129,7 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
         else:
             ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
                                   depth_max=depth_max)
-    extra = {}
+    extra = {} if df_stats is None else {"depth_filter": df_stats}
     if int(min_component) > 0:
         extra["components"] = remove_small_components(vol, int(min_component),
                                                       component_connectivity)
