@@ -1456,6 +1456,41 @@ int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx,
                             uint32_t W, float trunc, float max_weight, float depth_min,
                             float depth_max, void* stream);
 
+/* ucsa_tsdf_integrate_weighted: the same integration with a weight per pixel,
+ * pixel_weight [B,H,W] fp32 on the device (ucsa_depth_confidence makes one from
+ * the depth front end's outputs; any map of finite positive numbers will do).
+ * The contract is ucsa_tsdf_integrate's, verbatim, with these lines changed:
+ *   z = depth[b][v][u]; skip unless measured (as above);
+ *   w = pixel_weight[b][v][u]; skip unless w > 0 and w is finite (NaN skips);
+ *   sdf = z - c_z; skip if sdf < -trunc; x = min(1, sdf / trunc);
+ *   w1 = weight + w; tsdf = (tsdf*weight + x*w) / w1;
+ *   rgb_c = (rgb_c*weight + (float)color[b][v][u][c]*w) / w1  for c = 0, 1, 2;
+ *   weight = min(w1, max_weight).
+ * tests/weighted_numpy.py restates it and the volumes match it bit for bit.
+ * Consequences: pixel_weight == 1.0f everywhere gives ucsa_tsdf_integrate's
+ * bytes (x*1.0f and c*1.0f are exact); a view whose weights are all 0 (or
+ * negative, NaN, inf) leaves the volume's bytes alone; the updated tsdf lies
+ * between the old value and x up to rounding; one call with B views, B calls
+ * with one view and every split in between give the same bytes, and so do two
+ * runs.  The accumulated weight is in units of pixel weight: a voxel seen once
+ * at w = 0.3 holds 0.3, so a consumer's min_weight threshold is in those units
+ * too.  One thread owns a voxel, no atomics, the state is read once and
+ * written once, a voxel no view touched is not written: the same kernel, the
+ * same view loop and the same brick cull, with the weight gathered at the
+ * depth's own index (b*H + v)*W + u next to the depth gather.
+ * Limits as for ucsa_tsdf_integrate; pixel_weight (argument 9) must not be
+ * NULL, and the arguments after it sit one index higher than there: color
+ * (10), poses (11), B (12), fx (13), fy (14), cx (15), cy (16), H (17), W (18),
+ * trunc (19), max_weight (20), depth_min (21), depth_max (22). */
+int32_t ucsa_tsdf_integrate_weighted(float* tsdf, float* weight, float* rgb, uint32_t nx,
+                                     uint32_t ny, uint32_t nz, const float* origin3,
+                                     const float* spacing3, const float* depth,
+                                     const float* pixel_weight, const uint8_t* color,
+                                     const float* poses, uint32_t B, float fx, float fy,
+                                     float cx, float cy, uint32_t H, uint32_t W, float trunc,
+                                     float max_weight, float depth_min, float depth_max,
+                                     void* stream);
+
 /* ---- occupancy prior: a TSDF volume carves the marcher's cascade grid (not in
  * the reference; its parent code base had mark_untrained_grid) ---------------
  * ucsa_tsdf_occupancy: the volume (tsdf, weight [nx,ny,nz] fp32, origin3 /
@@ -2520,7 +2555,8 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
  * (not in the reference) -----------------------------------------------------
  * What KinectFusion does to a depth frame before it integrates or tracks it
  * (utils/depth_frontend.py): everything above reads depth[v][u] as the sensor
- * gave it.  Three entry points over depth [B,H,W] fp32 z-depth on the device;
+ * gave it.  Three entry points over depth [B,H,W] fp32 z-depth on the device
+ * (and ucsa_depth_confidence, last in this section, over their outputs);
  * fx, fy, cx, cy, depth_min, depth_max and every threshold are HOST scalars.
  * All arithmetic is fp32, every operation as written, no contraction, division
  * and sqrt correctly rounded; tests/depth_numpy.py restates the three contracts
@@ -2590,7 +2626,27 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
  * sigma_depth (7), sigma_z2 (8), fx (9), fy (10), cx (11), cy (12), max_jump
  * (13), max_jump_z2 (14), min_cos (15), reject (16), depth_min (17), depth_max
  * (18), filtered (19), clean (20), points (21), normals (22), mask (23).
- * An argument error returns UCSA_ERR_ARG - index before any launch. */
+ * An argument error returns UCSA_ERR_ARG - index before any launch.
+ *
+ * ucsa_depth_confidence: the weight of a pixel's measurement for
+ * ucsa_tsdf_integrate_weighted, from the outputs of ucsa_depth_normals /
+ * ucsa_depth_frontend: points [B,H,W,3], normals [B,H,W,3], mask [B,H,W] ->
+ * weight [B,H,W] fp32.  A plain kernel, one thread per pixel, no LDS.  Per
+ * pixel, with p the point, n the normal, m the mask:
+ *   if !(m & MEASURED) or m & reject: w = 0 (reject a set of EDGE | GRAZING);
+ *   z = p2; sigma = sigma_depth + sigma_z2 * (z*z); s = sigma_depth / sigma;
+ *   wz = s*s  (the inverse variance of the filter's own noise model, relative
+ *   to z = 0; exactly 1 with sigma_z2 = 0);
+ *   if m & NORMAL: dot = (n0*p0 + n1*p1) + n2*p2;
+ *     cosv = (-dot) / sqrtf((p0*p0 + p1*p1) + p2*p2)  (ucsa_depth_normals' own
+ *     expression on the same operands: the same bits);
+ *     wa = fminf(fmaxf(cosv, cos_floor), 1.0f); a NaN cosv gives cos_floor;
+ *   without a normal: wa = cos_floor;
+ *   w = wz * wa, in (0, 1] unless wz underflows.
+ * Arguments: points (0), normals (1), mask (2), B >= 1 (3), 1 <= H <= 16384
+ * (4), 1 <= W <= 16384 (5), sigma_depth > 0 finite (6), sigma_z2 >= 0 finite
+ * (7), 0 < cos_floor <= 1 (8), reject within EDGE | GRAZING (9), weight
+ * [B,H,W], sharing no byte with an input (10). */
 #define UCSA_DEPTH_RANGE_BINS 256u
 #define UCSA_DEPTH_MEASURED 1u
 #define UCSA_DEPTH_NORMAL 2u
@@ -2611,6 +2667,10 @@ int32_t ucsa_depth_frontend(const float* depth, uint32_t B, uint32_t H, uint32_t
                             uint32_t reject, float depth_min, float depth_max, float* filtered,
                             float* clean, float* points, float* normals, uint8_t* mask,
                             void* stream);
+int32_t ucsa_depth_confidence(const float* points, const float* normals, const uint8_t* mask,
+                              uint32_t B, uint32_t H, uint32_t W, float sigma_depth,
+                              float sigma_z2, float cos_floor, uint32_t reject, float* weight,
+                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ first stage of the mapping-based pseudo-label baseline.
         [--min_weight K] [--no_color] [--pose_frame] \\
         [--min_component N] [--component_connectivity {6,26}] [--simplify CELL] \\
         [--refine_poses [--refine_warmup K] [--refine_iters N] [--refine_stride S] \\
-         [--refine_min_matched SHARE] [--poses_out FILE.npy]] [--depth_filter SPEC]
+         [--refine_min_matched SHARE] [--poses_out FILE.npy]] [--depth_filter SPEC] \\
+        [--view_weights SPEC]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
 ``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement; scene units as
@@ -45,7 +46,19 @@ tracked; SPEC is ``default`` or a comma-separated list of ``DepthFilter``'s
 fields, lengths in metres (``radius=3,sigma_space=1.5,sigma_depth=0.01,
 sigma_z2=0.002,max_jump=0.05,min_cos=0.1,reject_grazing=0``).  It prints one
 ``depth_filter:`` line with the share of pixels rejected per bit; without the
-flag nothing changes.  Prints one JSON line last."""
+flag nothing changes.  ``--view_weights SPEC`` (needs ``--depth_filter``) weights
+every pixel's measurement by its range and viewing angle
+(``utils.depth_frontend.ViewWeights``, ``ops.depth.integrate_tsdf_weighted``):
+w = (sigma_depth / (sigma_depth + sigma_z2 z^2))^2 times the cosine between
+normal and view ray, the cosine floored at ``cos_floor``; SPEC is ``default`` or
+``cos_floor=0.2,sigma_depth=0.01,sigma_z2=0.002`` (metres; an absent sigma is
+the filter's).  It prints one ``view_weights:`` line with the mean weight of the
+kept pixels.  A voxel's weight is then the sum of its pixels' weights -- seen once
+at w = 0.3 it holds 0.3 -- and ``--min_weight`` is in those units and may be a
+fraction: ``cos_floor`` times the range factor at the farthest depth (0.1 with
+the default filter, whose sigma_z2 is 0) keeps every voxel seen once, as 1 does
+without weights; k times the printed mean asks for about k average views.  The
+default stays 1.  Without the flag nothing changes.  Prints one JSON line last."""
 import argparse
 import json
 import os
@@ -71,8 +84,10 @@ def parse_args(argv=None):
     p.add_argument("--aabb", type=float, nargs=6, default=None,
                    help="x0 y0 z0 x1 y1 z1, NGP frame, scene units")
     p.add_argument("--every", type=int, default=1, help="use every N-th frame")
-    p.add_argument("--min_weight", type=int, default=1,
-                   help="a voxel counts as observed from this many views on")
+    p.add_argument("--min_weight", type=float, default=1,
+                   help="a voxel counts as observed from this many views on; with "
+                        "--view_weights from this accumulated pixel weight on (a fraction "
+                        "such as 0.1 then means: seen at least once)")
     p.add_argument("--no_color", action="store_true")
     p.add_argument("--pose_frame", action="store_true",
                    help="write the mesh in the JSON pose frame, in metres")
@@ -95,14 +110,24 @@ def parse_args(argv=None):
     p.add_argument("--depth_filter", default=None, metavar="SPEC",
                    help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
                         "lengths in metres (default: off)")
+    p.add_argument("--view_weights", default=None, metavar="SPEC",
+                   help="'default' or field=value,... of utils.depth_frontend.ViewWeights "
+                        "(cos_floor, sigma_depth, sigma_z2; needs --depth_filter): weight "
+                        "every pixel by range and viewing angle (default: off)")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     from PIL import Image
     a = parse_args(argv)
-    if a.every < 1 or a.min_weight < 1 or a.batch < 1:
-        raise SystemExit("--every, --min_weight and --batch must be >= 1")
+    if a.view_weights is not None and a.depth_filter is None:
+        raise SystemExit("--view_weights needs --depth_filter")
+    if a.view_weights is None and a.min_weight == int(a.min_weight):
+        a.min_weight = int(a.min_weight)
+    if a.every < 1 or a.batch < 1 or not (a.min_weight >= 1 or
+                                          (a.view_weights is not None and a.min_weight > 0)):
+        raise SystemExit("--every, --min_weight and --batch must be >= 1 (--min_weight > 0 "
+                         "with --view_weights)")
     if a.min_component < 0:
         raise SystemExit("--min_component must be >= 0")
     if a.simplify is not None and not a.simplify > 0:
@@ -136,6 +161,10 @@ def main(argv=None):
     if a.depth_filter is not None:
         from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
         refine["depth_filter"] = DepthFilter.from_string(a.depth_filter).scaled(uom)
+    if a.view_weights is not None:
+        from ucsa_neural_rendering_amd.utils.depth_frontend import (ViewWeights,
+                                                                    weight_stats_line)
+        refine["view_weights"] = ViewWeights.from_string(a.view_weights).scaled(uom)
     mesh = fuse_depth_views(poses, fr["intrinsics"], H, W, depth,
                             color_maps=None if a.no_color else color, aabb=a.aabb,
                             voxel=voxel, trunc=None if a.trunc is None else a.trunc * uom,
@@ -144,6 +173,8 @@ def main(argv=None):
                             component_connectivity=a.component_connectivity, **refine)
     if a.depth_filter is not None:
         print(stats_line(mesh["depth_filter"]))
+    if a.view_weights is not None:
+        print(weight_stats_line(mesh["view_weights"]))
     tracked = None
     if a.refine_poses:
         recs = [r for r in mesh["refine"] if r is not None]

@@ -4,7 +4,8 @@ fusion on the GPU, then ``ops.tsdf_occupancy`` (``utils/occupancy_prior.py``).
 
     python scripts/occupancy_prior.py --scene_root <root>/<scene> --out prior.npz \\
         [--bound 4] [--voxel METRES] [--trunc METRES] [--dilate METRES] \\
-        [--unknown {keep,empty}] [--every N] [--depth_filter SPEC]
+        [--unknown {keep,empty}] [--every N] [--depth_filter SPEC] \\
+        [--view_weights SPEC] [--min_weight W]
 
 Reads the frames of transforms_train.json (every ``--every``-th) as
 ``scripts/fuse_tsdf_mesh.py`` does: the poses in the field's (NGP) frame and
@@ -20,6 +21,14 @@ sends every frame through the depth front end (``utils.depth_frontend``) before
 it is integrated; SPEC as for ``scripts/fuse_tsdf_mesh.py`` (``default`` or
 ``field=value,...``, lengths in metres).  It prints one ``depth_filter:`` line
 with the share of pixels rejected per bit; without the flag nothing changes.
+``--view_weights SPEC`` (needs ``--depth_filter``; ``default`` or
+``field=value,...`` of ``utils.depth_frontend.ViewWeights``, as for
+``scripts/fuse_tsdf_mesh.py``) integrates with a weight per pixel from its range
+and viewing angle and prints one ``view_weights:`` line with the mean weight of
+the kept pixels.  A voxel's weight is then in units of pixel weight (seen once at
+w = 0.3 it holds 0.3) and ``--min_weight`` (default 1, as before: the weight from
+which a voxel counts as observed) is in those units: 0.1 -- ``cos_floor`` with
+the default filter -- carves what 1 carves without weights.
 
     python scripts/occupancy_prior.py --mesh M.ply [--mesh_pose_frame] --out prior.npz \\
         [--bound 4] [--dilate UNITS] [--H 128]
@@ -65,6 +74,13 @@ def parse_args(argv=None):
     p.add_argument("--depth_filter", default=None, metavar="SPEC",
                    help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
                         "lengths in metres (default: off)")
+    p.add_argument("--view_weights", default=None, metavar="SPEC",
+                   help="'default' or field=value,... of utils.depth_frontend.ViewWeights "
+                        "(cos_floor, sigma_depth, sigma_z2; needs --depth_filter): weight "
+                        "every pixel by range and viewing angle (default: off)")
+    p.add_argument("--min_weight", type=float, default=None,
+                   help="a voxel counts as observed from this weight on (default 1); with "
+                        "--view_weights in units of accumulated pixel weight, 0.1 = seen once")
     a = p.parse_args(argv)
     if (a.scene_root is None) == (a.mesh is None):
         p.error("one of --scene_root (the depth route) and --mesh (the mesh route) is required")
@@ -108,12 +124,22 @@ def main(argv=None):
     if a.depth_filter is not None:
         from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
         extra["depth_filter"] = DepthFilter.from_string(a.depth_filter).scaled(uom)
+    if a.view_weights is not None:
+        if a.depth_filter is None:
+            raise SystemExit("--view_weights needs --depth_filter")
+        from ucsa_neural_rendering_amd.utils.depth_frontend import (ViewWeights,
+                                                                    weight_stats_line)
+        extra["view_weights"] = ViewWeights.from_string(a.view_weights).scaled(uom)
+    if a.min_weight is not None:
+        extra["min_weight"] = a.min_weight
     mask, st = prior_from_depth_views(poses, fr["intrinsics"], fr["H"], fr["W"], depth, a.bound,
                                       voxel=voxel,
                                       trunc=None if a.trunc is None else a.trunc * uom,
                                       dilate=dilate, unknown=a.unknown, **extra)
     if a.depth_filter is not None:
         print(stats_line(st["depth_filter"]))
+    if a.view_weights is not None:
+        print(weight_stats_line(st["view_weights"]))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     save_prior(a.out, mask, a.bound, voxel=np.float32(voxel), trunc=np.float32(st["trunc"]),
                dilate=np.float32(voxel if dilate is None else dilate), unknown=a.unknown,

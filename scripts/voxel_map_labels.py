@@ -51,7 +51,16 @@ the output is unchanged.
 (``utils.depth_frontend``) before it is integrated and voted with; SPEC as for
 ``scripts/fuse_tsdf_mesh.py`` (``default`` or ``field=value,...``, lengths in
 metres).  It prints one ``depth_filter:`` line with the share of pixels rejected
-per bit; without the flag nothing changes."""
+per bit; without the flag nothing changes.
+``--view_weights SPEC`` (needs ``--depth_filter``; ``default`` or
+``field=value,...`` of ``utils.depth_frontend.ViewWeights``, as for
+``scripts/fuse_tsdf_mesh.py``) integrates the TSDF half with a weight per pixel
+from its range and viewing angle; the votes and the evidence are not weighted.
+It prints one ``view_weights:`` line with the mean weight of the kept pixels.
+The volume's weight is then in units of pixel weight (a voxel seen once at
+w = 0.3 holds 0.3): ``--min_weight`` (default 1, as before) is what the
+ray-caster asks of a voxel, and with weights on 0.1 -- ``cos_floor`` with the
+default filter -- means "seen at least once".  Without the flag nothing changes."""
 import argparse
 import json
 import os
@@ -91,6 +100,13 @@ def parse_args(argv=None):
     p.add_argument("--depth_filter", default=None, metavar="SPEC",
                    help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
                         "lengths in metres (default: off)")
+    p.add_argument("--view_weights", default=None, metavar="SPEC",
+                   help="'default' or field=value,... of utils.depth_frontend.ViewWeights "
+                        "(cos_floor, sigma_depth, sigma_z2; needs --depth_filter): weight "
+                        "every pixel by range and viewing angle (default: off)")
+    p.add_argument("--min_weight", type=float, default=None,
+                   help="the ray-caster's least voxel weight (default: its own, 1); with "
+                        "--view_weights in units of accumulated pixel weight, 0.1 = seen once")
     p.add_argument("--gt_mesh", default=None,
                    help="score the voxel map in 3D at this labelled mesh's vertices (.ply)")
     p.add_argument("--gt_pose_frame", action="store_true",
@@ -187,6 +203,12 @@ def main(argv=None):
     if a.depth_filter is not None:
         from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
         front = {"depth_filter": DepthFilter.from_string(a.depth_filter).scaled(uom)}
+    if a.view_weights is not None:
+        if a.depth_filter is None:
+            raise SystemExit("--view_weights needs --depth_filter")
+        from ucsa_neural_rendering_amd.utils.depth_frontend import (ViewWeights,
+                                                                    weight_stats_line)
+        front["view_weights"] = ViewWeights.from_string(a.view_weights).scaled(uom)
     fused = fuse_semantic_views(poses, fr["intrinsics"], H, W, depth,
                                 None if soft else (lambda i: png(src, i)),
                                 aabb=a.aabb, voxel=a.voxel * uom,
@@ -201,6 +223,8 @@ def main(argv=None):
     t_fuse = time.perf_counter() - t0
     if a.depth_filter is not None:
         print(stats_line(fused["depth_filter"]))
+    if a.view_weights is not None:
+        print(weight_stats_line(fused["view_weights"]))
     vol = fused["volume"]
     far = a.far
     if far is None:
@@ -210,7 +234,8 @@ def main(argv=None):
         os.makedirs(os.path.join(a.out_dir, k), exist_ok=True)
     maps, t_cast = [], 0.0
     it = render_voxel_map(vol, fused["labels"], poses, fr["intrinsics"], H, W, a.near, far,
-                          step=None if a.step is None else a.step * uom, batch=a.batch)
+                          step=None if a.step is None else a.step * uom, batch=a.batch,
+                          **({} if a.min_weight is None else {"min_weight": a.min_weight}))
     while True:
         torch.cuda.synchronize()
         t0 = time.perf_counter()

@@ -320,6 +320,9 @@ SIGNATURES = {
     "ucsa_tsdf_integrate": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, C.POINTER(_f),
                                         C.POINTER(_f), _p, _p, _p, _u32, _f, _f, _f, _f,
                                         _u32, _u32, _f, _f, _f, _f, _p]),
+    "ucsa_tsdf_integrate_weighted": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                                 C.POINTER(_f), _p, _p, _p, _p, _u32, _f, _f, _f,
+                                                 _f, _u32, _u32, _f, _f, _f, _f, _p]),
     # ---- occupancy prior (a TSDF volume carves the marcher's cascade grid) ----
     "ucsa_tsdf_occupancy_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32]),
     "ucsa_tsdf_occupancy": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
@@ -408,6 +411,7 @@ SIGNATURES = {
                                        _p, _p, _p, _p]),
     "ucsa_depth_frontend": (C.c_int32, [_p, _u32, _u32, _u32, _p, _u32, _p, _f, _f, _f, _f, _f,
                                         _f, _f, _f, _f, _u32, _f, _f, _p, _p, _p, _p, _p, _p]),
+    "ucsa_depth_confidence": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, _f, _f, _f, _u32, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

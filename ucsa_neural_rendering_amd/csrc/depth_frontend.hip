@@ -25,6 +25,11 @@
 // lanes and 48 = 16 mod 32 puts the two rows of a 32-lane group on disjoint
 // banks for every tap.  No atomics, no scratch; R is a template argument so
 // that the window loops unroll.
+//
+// k_depth_confidence  (ucsa_depth_confidence) one thread per pixel, no LDS: the
+//                     weight of a pixel's measurement for
+//                     ucsa_tsdf_integrate_weighted from the points, normals and
+//                     mask above; tests/weighted_numpy.py restates it.
 #include <cmath>
 
 #include "ucsa_common.h"
@@ -261,6 +266,44 @@ int32_t df_run(DfArgs a, uint32_t B, int r, void* stream) {
   return ucsa_launch_status();
 }
 
+// ucsa_depth_confidence: the weight a pixel's measurement gets in
+// ucsa_tsdf_integrate_weighted.  One thread per pixel, 28 bytes in and 4 out,
+// no LDS, no atomics: the kernel is its loads.
+constexpr int DC_BLOCK = 256;
+
+struct DcArgs {
+  const float* points;
+  const float* normals;
+  const uint8_t* mask;
+  float* weight;
+  uint32_t hw;
+  float sigma_depth, sigma_z2, cos_floor;
+  uint32_t reject;
+};
+
+__global__ void __launch_bounds__(DC_BLOCK) k_depth_confidence(DcArgs a) {
+  const uint32_t e = blockIdx.x * DC_BLOCK + threadIdx.x;
+  if (e >= a.hw) return;
+  const size_t pix = (size_t)blockIdx.y * a.hw + e;
+  const uint32_t m = a.mask[pix];
+  float w = 0.0f;
+  if ((m & 1u) && !(m & a.reject)) {
+    const float p0 = a.points[3 * pix], p1 = a.points[3 * pix + 1], p2 = a.points[3 * pix + 2];
+    const float sigma = a.sigma_depth + a.sigma_z2 * (p2 * p2);
+    const float s = a.sigma_depth / sigma;
+    const float wz = s * s;
+    float wa = a.cos_floor;
+    if (m & 2u) {
+      const float n0 = a.normals[3 * pix], n1 = a.normals[3 * pix + 1], n2 = a.normals[3 * pix + 2];
+      const float dot = (n0 * p0 + n1 * p1) + n2 * p2;
+      const float cosv = (-dot) / sqrtf((p0 * p0 + p1 * p1) + p2 * p2);
+      wa = fminf(fmaxf(cosv, a.cos_floor), 1.0f);  // a NaN cosv gives cos_floor
+    }
+    w = wz * wa;
+  }
+  a.weight[pix] = w;
+}
+
 }  // namespace
 
 // the frames: arguments k0 .. k0 + 3 of every entry point
@@ -387,4 +430,44 @@ extern "C" int32_t ucsa_depth_frontend(const float* depth, uint32_t B, uint32_t 
   a.min_cos = min_cos;
   a.reject = reject;
   return df_run<2>(a, B, (int)radius, stream);
+}
+
+extern "C" int32_t ucsa_depth_confidence(const float* points, const float* normals,
+                                         const uint8_t* mask, uint32_t B, uint32_t H, uint32_t W,
+                                         float sigma_depth, float sigma_z2, float cos_floor,
+                                         uint32_t reject, float* weight, void* stream) {
+  UCSA_CHECK_ARG(points, 0);
+  UCSA_CHECK_ARG(normals, 1);
+  UCSA_CHECK_ARG(mask, 2);
+  UCSA_CHECK_ARG(B >= 1, 3);
+  UCSA_CHECK_ARG(H >= 1 && H <= 16384, 4);
+  UCSA_CHECK_ARG(W >= 1 && W <= 16384, 5);
+  UCSA_CHECK_ARG(sigma_depth > 0.0f && std::isfinite(sigma_depth), 6);
+  UCSA_CHECK_ARG(sigma_z2 >= 0.0f && std::isfinite(sigma_z2), 7);
+  UCSA_CHECK_ARG(cos_floor > 0.0f && cos_floor <= 1.0f, 8);
+  UCSA_CHECK_ARG((reject & ~(UCSA_DEPTH_EDGE | UCSA_DEPTH_GRAZING)) == 0u, 9);
+  const size_t n = (size_t)B * H * W;
+  // weight [n] floats shares no byte with an input
+  const auto apart = [&](const void* p, size_t bytes) {
+    const char *w0 = (const char*)weight, *q0 = (const char*)p;
+    return w0 + 4 * n <= q0 || q0 + bytes <= w0;
+  };
+  UCSA_CHECK_ARG(weight && apart(points, 12 * n) && apart(normals, 12 * n) && apart(mask, n), 10);
+  DcArgs a;
+  a.hw = H * W;
+  a.sigma_depth = sigma_depth;
+  a.sigma_z2 = sigma_z2;
+  a.cos_floor = cos_floor;
+  a.reject = reject;
+  UCSA_CLEAR_ERR();
+  for (uint32_t b0 = 0; b0 < B; b0 += DF_MAXB) {
+    const size_t off = (size_t)b0 * a.hw;
+    a.points = points + 3 * off;
+    a.normals = normals + 3 * off;
+    a.mask = mask + off;
+    a.weight = weight + off;
+    const dim3 grid(ucsa_div_up(a.hw, DC_BLOCK), B - b0 < DF_MAXB ? B - b0 : DF_MAXB);
+    hipLaunchKernelGGL(k_depth_confidence, grid, dim3(DC_BLOCK), 0, (hipStream_t)stream, a);
+  }
+  return ucsa_launch_status();
 }

@@ -24,6 +24,12 @@
 //                   voxel of the brick would have skipped: no bit changes.
 // No atomics, no LDS beyond the cull's 32 x 8 points.  A call with more than
 // TS_MAXB views is a sequence of launches on the stream, in view order.
+//
+// ucsa_tsdf_integrate_weighted is the same kernel with WEIGHTED set: a view's
+// measurement counts with pixel_weight[b][v][u] instead of 1.  The weight is
+// gathered with the depth's own index, next to the depth gather; the view loop,
+// the cull and the state traffic are shared, and the unweighted instantiation
+// compiles to the code it was.
 #include <cmath>
 
 #include "tsdf_project.h"
@@ -45,9 +51,10 @@ struct TsArgs {
   uint32_t nx, ny, nz, B, H, W;
   float o[3], h[3];
   float fx, fy, cx, cy, trunc, max_weight, dmin, dmax;
+  const float* pixel_weight;  // [B,H,W], WEIGHTED only (last: the other offsets stay)
 };
 
-template <bool COLOR>
+template <bool COLOR, bool WEIGHTED>
 __global__ void __launch_bounds__(TS_BK* TS_BJ) k_tsdf_integrate(TsArgs a) {
   __shared__ float s_c[TS_MAXB][8][3];
   __shared__ uint32_t s_cull;
@@ -105,15 +112,30 @@ __global__ void __launch_bounds__(TS_BK* TS_BJ) k_tsdf_integrate(TsArgs a) {
     if (!(u >= 0.0f && u < fW && v >= 0.0f && v < fH)) continue;
     const size_t pix = ((size_t)b * a.H + (uint32_t)v) * a.W + (uint32_t)u;
     const float d = a.depth[pix];
+    float pw = 1.0f;
+    if constexpr (WEIGHTED) pw = a.pixel_weight[pix];  // pix is in range: the depth's index
     if (!(isfinite(d) && d >= a.dmin && d <= a.dmax)) continue;
+    if constexpr (WEIGHTED) {
+      if (!(pw > 0.0f && isfinite(pw))) continue;
+    }
     const float sdf = d - c[2];
     if (sdf < -a.trunc) continue;
     const float val = fminf(1.0f, sdf / a.trunc);
-    const float w1 = w + 1.0f;
-    tsdf = (tsdf * w + val) / w1;
-    if (COLOR) {
+    float w1;
+    if constexpr (WEIGHTED) {
+      w1 = w + pw;
+      tsdf = (tsdf * w + val * pw) / w1;
+      if (COLOR) {
 #pragma unroll
-      for (int r = 0; r < 3; ++r) rgb[r] = (rgb[r] * w + (float)a.color[3 * pix + r]) / w1;
+        for (int r = 0; r < 3; ++r) rgb[r] = (rgb[r] * w + (float)a.color[3 * pix + r] * pw) / w1;
+      }
+    } else {
+      w1 = w + 1.0f;
+      tsdf = (tsdf * w + val) / w1;
+      if (COLOR) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) rgb[r] = (rgb[r] * w + (float)a.color[3 * pix + r]) / w1;
+      }
     }
     w = fminf(w1, a.max_weight);
     dirty = true;
@@ -127,36 +149,37 @@ __global__ void __launch_bounds__(TS_BK* TS_BJ) k_tsdf_integrate(TsArgs a) {
   }
 }
 
-}  // namespace
-
-extern "C" int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx,
-                                       uint32_t ny, uint32_t nz, const float* origin3,
-                                       const float* spacing3, const float* depth,
-                                       const uint8_t* color, const float* poses, uint32_t B,
-                                       float fx, float fy, float cx, float cy, uint32_t H,
-                                       uint32_t W, float trunc, float max_weight,
-                                       float depth_min, float depth_max, void* stream) {
+// both entry points; weighted: ucsa_tsdf_integrate_weighted, whose arguments
+// after depth sit one index higher
+int32_t ts_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx, uint32_t ny,
+                     uint32_t nz, const float* origin3, const float* spacing3,
+                     const float* depth, const float* pixel_weight, const uint8_t* color,
+                     const float* poses, uint32_t B, float fx, float fy, float cx, float cy,
+                     uint32_t H, uint32_t W, float trunc, float max_weight, float depth_min,
+                     float depth_max, void* stream, bool weighted) {
+  const int s = weighted ? 1 : 0;
   UCSA_CHECK_ARG(tsdf, 0);
   UCSA_CHECK_ARG(weight, 1);
-  UCSA_CHECK_ARG((rgb == nullptr) == (color == nullptr), rgb ? 9 : 2);
+  UCSA_CHECK_ARG((rgb == nullptr) == (color == nullptr), rgb ? 9 + s : 2);
   UCSA_CHECK_ARG(nx >= 2 && (uint64_t)nx * ny * nz <= 0x7FFFFFFFull, 3);
   UCSA_CHECK_ARG(ny >= 2, 4);
   UCSA_CHECK_ARG(nz >= 2, 5);
   UCSA_CHECK_ARG(origin3, 6);
   UCSA_CHECK_ARG(spacing3, 7);
   UCSA_CHECK_ARG(depth, 8);
-  UCSA_CHECK_ARG(poses, 10);
-  UCSA_CHECK_ARG(B >= 1, 11);
-  UCSA_CHECK_ARG(fx > 0.0f && std::isfinite(fx), 12);
-  UCSA_CHECK_ARG(fy > 0.0f && std::isfinite(fy), 13);
-  UCSA_CHECK_ARG(std::isfinite(cx), 14);
-  UCSA_CHECK_ARG(std::isfinite(cy), 15);
-  UCSA_CHECK_ARG(H >= 1 && H <= 16384, 16);
-  UCSA_CHECK_ARG(W >= 1 && W <= 16384, 17);
-  UCSA_CHECK_ARG(trunc > 0.0f && std::isfinite(trunc), 18);
-  UCSA_CHECK_ARG(max_weight >= 1.0f, 19);
-  UCSA_CHECK_ARG(!std::isnan(depth_min), 20);
-  UCSA_CHECK_ARG(depth_max >= depth_min, 21);
+  UCSA_CHECK_ARG(!weighted || pixel_weight, 9);
+  UCSA_CHECK_ARG(poses, 10 + s);
+  UCSA_CHECK_ARG(B >= 1, 11 + s);
+  UCSA_CHECK_ARG(fx > 0.0f && std::isfinite(fx), 12 + s);
+  UCSA_CHECK_ARG(fy > 0.0f && std::isfinite(fy), 13 + s);
+  UCSA_CHECK_ARG(std::isfinite(cx), 14 + s);
+  UCSA_CHECK_ARG(std::isfinite(cy), 15 + s);
+  UCSA_CHECK_ARG(H >= 1 && H <= 16384, 16 + s);
+  UCSA_CHECK_ARG(W >= 1 && W <= 16384, 17 + s);
+  UCSA_CHECK_ARG(trunc > 0.0f && std::isfinite(trunc), 18 + s);
+  UCSA_CHECK_ARG(max_weight >= 1.0f, 19 + s);
+  UCSA_CHECK_ARG(!std::isnan(depth_min), 20 + s);
+  UCSA_CHECK_ARG(depth_max >= depth_min, 21 + s);
   TsArgs a;
   a.tsdf = tsdf;
   a.weight = weight;
@@ -184,17 +207,50 @@ extern "C" int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, u
   UCSA_CHECK_ARG(gy <= 65535u, 4);
   UCSA_CHECK_ARG(nx <= 65535u, 3);
   const dim3 grid(ucsa_div_up(nz, TS_BK), gy, nx), block(TS_BK, TS_BJ);
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)stream;
   UCSA_CLEAR_ERR();
   for (uint32_t b0 = 0; b0 < B; b0 += TS_MAXB) {
     a.B = B - b0 < TS_MAXB ? B - b0 : TS_MAXB;
     a.depth = depth + (size_t)b0 * H * W;
+    a.pixel_weight = weighted ? pixel_weight + (size_t)b0 * H * W : nullptr;
     a.color = color ? color + (size_t)b0 * H * W * 3 : nullptr;
     a.poses = poses + 16 * (size_t)b0;
-    if (color)
-      hipLaunchKernelGGL(k_tsdf_integrate<true>, grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL(k_tsdf_integrate<false>, grid, block, 0, s, a);
+    if (weighted) {
+      if (color)
+        hipLaunchKernelGGL((k_tsdf_integrate<true, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((k_tsdf_integrate<false, true>), grid, block, 0, st, a);
+    } else {
+      if (color)
+        hipLaunchKernelGGL((k_tsdf_integrate<true, false>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((k_tsdf_integrate<false, false>), grid, block, 0, st, a);
+    }
   }
   return ucsa_launch_status();
+}
+
+}  // namespace
+
+extern "C" int32_t ucsa_tsdf_integrate(float* tsdf, float* weight, float* rgb, uint32_t nx,
+                                       uint32_t ny, uint32_t nz, const float* origin3,
+                                       const float* spacing3, const float* depth,
+                                       const uint8_t* color, const float* poses, uint32_t B,
+                                       float fx, float fy, float cx, float cy, uint32_t H,
+                                       uint32_t W, float trunc, float max_weight,
+                                       float depth_min, float depth_max, void* stream) {
+  return ts_integrate(tsdf, weight, rgb, nx, ny, nz, origin3, spacing3, depth, nullptr, color,
+                      poses, B, fx, fy, cx, cy, H, W, trunc, max_weight, depth_min, depth_max,
+                      stream, false);
+}
+
+extern "C" int32_t ucsa_tsdf_integrate_weighted(
+    float* tsdf, float* weight, float* rgb, uint32_t nx, uint32_t ny, uint32_t nz,
+    const float* origin3, const float* spacing3, const float* depth, const float* pixel_weight,
+    const uint8_t* color, const float* poses, uint32_t B, float fx, float fy, float cx, float cy,
+    uint32_t H, uint32_t W, float trunc, float max_weight, float depth_min, float depth_max,
+    void* stream) {
+  return ts_integrate(tsdf, weight, rgb, nx, ny, nz, origin3, spacing3, depth, pixel_weight,
+                      color, poses, B, fx, fy, cx, cy, H, W, trunc, max_weight, depth_min,
+                      depth_max, stream, true);
 }

@@ -2,7 +2,8 @@
 point and a normal per pixel, and the mask that rejects depth edges and grazing
 views.  Reached as ``ops.depth.filter_depth``, ``ops.depth.depth_normals`` and
 ``ops.depth.depth_frontend`` (both in one launch).  ``utils.depth_frontend``
-sits on it."""
+sits on it.  ``ops.depth.depth_confidence`` turns those outputs into a weight
+per pixel and ``ops.depth.integrate_tsdf_weighted`` integrates with it."""
 from __future__ import annotations
 
 import math
@@ -11,8 +12,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._lib import check, lib
-from ._args import _f32, _gpu, _non_negative, _positive, _ptr, _stream
+from .._lib import check, fvec, lib
+from ._args import (_f32, _gpu, _non_negative, _positive, _ptr, _stream, _views,
+                    volume_lattice)
 
 RANGE_BINS = 256
 MAX_RADIUS = 4
@@ -183,3 +185,68 @@ def depth_frontend(depth, tables, intrinsics, sigma_depth: float, max_jump: floa
           "ucsa_depth_frontend")
     return {"depth": filtered, "clean": clean, "points": points, "normals": normals,
             "mask": mask}
+
+
+def depth_confidence(points, normals, mask, sigma_depth: float, sigma_z2: float = 0.0,
+                     cos_floor: float = 0.1, reject: int = EDGE | GRAZING):
+    """The weight of every pixel's measurement for ``integrate_tsdf_weighted``,
+    from ``depth_normals`` / ``depth_frontend``'s ``points`` [B,H,W,3],
+    ``normals`` [B,H,W,3] and ``mask`` [B,H,W] uint8 -> float32 [B,H,W]: 0 where
+    the pixel is not measured or carries a bit of ``reject``; elsewhere
+    (``sigma_depth`` / (``sigma_depth`` + ``sigma_z2`` z^2))^2 -- the inverse
+    variance of the front end's noise model relative to z = 0 -- times the
+    cosine between normal and view ray, clamped to [``cos_floor``, 1]
+    (``cos_floor`` where the pixel has no normal), so that no measured pixel is
+    silenced.  Contract of ucsa_depth_confidence (include/ucsa_hip.h)."""
+    if not (torch.is_tensor(points) and torch.is_tensor(normals) and torch.is_tensor(mask)):
+        raise _lib.UcsaError("points, normals and mask must be tensors on the GPU: the HIP path "
+                             "has no CPU fallback")
+    points = _gpu(points, "points", torch.float32, (None, None, None, 3))
+    B, H, W = (int(s) for s in points.shape[:3])
+    if min(B, H, W) < 1 or max(H, W) > 16384:
+        raise _lib.UcsaError(f"points must be [B,H,W,3] with B >= 1 and 1 <= H, W <= 16384, got "
+                             f"{tuple(points.shape)}")
+    dev = points.device
+    normals = _gpu(normals, "normals", torch.float32, (B, H, W, 3), device=dev)
+    mask = _gpu(mask, "mask", torch.uint8, (B, H, W), device=dev)
+    sigma_depth = _positive(sigma_depth, "sigma_depth")
+    sigma_z2 = _non_negative(sigma_z2, "sigma_z2")
+    cos_floor = float(cos_floor)
+    if not 0.0 < cos_floor <= 1.0:
+        raise _lib.UcsaError(f"cos_floor must be in (0, 1], got {cos_floor!r}")
+    if isinstance(reject, bool) or not isinstance(reject, int) or reject & ~(EDGE | GRAZING):
+        raise _lib.UcsaError(f"reject must be a set of EDGE (4) | GRAZING (8), got {reject!r}")
+    weight = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    check(lib().ucsa_depth_confidence(_ptr(points), _ptr(normals), _ptr(mask), B, H, W,
+                                      sigma_depth, sigma_z2, cos_floor, reject, _ptr(weight),
+                                      _stream()), "ucsa_depth_confidence")
+    return weight
+
+
+def integrate_tsdf_weighted(volume, depth, pixel_weight, poses, intrinsics, trunc: float,
+                            color=None, max_weight: float = 65504.0, depth_min: float = 1e-6,
+                            depth_max: float = 3.0e38):
+    """``ops.integrate_tsdf`` with a weight per pixel: ``pixel_weight`` [B,H,W]
+    float32 on the GPU (``depth_confidence``'s map, or any other); every other
+    argument as there.  A pixel whose weight is not finite and > 0 takes no
+    part; a measurement x enters as tsdf = (tsdf W + x w) / (W + w), W = min(W +
+    w, ``max_weight``).  In place; returns ``volume``.  Weights of 1.0 give
+    ``integrate_tsdf``'s bytes, and any split of the views over calls gives the
+    same bytes.  The volume's ``weight`` is then in units of pixel weight -- a
+    voxel seen once at w = 0.3 holds 0.3 -- and so is every ``min_weight`` that
+    is compared with it.  Contract of ucsa_tsdf_integrate_weighted
+    (include/ucsa_hip.h)."""
+    (nx, ny, nz), dev = volume_lattice(volume)
+    tsdf, weight, rgb = volume["tsdf"], volume["weight"], volume.get("rgb")
+    depth, poses, (B, H, W), (fx, fy, cx, cy) = _views(depth, poses, intrinsics, dev)
+    pixel_weight = _gpu(pixel_weight, "pixel_weight", torch.float32, (B, H, W), device=dev)
+    if (color is None) != (rgb is None):
+        raise _lib.UcsaError("color frames and a colour volume come as a pair")
+    if color is not None:
+        color = _gpu(color, "color", torch.uint8, (B, H, W, 3), device=dev)
+    check(lib().ucsa_tsdf_integrate_weighted(
+        _ptr(tsdf), _ptr(weight), _ptr(rgb), nx, ny, nz, fvec(volume["origin"]),
+        fvec(volume["spacing"]), _ptr(depth), _ptr(pixel_weight), _ptr(color), _ptr(poses), B,
+        fx, fy, cx, cy, H, W, float(trunc), float(max_weight), float(depth_min),
+        float(depth_max), _stream()), "ucsa_tsdf_integrate_weighted")
+    return volume

@@ -11,7 +11,11 @@ before the frame is integrated, voted with or tracked.
 ``DepthFilter`` holds the settings; every consumer takes ``depth_filter=None``
 and with None none of this is entered.  ``simulate_sensor_noise`` (numpy, no
 GPU) makes the frames this is for out of exact ones: ``SyntheticRoom``'s depth
-has no noise, no quantisation and no flying pixels.
+has no noise, no quantisation and no flying pixels.  ``ViewWeights`` (default
+off as well: ``view_weights=None``) turns the same run's points, normals and
+mask into a weight per pixel -- inverse variance under the filter's noise model
+times the viewing cosine -- and the consumers then integrate ``clean`` through
+``ops.depth.integrate_tsdf_weighted``.
 
 Not here: hole filling, a depth pyramid, guidance by the colour image."""
 from __future__ import annotations
@@ -75,6 +79,54 @@ class DepthFilter:
                 kw[name] = value.lower() in ("1", "true")
             else:
                 kw[name] = int(value) if kind == "int" else float(value)
+        return cls(**kw)
+
+
+@dataclasses.dataclass(frozen=True)
+class ViewWeights:
+    """Settings of the per-pixel weight of ``ops.depth.integrate_tsdf_weighted``
+    (``frame_weights``): w = (sigma_depth / (sigma_depth + sigma_z2 z^2))^2 times
+    the cosine between normal and view ray, the cosine clamped to
+    [``cos_floor``, 1].  ``sigma_depth`` / ``sigma_z2``: None means the
+    ``DepthFilter``'s own value, so that the weight is the inverse variance of
+    the noise model the filter was given."""
+    cos_floor: float = 0.1
+    sigma_depth: float = None
+    sigma_z2: float = None
+
+    def resolved(self, flt: DepthFilter):
+        """(sigma_depth, sigma_z2) with ``flt``'s values in place of None"""
+        return (flt.sigma_depth if self.sigma_depth is None else float(self.sigma_depth),
+                flt.sigma_z2 if self.sigma_z2 is None else float(self.sigma_z2))
+
+    def scaled(self, unit: float) -> "ViewWeights":
+        """the same weights for depths multiplied by ``unit``, as ``DepthFilter.scaled``"""
+        unit = float(unit)
+        return dataclasses.replace(
+            self, sigma_depth=None if self.sigma_depth is None else self.sigma_depth * unit,
+            sigma_z2=None if self.sigma_z2 is None else self.sigma_z2 / unit)
+
+    def least(self, flt: DepthFilter, z_max: float) -> float:
+        """The least weight a kept pixel at depth <= ``z_max`` can get: the
+        ``min_weight`` that, with weights on, means "seen at least once" as 1
+        does without them."""
+        sd, s2 = self.resolved(flt)
+        return float(self.cos_floor) * (sd / (sd + s2 * float(z_max) ** 2)) ** 2
+
+    @classmethod
+    def from_string(cls, spec: str) -> "ViewWeights":
+        """``"cos_floor=0.2,sigma_z2=0.004"``: a comma-separated list of
+        field=value over the defaults; ``"default"`` or an empty string gives the
+        defaults."""
+        names = [f.name for f in dataclasses.fields(cls)]
+        kw = {}
+        spec = spec.strip()
+        for item in ([] if spec in ("", "default") else spec.split(",")):
+            name, sep, value = (s.strip() for s in item.partition("="))
+            if not sep or name not in names:
+                raise ValueError(f"view weights: {item!r} is not one of " +
+                                 ", ".join(f"{n}=" for n in names))
+            kw[name] = float(value)
         return cls(**kw)
 
 
@@ -161,6 +213,45 @@ def clean_depth(depth, intrinsics, flt: DepthFilter, depth_min=1e-6, depth_max=3
     out = run_frontend(d, intrinsics, flt, depth_min, depth_max)
     _count(stats, out["mask"], flt.reject)
     return out["clean"] if depth.dim() == 3 else out["clean"][0]
+
+
+def frame_weights(frontend_outputs, flt: DepthFilter, vw: ViewWeights):
+    """``run_frontend``'s dict -> the weight of every pixel's measurement,
+    float32 [B,H,W] on the GPU (``ops.depth.depth_confidence``): 0 at the pixels
+    ``flt`` rejects -- the zeros of ``clean`` -- and in (0, 1] at the others"""
+    from .. import ops
+    sd, s2 = vw.resolved(flt)
+    return ops.depth.depth_confidence(frontend_outputs["points"], frontend_outputs["normals"],
+                                      frontend_outputs["mask"], sd, s2, cos_floor=vw.cos_floor,
+                                      reject=flt.reject)
+
+
+def new_weight_stats():
+    """the sums ``weighted_depth`` adds to"""
+    return {"kept": 0, "weight_sum": 0.0}
+
+
+def weight_stats_line(stats) -> str:
+    """the scripts' one ``view_weights:`` line: the mean weight of the kept pixels"""
+    return (f"view_weights: mean weight {stats['weight_sum'] / max(1, stats['kept']):.4f} over "
+            f"{stats['kept']} kept pixels")
+
+
+def weighted_depth(depth, intrinsics, flt: DepthFilter, vw: ViewWeights, depth_min=1e-6,
+                   depth_max=3.0e38, stats=None, weight_stats=None):
+    """``depth`` [B,H,W] (a float32 tensor on the GPU) -> (``clean``, ``weight``),
+    [B,H,W] each: ``clean_depth``'s frames and ``frame_weights`` of the same run
+    of the front end, what ``ops.depth.integrate_tsdf_weighted`` takes.
+    ``weight_stats`` (``new_weight_stats()``) gains the number of kept pixels and
+    the sum of their weights, at the price of one read-back."""
+    import torch
+    out = run_frontend(depth, intrinsics, flt, depth_min, depth_max)
+    _count(stats, out["mask"], flt.reject)
+    w = frame_weights(out, flt, vw)
+    if weight_stats is not None:
+        weight_stats["kept"] += int((w > 0).sum())
+        weight_stats["weight_sum"] += float(w.sum(dtype=torch.float64))
+    return out["clean"], w
 
 
 def frame_points(depth, intrinsics, flt: DepthFilter, stride: int = 1, depth_min=1e-6,

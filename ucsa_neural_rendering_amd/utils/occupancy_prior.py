@@ -34,10 +34,15 @@ from .tsdf_fusion import depth_points_aabb
 def volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel=0.05, trunc=None,
                             aabb=None, batch=16, max_weight=65504.0, depth_min=1e-6,
                             depth_max=3.0e38, device="cuda", depth_filter=None,
-                            depth_filter_stats=None):
+                            depth_filter_stats=None, view_weights=None,
+                            view_weight_stats=None):
     """The TSDF volume (``ops.tsdf_volume``, no colour) of the views, chosen and
     integrated as ``fuse_depth_views`` does -> (volume, trunc, integrate_ms).
-    ``depth_filter`` / ``depth_filter_stats`` as for ``track_depth_views``."""
+    ``depth_filter`` / ``depth_filter_stats`` and ``view_weights`` /
+    ``view_weight_stats`` as for ``track_depth_views``."""
+    if view_weights is not None and depth_filter is None:
+        raise ValueError("view_weights needs depth_filter: the weights come from that run's "
+                         "points, normals and mask")
     if depth_filter is not None:
         from . import depth_frontend
     dev = torch.device(device)
@@ -63,20 +68,31 @@ def volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel=0.05, tru
         b = min(a + batch, N)
         z = _batch(depth_maps, a, b, np.float32, H, W, "depth_maps").to(dev)
         P = poses[a:b].to(dev)
-        if depth_filter is not None:
+        pw = None
+        if view_weights is not None:
+            z, pw = depth_frontend.weighted_depth(z, intrinsics, depth_filter, view_weights,
+                                                  depth_min, depth_max, stats=depth_filter_stats,
+                                                  weight_stats=view_weight_stats)
+        elif depth_filter is not None:
             z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
                                            stats=depth_filter_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ops.integrate_tsdf(vol, z, P, intrinsics, trunc, max_weight=max_weight,
-                           depth_min=depth_min, depth_max=depth_max)
+        if pw is not None:
+            ops.depth.integrate_tsdf_weighted(vol, z, pw, P, intrinsics, trunc,
+                                              max_weight=max_weight, depth_min=depth_min,
+                                              depth_max=depth_max)
+        else:
+            ops.integrate_tsdf(vol, z, P, intrinsics, trunc, max_weight=max_weight,
+                               depth_min=depth_min, depth_max=depth_max)
         torch.cuda.synchronize()
         t_i += time.perf_counter() - t0
     return vol, trunc, 1e3 * t_i
 
 
 def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.05, trunc=None,
-                           aabb=None, batch=16, depth_filter=None, **occupancy_kw):
+                           aabb=None, batch=16, depth_filter=None, view_weights=None,
+                           **occupancy_kw):
     """``poses`` [N,4,4] camera-to-world (NGP frame), ``depth_maps`` a sequence
     or callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), ``bound``
     the renderer's; ``voxel`` / ``trunc`` (default 4 voxels) / ``aabb`` (None =
@@ -90,11 +106,24 @@ def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.0
     ``occupancy_ms`` (device-synchronised host clock).  ``depth_filter`` (a
     ``utils.depth_frontend.DepthFilter``) integrates the frames as the depth
     front end cleans them and adds the rejection counts to the stats as
-    ``depth_filter``; None enters none of it."""
+    ``depth_filter``; None enters none of it.  ``view_weights`` (a
+    ``utils.depth_frontend.ViewWeights``; needs ``depth_filter``) integrates them
+    through ``ops.depth.integrate_tsdf_weighted`` with the confidence map of the
+    same run and adds ``view_weights`` to the stats.  The volume's weight is then
+    in units of pixel weight -- a voxel seen once at w = 0.3 holds 0.3 -- and so is
+    ``min_weight``: ``view_weights.least(depth_filter, z_max)`` carves what 1
+    carves without weights, the default of 1 only what several good views agree
+    on.  None enters none of it."""
+    if view_weights is not None and depth_filter is None:
+        raise ValueError("view_weights needs depth_filter: the weights come from that run's "
+                         "points, normals and mask")
     df_kw = {}
     if depth_filter is not None:
         from . import depth_frontend
         df_kw = {"depth_filter": depth_filter, "depth_filter_stats": depth_frontend.new_stats()}
+    if view_weights is not None:
+        df_kw.update(view_weights=view_weights,
+                     view_weight_stats=depth_frontend.new_weight_stats())
     vol, trunc, t_i = volume_from_depth_views(poses, intrinsics, H, W, depth_maps, voxel, trunc,
                                               aabb, batch, **df_kw)
     torch.cuda.synchronize()
@@ -111,6 +140,8 @@ def prior_from_depth_views(poses, intrinsics, H, W, depth_maps, bound, voxel=0.0
              "integrate_ms": t_i, "occupancy_ms": 1e3 * t_o}
     if depth_filter is not None:
         stats["depth_filter"] = df_kw["depth_filter_stats"]
+    if view_weights is not None:
+        stats["view_weights"] = df_kw["view_weight_stats"]
     return mask, stats
 
 

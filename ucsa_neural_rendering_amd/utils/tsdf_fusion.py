@@ -12,8 +12,9 @@ voxel state is read and written once per batch); ``ops.marching_cubes`` with
 with an unobserved corner (no second sheet one truncation distance behind the
 walls).  Per-voxel class votes and the ray-cast model view of the volume are in
 ``utils/voxel_map.py``.  Out of scope: sparse / hashed voxel blocks, bilinear
-depth lookup, distance- or angle-dependent weights, anything in the training
-loop.  ``fuse_depth_views(refine_poses=True)`` refines each frame's pose against
+depth lookup, anything in the training loop.  ``view_weights`` (with
+``depth_filter``) integrates every pixel with a weight from its range and
+viewing angle (``ops.depth.integrate_tsdf_weighted``).  ``fuse_depth_views(refine_poses=True)`` refines each frame's pose against
 the volume before it is integrated (``track_depth_views``).
 
 ``remove_small_components`` drops the floaters first: the specks of truncation
@@ -127,7 +128,7 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                      depth_min=1e-6, depth_max=3.0e38, device="cuda", min_component=0,
                      component_connectivity=26, refine_poses=False, refine_warmup=1,
                      refine_kw=None, refine_min_matched=0.25, refine_max_step=None,
-                     depth_filter=None):
+                     depth_filter=None, view_weights=None):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps``: a sequence
     or a callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), read
     batch by batch; ``color_maps`` likewise ``i -> [H,W,3]`` uint8 or None;
@@ -152,12 +153,25 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     integrated with the filtered frames without their rejected pixels, tracking
     takes the kept pixels' points, and the dict gains ``depth_filter``, the
     rejection counts (``depth_frontend.stats_line`` prints them).  The box is
-    still that of the raw frames.  None enters none of it."""
+    still that of the raw frames.  None enters none of it.  ``view_weights`` (a
+    ``utils.depth_frontend.ViewWeights``; needs ``depth_filter``, whose points,
+    normals and mask it reads) integrates the cleaned frames through
+    ``ops.depth.integrate_tsdf_weighted`` with ``depth_confidence``'s map, and
+    the dict gains ``view_weights`` (``depth_frontend.weight_stats_line``).  The
+    volume's weight, and so ``min_weight``, is then in units of pixel weight: a
+    voxel seen once at w = 0.3 holds 0.3, and ``min_weight`` =
+    ``view_weights.least(depth_filter, z_max)`` keeps what 1 keeps without
+    weights.  None enters none of it."""
     dev = torch.device(device)
-    df_stats = None
+    if view_weights is not None and depth_filter is None:
+        raise ValueError("view_weights needs depth_filter: the weights come from that run's "
+                         "points, normals and mask")
+    df_stats = vw_stats = None
     if depth_filter is not None:
         from . import depth_frontend
         df_stats = depth_frontend.new_stats()
+        if view_weights is not None:
+            vw_stats = depth_frontend.new_weight_stats()
     voxel = float(voxel)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
     if not (voxel > 0 and trunc > 0):
@@ -186,7 +200,9 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                                     refine_kw=refine_kw, refine_min_matched=refine_min_matched,
                                     refine_max_step=refine_max_step,
                                     **({} if depth_filter is None else
-                                       {"depth_filter": depth_filter, "depth_filter_stats": df_stats}))
+                                       {"depth_filter": depth_filter, "depth_filter_stats": df_stats}),
+                                    **({} if view_weights is None else
+                                       {"view_weights": view_weights, "view_weight_stats": vw_stats}))
         t_i = 1e-3 * tracked["integrate_ms"]
     # tracked: every view is in the volume already; otherwise a batch of views per call
     for a in ([] if tracked is not None else range(0, N, batch)):
@@ -200,13 +216,23 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                 raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape[1:]}")
             col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))).to(dev)
         P = poses[a:b].to(dev)
-        if depth_filter is not None:
+        pw = None
+        if view_weights is not None:
+            z, pw = depth_frontend.weighted_depth(z, intrinsics, depth_filter, view_weights,
+                                                  depth_min, depth_max, stats=df_stats,
+                                                  weight_stats=vw_stats)
+        elif depth_filter is not None:
             z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
                                            stats=df_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
-                           depth_min=depth_min, depth_max=depth_max)
+        if pw is not None:
+            ops.depth.integrate_tsdf_weighted(vol, z, pw, P, intrinsics, trunc, color=col,
+                                              max_weight=max_weight, depth_min=depth_min,
+                                              depth_max=depth_max)
+        else:
+            ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
+                               depth_min=depth_min, depth_max=depth_max)
         torch.cuda.synchronize()
         t_i += time.perf_counter() - t0
     stats = None
@@ -225,6 +251,8 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                      refine_ms=tracked["refine_ms"])
     if df_stats is not None:
         extra["depth_filter"] = df_stats
+    if vw_stats is not None:
+        extra["view_weights"] = vw_stats
     return {**extra, "verts": verts.cpu().numpy(), "faces": faces.cpu().numpy(),
             "normals": normals.cpu().numpy(),
             "rgb": None if rgb is None else rgb.cpu().numpy(), "labels": None,
@@ -235,7 +263,8 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
 def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_maps=None,
                       min_weight=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
                       refine_warmup=1, refine_kw=None, refine_min_matched=0.25,
-                      refine_max_step=None, depth_filter=None, depth_filter_stats=None):
+                      refine_max_step=None, depth_filter=None, depth_filter_stats=None,
+                      view_weights=None, view_weight_stats=None):
     """Frame-to-model tracking, the other half of KinectFusion: integrate the
     views into ``volume`` (in place) one per call, each with a pose refined
     against the volume as it then stands.  The first ``refine_warmup`` frames
@@ -256,8 +285,17 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
     ``utils.depth_frontend.DepthFilter``) a frame is tracked with the points of
     the pixels the front end keeps and integrated with its cleaned depth;
     ``depth_filter_stats`` (``depth_frontend.new_stats()``) gains the counts of
-    the integrated frames."""
+    the integrated frames.  ``view_weights`` (a ``ViewWeights``; needs
+    ``depth_filter``) integrates each frame through
+    ``ops.depth.integrate_tsdf_weighted`` with the confidence map of the same
+    run of the front end; the volume's weight is then in units of pixel weight,
+    and so is the ``min_weight`` tracking compares it with.
+    ``view_weight_stats`` (``depth_frontend.new_weight_stats()``) gains the kept
+    pixels' count and weight."""
     from .registration import pose_step, refine_pose_tsdf
+    if view_weights is not None and depth_filter is None:
+        raise ValueError("view_weights needs depth_filter: the weights come from that run's "
+                         "points, normals and mask")
     if depth_filter is not None:
         from . import depth_frontend
         kw_filter = {"depth_filter": depth_filter}
@@ -297,13 +335,23 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
         used.append(pose)
         records.append(rec)
         P = torch.from_numpy(pose.astype(np.float32)[None]).to(dev)
-        if depth_filter is not None:
+        pw = None
+        if view_weights is not None:
+            z, pw = depth_frontend.weighted_depth(z, intrinsics, depth_filter, view_weights,
+                                                  depth_min, depth_max, stats=depth_filter_stats,
+                                                  weight_stats=view_weight_stats)
+        elif depth_filter is not None:
             z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
                                            stats=depth_filter_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ops.integrate_tsdf(volume, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
-                           depth_min=depth_min, depth_max=depth_max)
+        if pw is not None:
+            ops.depth.integrate_tsdf_weighted(volume, z, pw, P, intrinsics, trunc, color=col,
+                                              max_weight=max_weight, depth_min=depth_min,
+                                              depth_max=depth_max)
+        else:
+            ops.integrate_tsdf(volume, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
+                               depth_min=depth_min, depth_max=depth_max)
         torch.cuda.synchronize()
         t_i += time.perf_counter() - t0
     return {"poses": np.stack(used), "refine": records, "integrate_ms": 1e3 * t_i,

@@ -19,7 +19,8 @@ first (``ops.smooth_voxel_table``): a voxel that one view reached decides with
 its neighbourhood, and a voxel that the geometry saw but no label reached takes
 its neighbours' label.  Out of
 scope: sparse / hashed blocks, float probabilities on the device, priors,
-view-dependent weights, pose refinement."""
+weights on the votes or the evidence (``view_weights`` weights the TSDF half
+only), pose refinement."""
 from __future__ import annotations
 
 import numpy as np
@@ -35,7 +36,7 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
                         min_votes=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
                         device="cuda", score_maps=None, min_margin=0, smooth=0,
                         smooth_neighbourhood=26, min_component=0, component_connectivity=26,
-                        depth_filter=None):
+                        depth_filter=None, view_weights=None):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps`` /
     ``label_maps`` / ``color_maps``: sequences or callables ``i -> [H,W]`` fp32
     z-depth in scene units (0 = none), ``[H,W]`` uint8 class ids (0 = no vote),
@@ -71,11 +72,24 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
     through the depth front end first: the volume is integrated and the votes
     or the evidence are cast with the filtered frames without their rejected
     pixels, and the dict gains ``depth_filter``, the rejection counts.  None
-    enters none of it."""
-    df_stats = None
+    enters none of it.
+    ``view_weights`` (a ``utils.depth_frontend.ViewWeights``; needs
+    ``depth_filter``) integrates the TSDF half through
+    ``ops.depth.integrate_tsdf_weighted`` with the confidence map of the same
+    run of the front end; the integer vote and evidence tables are not
+    weighted.  The volume's weight is then in units of pixel weight (a voxel seen
+    once at w = 0.3 holds 0.3), which is what ``observed``, the ray-caster's and
+    ``remove_small_components``' ``min_weight`` compare with; the dict gains
+    ``view_weights``.  None enters none of it."""
+    if view_weights is not None and depth_filter is None:
+        raise ValueError("view_weights needs depth_filter: the weights come from that run's "
+                         "points, normals and mask")
+    df_stats = vw_stats = None
     if depth_filter is not None:
         from . import depth_frontend
         df_stats = depth_frontend.new_stats()
+        if view_weights is not None:
+            vw_stats = depth_frontend.new_weight_stats()
     smooth = int(smooth)
     if smooth < 0:
         raise ValueError("smooth must be >= 0")
@@ -118,11 +132,19 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
                 raise ValueError(f"color_maps: views must be [{H},{W},3], got {col.shape[1:]}")
             col = torch.from_numpy(np.ascontiguousarray(col.astype(np.uint8, copy=False))).to(dev)
         P = poses[a:b].to(dev)
-        if depth_filter is not None:
-            z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min, depth_max,
-                                           stats=df_stats)
-        ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
-                           depth_min=depth_min, depth_max=depth_max)
+        if view_weights is not None:
+            z, pw = depth_frontend.weighted_depth(z, intrinsics, depth_filter, view_weights,
+                                                  depth_min, depth_max, stats=df_stats,
+                                                  weight_stats=vw_stats)
+            ops.depth.integrate_tsdf_weighted(vol, z, pw, P, intrinsics, trunc, color=col,
+                                              max_weight=max_weight, depth_min=depth_min,
+                                              depth_max=depth_max)
+        else:
+            if depth_filter is not None:
+                z = depth_frontend.clean_depth(z, intrinsics, depth_filter, depth_min,
+                                               depth_max, stats=df_stats)
+            ops.integrate_tsdf(vol, z, P, intrinsics, trunc, color=col, max_weight=max_weight,
+                               depth_min=depth_min, depth_max=depth_max)
         if soft:
             ops.accumulate_voxel_evidence(votes, vol, z, sc, P, intrinsics, trunc,
                                           depth_min=depth_min, depth_max=depth_max)
@@ -130,6 +152,8 @@ def fuse_semantic_views(poses, intrinsics, H, W, depth_maps, label_maps, color_m
             ops.vote_voxel_labels(votes, vol, z, lab, P, intrinsics, trunc, depth_min=depth_min,
                                   depth_max=depth_max)
     extra = {} if df_stats is None else {"depth_filter": df_stats}
+    if vw_stats is not None:
+        extra["view_weights"] = vw_stats
     if int(min_component) > 0:
         extra["components"] = remove_small_components(vol, int(min_component),
                                                       component_connectivity)
