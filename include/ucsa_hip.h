@@ -509,6 +509,12 @@ int32_t ucsa_composite_train_fwd_x3(
 uint32_t ucsa_mlp_pack_f16_halves(int32_t kind, uint32_t n_classes);
 int32_t ucsa_mlp_pack_f16(int32_t kind, const float* params, void* packed_half,
                           uint32_t n_classes, void* stream);
+/* Limit: a feature below 2^-14 is an fp16 subnormal (below 2^-25: zero).  The
+ * f16 MFMA aligns its products to the largest product EXPONENT and takes a
+ * subnormal operand at the exponent 2^-14, so such features carry an ABSOLUTE
+ * error of up to 2^-23 * 2^-14 * max|w| per term on the layer they enter, not a
+ * relative one (measured: docs/DESIGN_NOTEBOOK.md, section DN).  Features beyond
+ * 65504 become inf.  The _x3 and _h2 forms have neither limit within 2^20. */
 int32_t ucsa_sigma_mlp_fwd_f16(const float* feat, const void* packed_sigma_half,
                                uint32_t M, uint32_t n_levels, float* h,
                                float* sigma, void* stream);

@@ -1,6 +1,8 @@
 """numpy restatement of the colour / semantics / compositing stage and of its
 backward (include/ucsa_hip.h: ``ucsa_composite_fwd*``, ``ucsa_composite_train_fwd_*``,
-``ucsa_composite_bwd*``) and of the sigma-net backward (``ucsa_sigma_mlp_bwd*``):
+``ucsa_composite_bwd*``) and of the sigma net, backward (``ucsa_sigma_mlp_bwd*``)
+and forward (``ucsa_sigma_mlp_fwd*``: ``sigma_forward(outputs=True)``, used
+through tests/density_numpy.py):
 the float64 yardstick of tests/test_shade_reference_cpu.py and
 tests/test_gpu_shade_reference.py (test infrastructure: plain numpy, no torch
 op, no GPU, no HIP library).
@@ -606,14 +608,148 @@ def composite_backward(rays_d, norms, z_c, sigma_c, h_c, z_f, sigma_f, h_f,
 # ---------------------------------------------------------------------------
 # sigma net: 32 -> 64 (ReLU) -> 16, no padding constant
 # ---------------------------------------------------------------------------
-def sigma_forward(feat, sigma_params, mode=FP32, round_hidden=False, dt=F64):
-    p = _np(sigma_params, F64).astype(dt)
+H2_SIGMA_SCALE = 16.0              # ucsa_mlp_pack_h2: W1 x 2^-4, W2 x 2^4 (mfma_mlp_h2.h "RANGE")
+
+
+def _q_hidden(v, e):
+    """fp16 rounding of a layer input whose bound e need NOT be small against
+    an fp16 ulp (a ReLU output next to zero sits among the fp16 subnormals):
+    rounding is monotone, so the kernel's f16(v~), v~ in [v - e, v + e], lies in
+    [f16(v - e), f16(v + e)].  The value is ``_q``'s; the bound is the larger of
+    ``_q``'s and that interval's ends (they agree wherever e is below a
+    quarter ulp)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        q, eq = _q(v, e, F16M(1.0))
+        e = np.asarray(e, F64)
+        span = np.maximum(np.abs(q16(v + e) - q), np.abs(q16(v - e) - q))
+    return q, np.maximum(np.nan_to_num(eq, nan=0.0, posinf=np.inf), span)
+
+
+F16_MIN = 2.0 ** -14               # smallest normal fp16
+
+
+def _f16_subnormal_floor(x, W):
+    """What an fp16 MFMA contraction x W^T of K terms may lose when an operand
+    is an fp16 SUBNORMAL.  The matrix unit adds the K exact products as
+    fixed-point numbers aligned to the largest product EXPONENT of the block
+    and cuts them at fp32's 24 bits; a subnormal operand enters with the
+    exponent of the smallest normal, 2^-14, however many leading zeros its
+    mantissa has, so the cut lies up to 2^10 times higher above such a term
+    than ``_lin``'s relative (K + 1) u allows for.  Charged: one cut (2^-23) of
+    the largest NOMINAL product, max(|x|, 2^-14) max(|w|, 2^-14), per term,
+    wherever a term has a non-zero subnormal operand; nothing elsewhere (an
+    exact zero has no exponent to raise, normal operands are ``_lin``'s)."""
+    x64, W64 = np.abs(np.asarray(x, F64)), np.abs(np.asarray(W, F64))
+    sx, sw = (x64 > 0) & (x64 < F16_MIN), (W64 > 0) & (W64 < F16_MIN)
+    nx, nw = np.where(sx, F16_MIN, x64), np.where(sw, F16_MIN, W64)
+    with np.errstate(invalid="ignore"):
+        worst = (nx * sx).max(1)[:, None] * nw.max(1)[None, :] + \
+            np.where(np.isfinite(nx), nx, 0.0).max(1)[:, None] * (nw * sw).max(1)[None, :]
+    return W.shape[1] * 2.0 ** -23 * worst
+
+
+def sigma_forward(feat, sigma_params, mode=FP32, round_hidden=False, dt=F64,
+                  e_feat=None, outputs=False):
+    """The sigma net's first layer (what ``sigma_backward`` reads).
+
+    ``outputs=True`` goes on to what ``ucsa_sigma_mlp_fwd*`` return: ``h``
+    [M, 16], its bound ``e_h`` and ``sigma = exp(h[:, 0])`` as the allowed
+    interval [``sigma_lo``, ``sigma_hi``] (``sigma_interval``).  Then, in fp16
+    mode, the weights and the features are rounded to fp16 as the kernel loads
+    them and the hidden activation is rounded after the ReLU (chain_relu_h);
+    ``e_feat`` is the bound the features already carry (a hash-grid encode in
+    front: the features are then taken as float64, not as fp32 inputs).
+
+    Unlike the backward, the forward needs NO pinned gates: ReLU is
+    1-Lipschitz, so a pre-activation within its bound e of zero gives an
+    activation within e of the reference's whichever side either lies on;
+    ``_relu_e`` holds everywhere else.
+
+    f16x2 stores W1 x 2^-4 and W2 x 2^4 (``H2_SIGMA_SCALE``), so the ABSOLUTE
+    2^-36 of an operand stored 16 times smaller -- a small W1 entry, a hidden
+    activation -- counts 16 times against its partner: 15 ``absop`` sum |x| more
+    on the first layer, 15 ``absop`` sum |W2| more on the second than ``_lin``
+    charges for unscaled operands.
+
+    fp16 mode: features below 2^-14 and hidden activations below 2^-14 are
+    fp16 subnormals; both layers carry ``_f16_subnormal_floor``."""
+    p = _np(sigma_params, F64)
+    if outputs and mode.half:
+        p = q16(p)
+    p = p.astype(dt)
     W1, W2 = p[:2048].reshape(64, 32), p[2048:3072].reshape(16, 64)
-    x = np.asarray(_np(feat, F32), dt).reshape(-1, 32)
-    a1, e_a1 = _lin(x, np.zeros(x.shape), W1, mode, dt)
+    if e_feat is None:
+        x = np.asarray(_np(feat, F32), dt).reshape(-1, 32)
+        e_x = np.zeros(x.shape)
+    else:
+        x = np.asarray(feat, dt).reshape(-1, 32)
+        e_x = np.asarray(e_feat, F64).reshape(-1, 32)
+    if outputs:
+        with np.errstate(invalid="ignore", over="ignore"):
+            x, e_x = _q(x, e_x, mode)
+            e_x = np.nan_to_num(e_x, nan=0.0, posinf=np.inf)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a1, e_a1 = _lin(x, e_x, W1, mode, dt)
     if round_hidden:
         a1, e_a1 = _q(a1, e_a1, F16M(1.0))
-    return NS(W1=W1, W2=W2, x=x, a1=a1, e_a1=e_a1)
+    f = NS(W1=W1, W2=W2, x=x, a1=a1, e_a1=e_a1)
+    if not outputs:
+        return f
+    x64, a64 = np.abs(np.asarray(x, F64)), np.asarray(a1, F64)
+    extra = (H2_SIGMA_SCALE - 1.0) * mode.absop
+    with np.errstate(invalid="ignore", over="ignore"):
+        e_a1 = e_a1 + extra * x64.sum(1, keepdims=True)
+        if mode.half:
+            e_a1 = e_a1 + _f16_subnormal_floor(x, W1)
+        f.e_a1 = e_a1
+        hid = np.maximum(a1, 0)
+        e_hid = np.where(np.abs(a64) <= e_a1, e_a1, _relu_e(a1, e_a1))
+        if mode.half:
+            hid, e_hid = _q_hidden(hid, e_hid)
+        f.hid, f.e_hid = hid, e_hid
+        f.h, e_h = _lin(hid, e_hid, W2, mode, dt)
+        e_h = e_h + extra * np.abs(np.asarray(W2, F64)).sum(1)[None, :]
+        if mode.half:
+            e_h = e_h + _f16_subnormal_floor(hid, W2)
+        # an all-zero input row is exact in every mode (the terms of a split 0
+        # are 0, every product and sum is 0): no bound, absolute ones included
+        zero = ((x64 == 0) & (e_x == 0)).all(1, keepdims=True)
+        f.e_a1, f.e_hid, f.e_h = (np.where(zero, 0.0, v) for v in (e_a1, e_hid, e_h))
+        f.sigma_lo, f.sigma_hi = sigma_interval(f.h[:, 0], f.e_h[:, 0])
+    return f
+
+
+FLT_MAX = float(np.finfo(F32).max)
+FLT_MIN = 2.0 ** -126              # smallest normal fp32
+EXPF_ULP = 2.0 ** -23              # libm expf: 1 ulp (module docstring)
+
+
+def sigma_interval(h0, e_h0):
+    """Where ``expf(h0~)`` may land for h0~ within e_h0 of h0: [exp(h0 - e)
+    (1 - 2^-23), exp(h0 + e) (1 + 2^-23)] (expf: 1 ulp).  An end below 2^-126
+    moves out by 2^-126 (a subnormal result may be flushed or kept: both
+    pass).  ``sigma_hi`` > FLT_MAX allows +inf, ``sigma_lo`` > FLT_MAX demands
+    it (``in_sigma_interval``).  An exact-zero h0 with a zero bound is
+    expf(0) = 1.0 exactly.  A NaN h0 gives NaN ends."""
+    h0, e = np.asarray(h0, F64), np.asarray(e_h0, F64)
+    e = np.where(np.isfinite(h0), e, 0.0)          # +-inf: exp is inf / 0 whatever the bound says
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        lo = np.exp(h0 - e) * (1.0 - EXPF_ULP)
+        hi = np.exp(h0 + e) * (1.0 + EXPF_ULP)
+        lo = np.where(lo < FLT_MIN, np.maximum(lo - FLT_MIN, 0.0), lo)
+        hi = np.where(hi < FLT_MIN, hi + FLT_MIN, hi)
+    one = (h0 == 0.0) & (e == 0.0)
+    return np.where(one, 1.0, lo), np.where(one, 1.0, hi)
+
+
+def in_sigma_interval(got, lo, hi):
+    """bool per element: ``got`` (fp32 values) allowed by the interval."""
+    got = np.asarray(got, F64)
+    with np.errstate(invalid="ignore"):
+        finite_ok = np.isfinite(got) & (got >= lo) & (got <= hi) & ~(lo > FLT_MAX)
+        inf_ok = np.isposinf(got) & (hi > FLT_MAX)
+        nan_ok = np.isnan(got) & np.isnan(lo)
+    return finite_ok | inf_ok | nan_ok
 
 
 def sigma_backward(feat, d_h, sigma_params, mode=FP32, round_hidden=False, dt=F64,

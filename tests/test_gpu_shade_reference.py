@@ -113,6 +113,43 @@ def test_forward(ops, entry, case):
                        f"{entry} {case[0]}", c.name)
 
 
+# the split inference composite (csrc/composite_split.hip: k_weights_compact +
+# k_shade_dense / k_shade16): what every inference render runs
+INFER = {"composite_infer": ("fp32", "fp32", "mlp_pack"),
+         "composite_infer_f16": ("f16(gs=1024)", "f16", "mlp_pack_f16"),
+         "composite_infer_x3": ("fp32", "x3", "mlp_pack_x3"),
+         "composite_infer_h2": ("fp32", "h2", "mlp_pack_h2")}
+
+
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+@pytest.mark.parametrize("entry", list(INFER))
+def test_infer_forward(ops, entry, case):
+    """image, depth and semantics of the kernel pair within their bounds,
+    against the reference of the entry point's arithmetic.  The outputs start
+    as NaN: a ray without a masked sample must still get its zeros.
+    k_weights_compact decides the mask on its own fp32 weights, so the cases
+    carry the same pin as for the fused forwards (no weight within its bound
+    of 1e-4)."""
+    from ucsa_neural_rendering_amd import _lib
+    lib = _lib.lib()
+    pin, mode, pack = INFER[entry]
+    c = _case(*case, pin)
+    ref = _ref_forward(*case, pin, mode)
+    pc = getattr(ops, pack)(_lib.MLP_COLOR, _dev(c.color_params), c.C)
+    ps = getattr(ops, pack)(_lib.MLP_SEM, _dev(c.sem_params), c.C)
+    N, T, t = c.N, c.T, c.t
+    nan = lambda *shape: torch.full(shape, float("nan"), device="cuda")
+    image, depth, sem = nan(N, 3), nan(N), nan(N, c.C)
+    ws = torch.empty(max(16, int(lib.ucsa_composite_infer_workspace_bytes(N, T, t))),
+                     dtype=torch.uint8, device="cuda")
+    p = ops._ptr
+    _lib.check(getattr(lib, "ucsa_" + entry)(
+        *[p(v) for v in _stage(c)], p(pc), p(ps), N, T, t, c.C, float(c.density_scale),
+        p(image), p(depth), p(sem), p(ws), ops._stream()), "ucsa_" + entry)
+    torch.cuda.synchronize()
+    sn.compare_forward(dict(image=image, depth=depth, semantics=sem), ref, f"{entry} {case[0]}", c.name)
+
+
 # ---------------------------------------------------------------------------
 # backwards
 # ---------------------------------------------------------------------------
