@@ -2557,6 +2557,74 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
                            uint64_t workspace_doubles, double* sums, float* value,
                            uint8_t* matched, void* stream);
 
+/* ---- projective ICP against a pair of maps (not in the reference) ----
+ * KinectFusion's own tracker as one step: move the source points (and their
+ * normals) by a rigid transform into the target camera's frame, project each
+ * into the target's image, gather the target's point and normal at that pixel
+ * (projective data association: a gather, not a search), gate the pair, and
+ * reduce the point-to-plane normal equations to the 29 float64 numbers of
+ * ucsa_icp_sums, mode 0, in the same order and the same tree, so that
+ * utils/registration.py's solve_step and compose take them unchanged.  The
+ * target maps are those of a second frame (ucsa_depth_normals /
+ * ucsa_depth_frontend: frame to frame) or of the model ray-cast from the last
+ * pose (ucsa_tsdf_raycast: frame to model).  No volume, mesh or grid.
+ * tests/projective_numpy.py restates the contract; sums, pixel and residual
+ * equal it byte for byte.
+ *
+ * points [n][3] float32, the source points; normals [n][3] float32, their
+ * normals, or NULL: no compatibility gate.  target_points [H][W][3] and
+ * target_normals [H][W][3] float32 in the target camera's frame, target_mask
+ * [H][W] uint8, ucsa_depth_normals' bit field; reject a subset of
+ * UCSA_DEPTH_EDGE | UCSA_DEPTH_GRAZING.  fx, fy, cx, cy, max_dist, min_cos and
+ * transform (12 float32, the rows of [R | t]: source frame -> target camera
+ * frame) are read on the host.  workspace, workspace_doubles and sums as for
+ * ucsa_icp_sums.  pixel [n] int32 and residual [n] float32 are optional (NULL:
+ * not written).
+ * Per point i < n, in float32, every operation as written, nothing fused,
+ * division correctly rounded:
+ *  1. q_k = ((R[k][0]*x + R[k][1]*y) + R[k][2]*z) + t[k], as ucsa_icp_sums.
+ *  2. With source normals s: m_k = (R[k][0]*s0 + R[k][1]*s1) + R[k][2]*s2.
+ *  3. Unmatched unless q2 > 0 (a NaN fails).
+ *  4. u = floorf((fx*q0)/q2 + cx), v = floorf((fy*q1)/q2 + cy):
+ *     ucsa_tsdf_integrate's own expression (pixel (row v, column u) covers
+ *     [u, u+1) x [v, v+1), its centre at +0.5).
+ *  5. inside iff 0 <= u < (float)W and 0 <= v < (float)H, compared in float32
+ *     (a NaN fails).  Nothing is converted to an integer and no index is formed
+ *     before inside holds.
+ *  6. c = target_points[v][u], nt = target_normals[v][u], mk = target_mask[v][u].
+ *     The target is valid iff mk & UCSA_DEPTH_NORMAL, !(mk & reject) and all
+ *     six floats are finite.
+ *  7. d = c - q; dist2 = (d0*d0 + d1*d1) + d2*d2; matched iff
+ *     dist2 <= max_dist*max_dist, the square taken in float32, inclusive.
+ *  8. With source normals also (m0*nt0 + m1*nt1) + m2*nt2 >= min_cos (a NaN
+ *     fails).  Without them min_cos is checked and otherwise unused.
+ *  9. r = (nt0*d0 + nt1*d1) + nt2*d2,
+ *     J = (q1*nt2 - q2*nt1, q2*nt0 - q0*nt2, q0*nt1 - q1*nt0, nt0, nt1, nt2),
+ *     each of the first three a product, a product, then the difference.
+ * 10. The 29 float64 terms and their tree are items 5 and 6 of ucsa_icp_sums in
+ *     mode 0: +0.0 by a select for an unmatched row, so that no NaN leaks in;
+ *     n == 0 gives 29 times +0.0.
+ * 11. pixel[i] = v*W + u where matched, -1 otherwise; residual[i] = r where
+ *     matched, NaN otherwise.
+ * One lane per point in work-groups of 256 (k_projective_icp_sums), then
+ * k_icp_reduce while more than one row is left.  Every lane reaches the one
+ * barrier (a lane with i >= n takes the unmatched path); no atomics; the same
+ * bytes every run.  The inputs are never modified.
+ * Limits: points not NULL unless n == 0 (0); n <= 2^31-1 (2); the three maps
+ * not NULL (3, 4, 5); 1 <= H <= 16384 (6), 1 <= W <= 16384 (7); reject within
+ * EDGE | GRAZING (8); fx, fy > 0 and finite (9, 10); cx, cy finite (11, 12);
+ * transform (13); max_dist > 0 with a finite float32 square (14);
+ * -1 <= min_cos <= 1 (15); the workspace (16, 17); sums (18).  An argument
+ * error returns UCSA_ERR_ARG - index before any launch and nothing is
+ * written. */
+int32_t ucsa_projective_icp_sums(const float* points, const float* normals, uint32_t n,
+                                 const float* target_points, const float* target_normals,
+                                 const uint8_t* target_mask, uint32_t H, uint32_t W,
+                                 uint32_t reject, float fx, float fy, float cx, float cy,
+                                 const float* transform, float max_dist, float min_cos,
+                                 double* workspace, uint64_t workspace_doubles, double* sums,
+                                 int32_t* pixel, float* residual, void* stream);
+
 /* ---- The depth front end: bilateral filter, points, normals, edge rejection
  * (not in the reference) -----------------------------------------------------
  * What KinectFusion does to a depth frame before it integrates or tracks it
@@ -2652,7 +2720,28 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
  * Arguments: points (0), normals (1), mask (2), B >= 1 (3), 1 <= H <= 16384
  * (4), 1 <= W <= 16384 (5), sigma_depth > 0 finite (6), sigma_z2 >= 0 finite
  * (7), 0 < cos_floor <= 1 (8), reject within EDGE | GRAZING (9), weight
- * [B,H,W], sharing no byte with an input (10). */
+ * [B,H,W], sharing no byte with an input (10).
+ *
+ * ucsa_depth_pyramid_down: one level of the depth pyramid that coarse-to-fine
+ * tracking runs on: depth [B,H,W] -> coarse [B,h,w] with h = ceil(H/2),
+ * w = ceil(W/2).  A plain kernel, one thread per coarse pixel, no LDS.  Coarse
+ * pixel (I, J) takes the block (2I, 2J), (2I, 2J+1), (2I+1, 2J), (2I+1, 2J+1)
+ * in that (row-major) order, or what exists of it at an odd edge:
+ *   z0 = the smallest measured depth of the block (found by `z < z0` in that
+ *   order, so the first of equal ones); none measured: coarse = 0.  Otherwise
+ *   thr = max_jump + max_jump_z2 * (z0*z0);  s = 0, count = 0;
+ *   for each measured member z_k in that order: d = z_k - z0; taken iff
+ *   d <= thr: s = s + d, count = count + 1  (z0's own 0 is taken);
+ *   coarse = z0 + s / (float)count.
+ * The foreground wins: a block straddling a depth edge returns the mean of its
+ * near side and nothing is averaged across the edge.  The value is an offset
+ * from z0, the filter's form: a constant block comes back with its own bits.
+ * The coarse level's camera is fx/2, fy/2, cx/2, cy/2: exact under the +0.5
+ * centre convention (coarse pixel J covers [2J, 2J+2) of the fine image).
+ * Arguments: depth (0), B >= 1 (1), 1 <= H <= 16384 (2), 1 <= W <= 16384 (3),
+ * max_jump >= 0 finite (4), max_jump_z2 >= 0 finite (5), depth_min not NaN
+ * (6), depth_max >= depth_min (7), coarse [B,h,w], sharing no byte with depth
+ * (8). */
 #define UCSA_DEPTH_RANGE_BINS 256u
 #define UCSA_DEPTH_MEASURED 1u
 #define UCSA_DEPTH_NORMAL 2u
@@ -2677,6 +2766,9 @@ int32_t ucsa_depth_confidence(const float* points, const float* normals, const u
                               uint32_t B, uint32_t H, uint32_t W, float sigma_depth,
                               float sigma_z2, float cos_floor, uint32_t reject, float* weight,
                               void* stream);
+int32_t ucsa_depth_pyramid_down(const float* depth, uint32_t B, uint32_t H, uint32_t W,
+                                float max_jump, float max_jump_z2, float depth_min,
+                                float depth_max, float* coarse, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ first stage of the mapping-based pseudo-label baseline.
         [--min_weight K] [--no_color] [--pose_frame] \\
         [--min_component N] [--component_connectivity {6,26}] [--simplify CELL] \\
         [--refine_poses [--refine_warmup K] [--refine_iters N] [--refine_stride S] \\
-         [--refine_min_matched SHARE] [--poses_out FILE.npy]] [--depth_filter SPEC] \\
+         [--refine_min_matched SHARE] [--refine_method {tsdf,projective}] \\
+         [--poses_out FILE.npy]] [--odometry] [--depth_filter SPEC] \\
         [--view_weights SPEC]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
@@ -39,7 +40,16 @@ one (rank below 6, a matched share below ``--refine_min_matched``, a step beyond
 0.1 rad or the truncation distance).  It prints one ``refine:`` line: frames
 refined, fallbacks, median and maximum step in radians and scene units, median
 rmse (over the frames that matched at all); ``--poses_out`` writes the poses used, [N,4,4] float64 in the NGP frame,
-as .npy.  Without the flag nothing changes.  ``--depth_filter SPEC`` sends every
+as .npy.  Without the flag nothing changes.  ``--refine_method projective``
+tracks with projective ICP against the model ray-cast from the given pose
+(``utils.registration.refine_pose_projective``; ``--refine_stride`` must stay 1)
+under the same fallback rules; ``tsdf``, the default, is the tracker above.
+``--odometry`` ignores the scene's poses after the first frame: the poses come
+from frame-to-frame projective ICP on a depth pyramid
+(``utils.registration.odometry``), chained from the first frame's given pose.  It
+prints one ``odometry:`` line (frames, fallbacks, median matched share, median
+rmse), honours ``--poses_out`` and combines with ``--refine_poses``, which then
+refines the odometry's poses.  ``--depth_filter SPEC`` sends every
 frame through the depth front end (``utils.depth_frontend``: bilateral filter,
 normals, rejection of depth-edge and grazing pixels) before it is integrated or
 tracked; SPEC is ``default`` or a comma-separated list of ``DepthFilter``'s
@@ -106,6 +116,10 @@ def parse_args(argv=None):
     p.add_argument("--refine_stride", type=int, default=1, help="every S-th row and column")
     p.add_argument("--refine_min_matched", type=float, default=0.25,
                    help="a frame with a smaller matched share keeps its given pose")
+    p.add_argument("--refine_method", choices=("tsdf", "projective"), default="tsdf",
+                   help="the tracker of --refine_poses (default: tsdf)")
+    p.add_argument("--odometry", action="store_true",
+                   help="ignore the poses after frame 0: frame-to-frame projective ICP")
     p.add_argument("--poses_out", default=None, help="write the poses used (.npy, [N,4,4])")
     p.add_argument("--depth_filter", default=None, metavar="SPEC",
                    help="'default' or field=value,... of utils.depth_frontend.DepthFilter, "
@@ -134,8 +148,10 @@ def main(argv=None):
         raise SystemExit("--simplify must be > 0")
     if a.refine_warmup < 1 or a.refine_iters < 1 or a.refine_stride < 1:
         raise SystemExit("--refine_warmup, --refine_iters and --refine_stride must be >= 1")
-    if a.poses_out is not None and not a.refine_poses:
-        raise SystemExit("--poses_out needs --refine_poses")
+    if a.poses_out is not None and not (a.refine_poses or a.odometry):
+        raise SystemExit("--poses_out needs --refine_poses or --odometry")
+    if a.refine_method == "projective" and a.refine_stride != 1:
+        raise SystemExit("--refine_method projective takes no --refine_stride")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
     keep = list(range(0, len(fr["stems"]), a.every))
@@ -158,9 +174,29 @@ def main(argv=None):
         refine = {"refine_poses": True, "refine_warmup": a.refine_warmup,
                   "refine_min_matched": a.refine_min_matched,
                   "refine_kw": {"iterations": a.refine_iters, "stride": a.refine_stride}}
+        if a.refine_method != "tsdf":
+            refine["refine_method"] = a.refine_method
+            if a.depth_filter is None:   # the thresholds' defaults are metres
+                from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter
+                refine["refine_kw"].update(depth_filter=DepthFilter().scaled(uom), filtered=False)
     if a.depth_filter is not None:
         from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter, stats_line
         refine["depth_filter"] = DepthFilter.from_string(a.depth_filter).scaled(uom)
+    walked = None
+    if a.odometry:
+        from ucsa_neural_rendering_amd.utils.depth_frontend import DepthFilter
+        from ucsa_neural_rendering_amd.utils.registration import odometry
+        odo = odometry((depth(i) for i in range(len(stems))), fr["intrinsics"],
+                       depth_filter=refine.get("depth_filter", DepthFilter().scaled(uom)),
+                       filtered=a.depth_filter is not None)
+        first = np.asarray(poses[0], np.float64)
+        poses = np.stack([first @ p for p in odo["poses"]])
+        recs = [r for r in odo["records"] if r is not None]
+        med = lambda x: float(np.median(x)) if len(x) else None
+        walked = {"frames": len(stems), "fallbacks": odo["fallbacks"],
+                  "matched_median": med([r["matched"] for r in recs]),
+                  "rmse_median": med([r["rmse"] for r in recs if np.isfinite(r["rmse"])])}
+        print("odometry: " + json.dumps(walked))
     if a.view_weights is not None:
         from ucsa_neural_rendering_amd.utils.depth_frontend import (ViewWeights,
                                                                     weight_stats_line)
@@ -188,9 +224,9 @@ def main(argv=None):
                    "step_units_max": max([r["step"][1] for r in recs], default=None),
                    "rmse_median": med(rmse)}
         print("refine: " + json.dumps(tracked))
-        if a.poses_out is not None:
-            os.makedirs(os.path.dirname(os.path.abspath(a.poses_out)), exist_ok=True)
-            np.save(a.poses_out, mesh["poses"])
+    if a.poses_out is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(a.poses_out)), exist_ok=True)
+        np.save(a.poses_out, mesh["poses"] if a.refine_poses else np.asarray(poses, np.float64))
     simplified = None
     if a.simplify is not None:
         from ucsa_neural_rendering_amd.utils.mesh_fusion import simplify_mesh
@@ -217,6 +253,8 @@ def main(argv=None):
         rec["simplify"] = simplified
     if tracked is not None:
         rec["refine"] = tracked
+    if walked is not None:
+        rec["odometry"] = walked
     print(json.dumps(rec))
     return rec
 

@@ -405,6 +405,10 @@ SIGNATURES = {
     "ucsa_tsdf_icp_sums": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f), C.POINTER(_f), _p,
                                        _u32, C.POINTER(_f), _f, _f, _f, _p, C.c_uint64, _p, _p,
                                        _p, _p]),
+    # ---- projective ICP against a pair of maps (the same 29 sums, a gather) ----
+    "ucsa_projective_icp_sums": (C.c_int32, [_p, _p, _u32, _p, _p, _p, _u32, _u32, _u32, _f, _f,
+                                             _f, _f, C.POINTER(_f), _f, _f, _p, C.c_uint64, _p,
+                                             _p, _p, _p]),
     # ---- the depth front end (bilateral filter, points, normals, edge rejection) ----
     "ucsa_depth_filter": (C.c_int32, [_p, _u32, _u32, _u32, _p, _u32, _p, _f, _f, _f, _f, _p, _p]),
     "ucsa_depth_normals": (C.c_int32, [_p, _u32, _u32, _u32, _f, _f, _f, _f, _f, _f, _f, _f, _f,
@@ -412,6 +416,7 @@ SIGNATURES = {
     "ucsa_depth_frontend": (C.c_int32, [_p, _u32, _u32, _u32, _p, _u32, _p, _f, _f, _f, _f, _f,
                                         _f, _f, _f, _f, _u32, _f, _f, _p, _p, _p, _p, _p, _p]),
     "ucsa_depth_confidence": (C.c_int32, [_p, _p, _p, _u32, _u32, _u32, _f, _f, _f, _u32, _p, _p]),
+    "ucsa_depth_pyramid_down": (C.c_int32, [_p, _u32, _u32, _u32, _f, _f, _f, _f, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

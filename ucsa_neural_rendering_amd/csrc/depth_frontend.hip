@@ -30,6 +30,10 @@
 //                     weight of a pixel's measurement for
 //                     ucsa_tsdf_integrate_weighted from the points, normals and
 //                     mask above; tests/weighted_numpy.py restates it.
+//
+// k_depth_pyramid_down  (ucsa_depth_pyramid_down) one thread per coarse pixel, no
+//                     LDS: one level of the depth pyramid of coarse-to-fine
+//                     tracking; tests/projective_numpy.py restates it.
 #include <cmath>
 
 #include "ucsa_common.h"
@@ -304,6 +308,56 @@ __global__ void __launch_bounds__(DC_BLOCK) k_depth_confidence(DcArgs a) {
   a.weight[pix] = w;
 }
 
+// ucsa_depth_pyramid_down: one level of the depth pyramid.  One thread per
+// coarse pixel, up to four loads and one store, no LDS, no atomics.  A member of
+// the 2 x 2 block is read only where it exists: 2I + dy < H and 2J + dx < W.
+struct DpArgs {
+  const float* depth;
+  float* out;
+  uint32_t H, W, h, w;
+  float dmin, dmax, max_jump, max_jump_z2;
+};
+
+__global__ void __launch_bounds__(DC_BLOCK) k_depth_pyramid_down(DpArgs a) {
+  const uint32_t e = blockIdx.x * DC_BLOCK + threadIdx.x;
+  if (e >= a.h * a.w) return;
+  const uint32_t I = e / a.w, J = e - I * a.w;
+  const float* img = a.depth + (size_t)blockIdx.y * a.H * a.W;
+  float z[4];
+  bool ok[4];
+  float z0 = INFINITY;
+  bool any = false;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) {  // row-major over the block
+    const uint32_t i = 2u * I + (k >> 1), j = 2u * J + (k & 1u);
+    z[k] = 0.0f;
+    ok[k] = false;
+    if (i < a.H && j < a.W) {
+      z[k] = img[(size_t)i * a.W + j];
+      ok[k] = isfinite(z[k]) && z[k] >= a.dmin && z[k] <= a.dmax;
+    }
+    if (ok[k]) {
+      if (z[k] < z0) z0 = z[k];  // the first of equal ones: a -0.0 after a +0.0 does not replace it
+      any = true;
+    }
+  }
+  float r = 0.0f;
+  if (any) {
+    const float thr = a.max_jump + a.max_jump_z2 * (z0 * z0);
+    float s = 0.0f, count = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float d = z[k] - z0;
+      if (ok[k] && d <= thr) {
+        s = s + d;
+        count = count + 1.0f;
+      }
+    }
+    r = z0 + s / count;
+  }
+  a.out[(size_t)blockIdx.y * a.h * a.w + e] = r;
+}
+
 }  // namespace
 
 // the frames: arguments k0 .. k0 + 3 of every entry point
@@ -468,6 +522,37 @@ extern "C" int32_t ucsa_depth_confidence(const float* points, const float* norma
     a.weight = weight + off;
     const dim3 grid(ucsa_div_up(a.hw, DC_BLOCK), B - b0 < DF_MAXB ? B - b0 : DF_MAXB);
     hipLaunchKernelGGL(k_depth_confidence, grid, dim3(DC_BLOCK), 0, (hipStream_t)stream, a);
+  }
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_depth_pyramid_down(const float* depth, uint32_t B, uint32_t H, uint32_t W,
+                                           float max_jump, float max_jump_z2, float depth_min,
+                                           float depth_max, float* coarse, void* stream) {
+  DF_CHECK_FRAME(0);
+  UCSA_CHECK_ARG(max_jump >= 0.0f && std::isfinite(max_jump), 4);
+  UCSA_CHECK_ARG(max_jump_z2 >= 0.0f && std::isfinite(max_jump_z2), 5);
+  UCSA_CHECK_ARG(!std::isnan(depth_min), 6);
+  UCSA_CHECK_ARG(depth_max >= depth_min, 7);
+  DpArgs a;
+  a.H = H;
+  a.W = W;
+  a.h = ucsa_div_up(H, 2u);
+  a.w = ucsa_div_up(W, 2u);
+  const size_t hw = (size_t)H * W, chw = (size_t)a.h * a.w;
+  // coarse [B][h][w] floats shares no byte with depth
+  const char *c0 = (const char*)coarse, *d0 = (const char*)depth;
+  UCSA_CHECK_ARG(coarse && (c0 + 4 * chw * B <= d0 || d0 + 4 * hw * B <= c0), 8);
+  a.dmin = depth_min;
+  a.dmax = depth_max;
+  a.max_jump = max_jump;
+  a.max_jump_z2 = max_jump_z2;
+  UCSA_CLEAR_ERR();
+  for (uint32_t b0 = 0; b0 < B; b0 += DF_MAXB) {
+    a.depth = depth + (size_t)b0 * hw;
+    a.out = coarse + (size_t)b0 * chw;
+    const dim3 grid(ucsa_div_up((uint32_t)chw, DC_BLOCK), B - b0 < DF_MAXB ? B - b0 : DF_MAXB);
+    hipLaunchKernelGGL(k_depth_pyramid_down, grid, dim3(DC_BLOCK), 0, (hipStream_t)stream, a);
   }
   return ucsa_launch_status();
 }

@@ -2,7 +2,9 @@
 // The contract is stated in include/ucsa_hip.h; tests/register_numpy.py restates
 // it over the brute-force search of tests/surface_numpy.py and the 29 sums match
 // it byte for byte.  The same step against a TSDF volume, ucsa_tsdf_icp_sums
-// (k_tsdf_icp_sums, further down), shares the reduction and the reduce kernel.
+// (k_tsdf_icp_sums, further down), shares the reduction and the reduce kernel,
+// and so does the step against a pair of vertex and normal maps by projection,
+// ucsa_projective_icp_sums (k_projective_icp_sums, after it).
 //
 // k_icp_sums<MODE>  a lane per point in work-groups of 256: the point is moved by
 //                   [R | t], the nearest-triangle search of triangle_grid.hip
@@ -307,7 +309,150 @@ __global__ void __launch_bounds__(PG_THREADS) k_tsdf_icp_sums(const float* __res
   icp_finish(sh, out);
 }
 
+// ---- one step of projective ICP against a pair of maps: ucsa_projective_icp_sums ----
+// k_projective_icp_sums  a lane per point in work-groups of 256: the point (and
+//                  its normal) is moved by [R | t], projected into the target
+//                  camera with ucsa_tsdf_integrate's expression, and the target's
+//                  point, normal and mask at that pixel are gathered (seven loads
+//                  issued together).  The gates (mask, finite, distance, normal
+//                  compatibility) follow, then r = nt . (c - q), J = (q x nt, nt)
+//                  and the 29 terms, reduced as in k_icp_sums: icp_put /
+//                  icp_finish, then k_icp_reduce on the group results.
+//
+// Why every index is in range: no float is converted to an integer and no index
+// is formed before `inside` holds, that is q2 > 0 and 0 <= u < (float)W and
+// 0 <= v < (float)H for the floored u, v (a NaN fails every comparison).  u and
+// v are then integers in [0, W - 1] and [0, H - 1]; the host checks H, W <=
+// 16384, so v*W + u <= 2^28 - 1 and the uint32 product does not wrap.  A lane
+// with i >= n, or without a pixel, loads nothing from the maps, holds +0.0 for
+// all 29 terms and still reaches the one barrier.
+struct ProjTarget {
+  const float* points;
+  const float* normals;
+  const uint8_t* mask;
+  uint32_t H, W, reject;
+  float fx, fy, cx, cy;
+};
+
+__global__ void __launch_bounds__(PG_THREADS) k_projective_icp_sums(
+    const float* __restrict__ points, const float* __restrict__ normals, uint32_t n, ProjTarget G,
+    Rigid T, float limit2, float min_cos, double* __restrict__ out, int32_t* __restrict__ pixel,
+    float* __restrict__ residual) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  const uint32_t i = blockIdx.x * PG_THREADS + threadIdx.x;  // < 2^31 + 256
+  const bool live = i < n;
+  float q[3] = {NAN, NAN, NAN}, m[3] = {0.0f, 0.0f, 0.0f};
+  if (live) {
+    const float x = points[3ull * i], y = points[3ull * i + 1u], z = points[3ull * i + 2u];
+    q[0] = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    q[1] = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    q[2] = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+    if (normals) {
+      const float s0 = normals[3ull * i], s1 = normals[3ull * i + 1u], s2 = normals[3ull * i + 2u];
+      m[0] = (T.m[0] * s0 + T.m[1] * s1) + T.m[2] * s2;
+      m[1] = (T.m[4] * s0 + T.m[5] * s1) + T.m[6] * s2;
+      m[2] = (T.m[8] * s0 + T.m[9] * s1) + T.m[10] * s2;
+    }
+  }
+  bool inside = live && q[2] > 0.0f;
+  float u = 0.0f, v = 0.0f;
+  if (inside) {
+    u = floorf((G.fx * q[0]) / q[2] + G.cx);
+    v = floorf((G.fy * q[1]) / q[2] + G.cy);
+    inside = u >= 0.0f && u < (float)G.W && v >= 0.0f && v < (float)G.H;
+  }
+  float c[3] = {0.0f, 0.0f, 0.0f}, nt[3] = {0.0f, 0.0f, 0.0f};
+  uint32_t mk = 0u, pix = 0u;
+  if (inside) {
+    pix = (uint32_t)v * G.W + (uint32_t)u;
+    // all seven loads before the first use
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      c[a] = G.points[3ull * pix + a];
+      nt[a] = G.normals[3ull * pix + a];
+    }
+    mk = G.mask[pix];
+  }
+  bool matched = inside && (mk & UCSA_DEPTH_NORMAL) != 0u && (mk & G.reject) == 0u;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) matched = matched && isfinite(c[a]) && isfinite(nt[a]);
+  float d[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) d[a] = c[a] - q[a];
+  const float dist2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+  matched = matched && dist2 <= limit2;
+  if (normals) matched = matched && (m[0] * nt[0] + m[1] * nt[1]) + m[2] * nt[2] >= min_cos;
+  float V[8][1];  // J (0..5), r (6) and 1 (7); unused bits of an unmatched row are selected away
+  icp_row<1>(q[0], q[1], q[2], d[0], d[1], d[2], nt[0], nt[1], nt[2], V, 0);
+  if (live) {
+    if (pixel) pixel[i] = matched ? (int32_t)pix : -1;
+    if (residual) residual[i] = matched ? V[6][0] : NAN;
+  }
+  uint32_t col = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int b = a; b < 6; ++b) icp_put(icp_term<1>(matched, V[a], V[b]), col++, sh);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) icp_put(icp_term<1>(matched, V[a], V[6]), col++, sh);
+  icp_put(icp_term<1>(matched, V[6], V[6]), col++, sh);
+  icp_put(icp_term<1>(matched, V[7], V[7]), col++, sh);
+  icp_finish(sh, out);
+}
+
 }  // namespace
+
+extern "C" int32_t ucsa_projective_icp_sums(const float* points, const float* normals, uint32_t n,
+                                            const float* target_points,
+                                            const float* target_normals,
+                                            const uint8_t* target_mask, uint32_t H, uint32_t W,
+                                            uint32_t reject, float fx, float fy, float cx, float cy,
+                                            const float* transform, float max_dist, float min_cos,
+                                            double* workspace, uint64_t workspace_doubles,
+                                            double* sums, int32_t* pixel, float* residual,
+                                            void* stream) {
+  UCSA_CHECK_ARG(n <= 0x7FFFFFFFu, 2);
+  UCSA_CHECK_ARG(n == 0 || points, 0);
+  UCSA_CHECK_ARG(target_points, 3);
+  UCSA_CHECK_ARG(target_normals, 4);
+  UCSA_CHECK_ARG(target_mask, 5);
+  UCSA_CHECK_ARG(H >= 1 && H <= 16384, 6);
+  UCSA_CHECK_ARG(W >= 1 && W <= 16384, 7);
+  UCSA_CHECK_ARG((reject & ~(UCSA_DEPTH_EDGE | UCSA_DEPTH_GRAZING)) == 0u, 8);
+  UCSA_CHECK_ARG(fx > 0.0f && pg_host_finite(fx), 9);
+  UCSA_CHECK_ARG(fy > 0.0f && pg_host_finite(fy), 10);
+  UCSA_CHECK_ARG(pg_host_finite(cx), 11);
+  UCSA_CHECK_ARG(pg_host_finite(cy), 12);
+  UCSA_CHECK_ARG(transform, 13);
+  const float limit2 = max_dist * max_dist;
+  UCSA_CHECK_ARG(max_dist > 0.0f && pg_host_finite(max_dist) && pg_host_finite(limit2), 14);
+  UCSA_CHECK_ARG(min_cos >= -1.0f && min_cos <= 1.0f, 15);
+  const uint64_t ws_rows = icp_workspace_rows(n);
+  UCSA_CHECK_ARG(ws_rows == 0 || workspace, 16);
+  UCSA_CHECK_ARG(workspace_doubles >= ws_rows * ICP_SUMS, 17);
+  UCSA_CHECK_ARG(sums, 18);
+  ProjTarget G;
+  G.points = target_points, G.normals = target_normals, G.mask = target_mask;
+  G.H = H, G.W = W, G.reject = reject;
+  G.fx = fx, G.fy = fy, G.cx = cx, G.cy = cy;
+  Rigid T;
+  for (int k = 0; k < 12; ++k) T.m[k] = transform[k];
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t count = n ? ucsa_div_up(n, PG_THREADS) : 1u;  // at least one stage: n == 0 gives +0.0
+  double* out = count == 1u ? sums : workspace;
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_projective_icp_sums, dim3(count), dim3(PG_THREADS), 0, s, points, normals, n,
+                     G, T, limit2, min_cos, out, pixel, residual);
+  while (count > 1u) {  // as in ucsa_icp_sums: at most three passes for n < 2^31
+    const uint32_t next = ucsa_div_up(count, PG_THREADS);
+    const double* in = out;
+    out = next == 1u ? sums : out + (uint64_t)count * ICP_SUMS;
+    hipLaunchKernelGGL(k_icp_reduce, dim3(next), dim3(PG_THREADS), 0, s, in, count, out);
+    count = next;
+  }
+  return ucsa_launch_status();
+}
 
 extern "C" int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx,
                                       uint32_t ny, uint32_t nz, const float* origin3,

@@ -250,3 +250,25 @@ def integrate_tsdf_weighted(volume, depth, pixel_weight, poses, intrinsics, trun
         fx, fy, cx, cy, H, W, float(trunc), float(max_weight), float(depth_min),
         float(depth_max), _stream()), "ucsa_tsdf_integrate_weighted")
     return volume
+
+
+def pyramid_down(depth, max_jump: float, max_jump_z2: float = 0.0, depth_min: float = 1e-6,
+                 depth_max: float = 3.0e38):
+    """One level of the depth pyramid: ``depth`` [B,H,W] (float32 on the GPU) ->
+    float32 [B,ceil(H/2),ceil(W/2)].  A coarse pixel takes its 2 x 2 block (what
+    exists of it at an odd edge): with z0 the smallest measured depth of the
+    block, the mean of the measured members within ``max_jump`` +
+    ``max_jump_z2`` z0^2 of z0, as z0 plus the mean offset; 0 where nothing is
+    measured.  The foreground wins, so a depth edge is not averaged across, and
+    a constant block keeps its bits.  The coarse level's intrinsics are
+    (fx/2, fy/2, cx/2, cy/2).  ``depth`` is not modified.  Contract of
+    ucsa_depth_pyramid_down (include/ucsa_hip.h)."""
+    depth, (B, H, W) = _frames(depth)
+    max_jump = _non_negative(max_jump, "max_jump")
+    max_jump_z2 = _non_negative(max_jump_z2, "max_jump_z2")
+    depth_min, depth_max = _range(depth_min, depth_max)
+    out = torch.empty((B, -(-H // 2), -(-W // 2)), dtype=torch.float32, device=depth.device)
+    check(lib().ucsa_depth_pyramid_down(_ptr(depth), B, H, W, max_jump, max_jump_z2, depth_min,
+                                        depth_max, _ptr(out), _stream()),
+          "ucsa_depth_pyramid_down")
+    return out

@@ -1,9 +1,12 @@
 """Registration of points to a triangle mesh: the fused step of ICP over the
 grid of ``ops.triangle_grid``.  Reached as ``ops.register.icp_sums``.  The same
-step against a TSDF volume, without a mesh: ``ops.register.tsdf_sums``."""
+step against a TSDF volume, without a mesh: ``ops.register.tsdf_sums``; and
+against a pair of vertex and normal maps, by projection:
+``ops.register.projective_sums``."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -13,6 +16,7 @@ from ._args import _gpu, _mesh, _origin_spacing, _points3, _positive, _ptr, _str
 
 ICP_SUMS = 29
 MODES = {"plane": 0, "point": 1}
+_EDGE, _GRAZING = 4, 8  # ops.depth's mask bits (UCSA_DEPTH_EDGE, UCSA_DEPTH_GRAZING)
 
 
 def workspace_rows(n: int) -> int:
@@ -174,3 +178,64 @@ def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
         _ptr(pts) if n else None, n, t12, trunc, min_weight, max_tsdf, _ptr(ws), ws_doubles,
         _ptr(sums), _ptr(value), _ptr(matched), _stream()), "ucsa_tsdf_icp_sums")
     return (sums, value, matched) if return_matches else sums
+
+
+def projective_sums(points, normals, target_points, target_normals, target_mask, intrinsics,
+                    transform, max_dist: float, min_cos: float = 0.0,
+                    reject: int = _EDGE | _GRAZING, return_matches: bool = False):
+    """The normal equations of one projective point-to-plane ICP step of
+    ``points`` [N,3] (float32 on the GPU) against a pair of maps -> ``sums``
+    float64 [29] on the device, or (``sums``, ``pixel`` int32 [N], ``residual``
+    float32 [N]) with ``return_matches``.  The maps are ``target_points`` and
+    ``target_normals`` [H,W,3] float32 in the target camera's frame and
+    ``target_mask`` [H,W] uint8 (``ops.depth.depth_normals``' outputs for one
+    frame, or a model ray-cast dressed the same way); ``intrinsics`` (fx, fy,
+    cx, cy) is the target camera.  One call moves every point by ``transform``
+    (a 3x4 or 4x4 array-like on the host, converted to float32: source frame ->
+    target camera frame, q = R p + t), projects q into the target image with
+    ``ops.integrate_tsdf``'s expression and gathers the pixel it falls in: no
+    search.  The pair matches when the pixel has a normal (mask bit 2), carries
+    no bit of ``reject`` (a set of EDGE (4) | GRAZING (8)), its six floats are
+    finite, the target point c lies within ``max_dist`` of q and -- with source
+    ``normals`` [N,3]; None: no such gate -- the rotated source normal and the
+    target normal nt have a cosine >= ``min_cos``.  Over the matched points
+    r = nt . (c - q) and J = (q x nt, nt) are summed as ``icp_sums`` does in mode
+    "plane": the same 29 float64 numbers in the same tree, so
+    ``utils.registration.solve_step`` and ``compose`` take them unchanged.
+    ``pixel`` is the matched pixel's row-major index or -1, ``residual`` r or
+    NaN.  Contract of ucsa_projective_icp_sums (include/ucsa_hip.h)."""
+    pts = _points3(points, "points")
+    dev = pts.device
+    n = int(pts.shape[0])
+    nrm = None if normals is None else _gpu(normals, "normals", torch.float32, (n, 3), device=dev)
+    tp = _gpu(target_points, "target_points", torch.float32, (None, None, 3), device=dev)
+    H, W = int(tp.shape[0]), int(tp.shape[1])
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise _lib.UcsaError(f"target_points must be [H,W,3] with 1 <= H, W <= 16384, got "
+                             f"{tuple(tp.shape)}")
+    tn = _gpu(target_normals, "target_normals", torch.float32, (H, W, 3), device=dev)
+    tm = _gpu(target_mask, "target_mask", torch.uint8, (H, W), device=dev)
+    try:
+        fx, fy, cx, cy = [float(v) for v in intrinsics]
+    except (TypeError, ValueError):
+        raise _lib.UcsaError("intrinsics must be (fx, fy, cx, cy)")
+    if not (fx > 0 and fy > 0 and all(math.isfinite(v) for v in (fx, fy, cx, cy))):
+        raise _lib.UcsaError(f"intrinsics must have fx, fy > 0 and be finite, got "
+                             f"{(fx, fy, cx, cy)}")
+    t12 = _transform12(transform)
+    max_dist = _positive(max_dist, "max_dist")
+    min_cos = float(min_cos)
+    if not -1.0 <= min_cos <= 1.0:
+        raise _lib.UcsaError(f"min_cos must be in [-1, 1], got {min_cos!r}")
+    if isinstance(reject, bool) or not isinstance(reject, int) or reject & ~(_EDGE | _GRAZING):
+        raise _lib.UcsaError(f"reject must be a set of EDGE (4) | GRAZING (8), got {reject!r}")
+    ws_doubles = ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    pixel = torch.empty(n, dtype=torch.int32, device=dev) if return_matches else None
+    residual = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    check(lib().ucsa_projective_icp_sums(
+        _ptr(pts) if n else None, _ptr(nrm) if n else None, n, _ptr(tp), _ptr(tn), _ptr(tm), H, W,
+        reject, fx, fy, cx, cy, t12, max_dist, min_cos, _ptr(ws), ws_doubles, _ptr(sums),
+        _ptr(pixel), _ptr(residual), _stream()), "ucsa_projective_icp_sums")
+    return (sums, pixel, residual) if return_matches else sums

@@ -17,7 +17,8 @@ mask into a weight per pixel -- inverse variance under the filter's noise model
 times the viewing cosine -- and the consumers then integrate ``clean`` through
 ``ops.depth.integrate_tsdf_weighted``.
 
-Not here: hole filling, a depth pyramid, guidance by the colour image."""
+Not here: hole filling, guidance by the colour image (the depth pyramid is
+``ops.depth.pyramid_down``, used by ``utils.registration.frame_maps``)."""
 from __future__ import annotations
 
 import dataclasses

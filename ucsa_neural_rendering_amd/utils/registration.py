@@ -24,10 +24,16 @@ volume's signed distance at the moved point, the normal its gradient), for a
 pose already within the truncation distance of the answer: frame-to-model
 tracking while a scene is fused (``utils.tsdf_fusion.track_depth_views``).
 
+``register_frames`` / ``odometry`` / ``refine_pose_projective`` are KinectFusion's
+own tracker (``ops.register.projective_sums``): a frame's vertex and normal maps
+on a depth pyramid (``frame_maps``) against a second pair of maps -- the frame
+before it, or the model ray-cast from the last pose -- matched by projection, a
+gather in place of a search, with a distance and a normal-compatibility gate.
+
 Not here: scale, rejection of matches on open boundaries, normal compatibility
-gates, robust kernels beyond the ``max_dist`` schedule, global (coarse)
-alignment: the start must lie within ``max_dist`` and a few degrees of the
-answer."""
+gates in the mesh and TSDF routes, robust kernels beyond the ``max_dist``
+schedule, global (coarse) alignment: the start must lie within ``max_dist`` and
+a few degrees of the answer."""
 from __future__ import annotations
 
 import math
@@ -374,3 +380,199 @@ def pose_step(a, b):
     relative rotation and the distance of the camera centres"""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return rotation_angle(a[:3, :3] @ b[:3, :3].T), float(np.linalg.norm(a[:3, 3] - b[:3, 3]))
+
+
+# ---------------------------------------------------------------------------
+# projective association: frame to frame and frame to model
+# ---------------------------------------------------------------------------
+_NORMAL, _EDGE, _GRAZING = 2, 4, 8
+
+
+def level_intrinsics(intrinsics, level: int):
+    """(fx, fy, cx, cy) of pyramid level ``level``: each divided by 2^level, exact
+    under the +0.5 pixel-centre convention (coarse pixel J covers [2J, 2J + 2))"""
+    s = 2.0 ** int(level)
+    return tuple(float(v) / s for v in intrinsics)
+
+
+def frame_maps(depth, intrinsics, depth_filter=None, levels: int = 3, filtered=None,
+               depth_min: float = 1e-6, depth_max: float = 3.0e38, device="cuda"):
+    """The vertex and normal maps of one z-depth frame ``depth`` [H,W] on a depth
+    pyramid -> list over the levels, finest first, of dicts: ``depth`` [h,w],
+    ``points`` and ``normals`` [h,w,3] float32 in the camera frame, ``mask`` [h,w]
+    uint8 (``ops.depth.depth_normals``' bits) and ``intrinsics``
+    (``level_intrinsics``), all on the device.  Level 0 is the frame itself --
+    through the bilateral filter when a ``depth_filter`` (a
+    ``utils.depth_frontend.DepthFilter``) is given (``filtered`` overrides that
+    choice) -- and level l + 1 is ``ops.depth.pyramid_down`` of level l.  The
+    thresholds are the filter's (None: its defaults) with ``max_jump`` and
+    ``max_jump_z2`` multiplied by 2^level at level ``level``: a coarse pixel is
+    2^level times as wide, so the depth step between neighbours on a slanted
+    surface grows as much, and with the fine threshold the coarse levels lose
+    their normals."""
+    import torch
+
+    from .. import ops
+    from .depth_frontend import DepthFilter, run_frontend
+    flt = DepthFilter() if depth_filter is None else depth_filter
+    filtered = depth_filter is not None if filtered is None else bool(filtered)
+    d = depth if torch.is_tensor(depth) else torch.as_tensor(np.array(depth, np.float32))
+    d = d.to(device=device, dtype=torch.float32)[None].contiguous()
+    out = []
+    for level in range(int(levels)):
+        s = 2.0 ** level
+        K = level_intrinsics(intrinsics, level)
+        if level == 0 and filtered:
+            m = run_frontend(d, K, flt, depth_min, depth_max)
+            d = m["depth"]
+        else:
+            if level:
+                d = ops.depth.pyramid_down(d, flt.max_jump * (s / 2), flt.max_jump_z2 * (s / 2),
+                                           depth_min, depth_max)
+            m = ops.depth.depth_normals(d, K, flt.max_jump * s, flt.max_jump_z2 * s, flt.min_cos,
+                                        depth_min, depth_max)
+        out.append({"depth": d[0], "points": m["points"][0], "normals": m["normals"][0],
+                    "mask": m["mask"][0], "intrinsics": K})
+    return out
+
+
+def _source_rows(maps, reject):
+    """the pixels of one level a frame is registered with: those with a normal and
+    no bit of ``reject``, in row-major order -> (points [N,3], normals [N,3])"""
+    m = maps["mask"]
+    keep = ((m & _NORMAL) != 0) & ((m & reject) == 0)
+    return maps["points"][keep].contiguous(), maps["normals"][keep].contiguous()
+
+
+def register_frames(src_maps, dst_maps, intrinsics, init=None, iterations=(10, 5, 4),
+                    max_dist: float = 0.3, min_cos: float = 0.8, reject: int = _EDGE | _GRAZING,
+                    rcond: float = 1e-8, tol_rot: float = 1e-6, tol_trans: float = 1e-6):
+    """Align one frame to a second pair of maps by projective point-to-plane ICP,
+    coarse to fine -> ``register_points``' dict; ``transform`` (4x4 float64) moves
+    the source camera's frame into the target camera's, and every ``history``
+    entry carries its ``level``.  ``src_maps`` and ``dst_maps`` are
+    ``frame_maps``' lists (the target may also be a model view dressed the same
+    way: ``refine_pose_projective``); ``intrinsics`` (fx, fy, cx, cy) of level 0.
+    ``iterations`` gives the iterations per level, finest first, and the number
+    of levels: (10, 5, 4) runs 4 at level 2, then 5 at level 1, then 10 at level
+    0; ``(n,)`` is a single level.  A level ends early on a step with |omega| <=
+    ``tol_rot`` and |upsilon| <= ``tol_trans``.  The source points of a level are
+    its pixels with a normal and no bit of ``reject``; a pair matches within
+    ``max_dist`` and with a cosine of the normals >= ``min_cos``.  Each iteration
+    is ``ops.register.projective_sums``, one read of 29 doubles, ``solve_step``
+    and ``compose``.  The basin is set by ``max_dist`` and the scene, not by a
+    truncation band; rank < 6 says the views do not constrain the motion."""
+    from .. import ops
+    iterations = tuple(int(k) for k in iterations)
+    if not iterations or len(src_maps) < len(iterations) or len(dst_maps) < len(iterations):
+        raise ValueError(f"iterations names {len(iterations)} levels, the maps have "
+                         f"{len(src_maps)} and {len(dst_maps)}")
+    T = compose(np.eye(4) if init is None else np.asarray(init, np.float64), np.zeros(6))
+    history, rank, done, converged, n_points = [], 0, 0, False, 0
+    for level in reversed(range(len(iterations))):
+        pts, nrm = _source_rows(src_maps[level], reject)
+        dst = dst_maps[level]
+        K = level_intrinsics(intrinsics, level)
+        n_points, converged = int(pts.shape[0]), False
+        for _ in range(iterations[level]):
+            sums = ops.register.projective_sums(pts, nrm, dst["points"], dst["normals"],
+                                                dst["mask"], K, T, max_dist, min_cos,
+                                                reject).cpu().numpy()
+            _, _, sse, count = normal_equations(sums)
+            xi, rank = solve_step(sums, rcond)
+            T = compose(T, xi)
+            done += 1
+            om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
+            history.append({"level": level, "matched": int(round(count)),
+                            "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
+                            "omega": om, "upsilon": up, "max_dist": float(max_dist),
+                            "sums": sums})
+            if count > 0 and om <= tol_rot and up <= tol_trans:
+                converged = True
+                break
+    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
+    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
+            "iterations": done, "converged": converged, "history": history,
+            "n_points": n_points}
+
+
+def odometry(depths, intrinsics, depth_filter=None, iterations=(10, 5, 4),
+             min_matched: float = 0.25, filtered=None, device="cuda", **kw):
+    """Camera poses of a depth sequence without any given pose: ``register_frames``
+    of every frame to the one before it, chained -> dict: ``poses`` [N,4,4]
+    float64 camera-to-world with frame 0 at the identity, ``records`` (per pair
+    a dict: ``matched`` -- the share of the source points --, ``rmse``, ``rank``,
+    ``iterations``, ``fallback``; None for frame 0) and ``fallbacks``.  A pair
+    whose last solve has rank < 6 or whose matched share is below
+    ``min_matched`` falls back: its motion is kept at the identity and counted.
+    Frame to frame: the drift adds up; fuse and track against the model
+    (``refine_pose_projective``) where a volume is at hand.  ``depth_filter`` and
+    ``filtered`` are ``frame_maps``'; ``kw`` goes to ``register_frames``."""
+    levels = len(tuple(iterations))
+    poses, records, fallbacks, prev = [np.eye(4)], [None], 0, None
+    for d in depths:
+        maps = frame_maps(d, intrinsics, depth_filter, levels, filtered, device=device)
+        if prev is not None:
+            out = register_frames(maps, prev, intrinsics, iterations=iterations, **kw)
+            share = out["matched"] / out["n_points"] if out["n_points"] else 0.0
+            fallback = bool(out["rank"] < 6 or share < min_matched)
+            fallbacks += fallback
+            poses.append(poses[-1] @ (np.eye(4) if fallback else out["transform"]))
+            records.append({"matched": share, "rmse": out["rmse"], "rank": out["rank"],
+                            "iterations": out["iterations"], "fallback": fallback})
+        prev = maps
+    return {"poses": np.stack(poses), "records": records, "fallbacks": int(fallbacks)}
+
+
+def model_maps(volume, pose, intrinsics, sizes, trunc: float, near: float, far: float,
+               min_weight: float = 1.0):
+    """The model seen from the camera-to-world ``pose`` as target maps, one dict per
+    level of ``sizes`` [(h, w), ...] in ``frame_maps``' layout: the depth of
+    ``ops.raycast_tsdf`` with the level's intrinsics, its back-projection
+    (``ops.depth.depth_normals``' points), the ray-caster's world-frame normals
+    rotated into the camera frame (n_k = (R[0][k] n0 + R[1][k] n1) + R[2][k] n2,
+    elementwise float32) and mask 3 (measured, normal) where the normal is not
+    zero, 0 elsewhere."""
+    import torch
+
+    from .. import ops
+    dev = volume["tsdf"].device
+    P = torch.as_tensor(np.asarray(pose, np.float64)).to(torch.float32).to(dev)
+    out = []
+    for level, (h, w) in enumerate(sizes):
+        K = level_intrinsics(intrinsics, level)
+        rc = ops.raycast_tsdf(volume, P[None], K, int(h), int(w), near, far, trunc=trunc,
+                              min_weight=min_weight)
+        nw = rc["normal"][0]
+        points = ops.depth.depth_normals(rc["depth"], K, 0.0, 0.0, 0.0)["points"][0]
+        nc = torch.stack([(P[0, k] * nw[..., 0] + P[1, k] * nw[..., 1]) + P[2, k] * nw[..., 2]
+                          for k in range(3)], -1).contiguous()
+        mask = ((nw != 0).any(-1).to(torch.uint8) * 3).contiguous()
+        out.append({"depth": rc["depth"][0], "points": points, "normals": nc, "mask": mask,
+                    "intrinsics": K})
+    return out
+
+
+def refine_pose_projective(depth, pose, intrinsics, volume, trunc: float, iterations=(10,),
+                           near: float = 0.05, far: float = 100.0, min_weight: float = 1.0,
+                           depth_filter=None, filtered=None, depth_min: float = 1e-6,
+                           depth_max: float = 3.0e38, **kw):
+    """Refine the camera-to-world ``pose`` (4x4) of one z-depth frame ``depth``
+    [H,W] against the TSDF ``volume`` by projective ICP -> ``register_frames``'
+    dict with ``pose`` (4x4 float64) = ``pose`` . ``transform``.  The target
+    maps are the model ray-cast once from ``pose`` at every level
+    (``model_maps``; ``near`` / ``far`` bound the cast), the source maps are
+    ``frame_maps`` of the frame, and ``transform`` starts at the identity: the
+    motion from the frame's true camera to the camera at ``pose``.  Unlike
+    ``refine_pose_tsdf`` the pose error at the surface may exceed ``trunc``: the
+    gate is ``register_frames``' ``max_dist``.  ``depth_filter`` and ``filtered``
+    are ``frame_maps``'; ``kw`` goes to ``register_frames``."""
+    iterations = tuple(int(k) for k in iterations)
+    dev = volume["tsdf"].device
+    src = frame_maps(depth, intrinsics, depth_filter, len(iterations), filtered,
+                     depth_min=depth_min, depth_max=depth_max, device=dev)
+    sizes = [tuple(m["mask"].shape) for m in src]
+    dst = model_maps(volume, pose, intrinsics, sizes, trunc, near, far, min_weight)
+    out = register_frames(src, dst, intrinsics, iterations=iterations, **kw)
+    out["pose"] = np.asarray(pose, np.float64) @ out["transform"]
+    return out

@@ -128,7 +128,7 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                      depth_min=1e-6, depth_max=3.0e38, device="cuda", min_component=0,
                      component_connectivity=26, refine_poses=False, refine_warmup=1,
                      refine_kw=None, refine_min_matched=0.25, refine_max_step=None,
-                     depth_filter=None, view_weights=None):
+                     depth_filter=None, view_weights=None, refine_method="tsdf"):
     """``poses`` [N,4,4] camera-to-world (NGP frame); ``depth_maps``: a sequence
     or a callable ``i -> [H,W]`` fp32 z-depth in scene units (0 = none), read
     batch by batch; ``color_maps`` likewise ``i -> [H,W,3]`` uint8 or None;
@@ -147,6 +147,8 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
     arguments go to): the box is still computed from the given poses, the views
     are integrated one per call, and the dict gains ``poses`` [N,4,4] float64
     (the poses used), ``refine`` (the per-frame records) and ``refine_ms``.
+    ``refine_method`` "tsdf" (the default) or "projective" chooses the tracker, as
+    in ``track_depth_views``.
     With ``refine_poses=False`` nothing of that is entered and every byte of the
     result is what it was.  ``depth_filter`` (a ``utils.depth_frontend.DepthFilter``)
     sends every frame through the depth front end first: the volume is
@@ -199,6 +201,8 @@ def fuse_depth_views(poses, intrinsics, H, W, depth_maps, color_maps=None, aabb=
                                     depth_max=depth_max, refine_warmup=refine_warmup,
                                     refine_kw=refine_kw, refine_min_matched=refine_min_matched,
                                     refine_max_step=refine_max_step,
+                                    **({} if refine_method == "tsdf" else
+                                       {"refine_method": refine_method}),
                                     **({} if depth_filter is None else
                                        {"depth_filter": depth_filter, "depth_filter_stats": df_stats}),
                                     **({} if view_weights is None else
@@ -264,7 +268,7 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
                       min_weight=1, max_weight=65504.0, depth_min=1e-6, depth_max=3.0e38,
                       refine_warmup=1, refine_kw=None, refine_min_matched=0.25,
                       refine_max_step=None, depth_filter=None, depth_filter_stats=None,
-                      view_weights=None, view_weight_stats=None):
+                      view_weights=None, view_weight_stats=None, refine_method="tsdf"):
     """Frame-to-model tracking, the other half of KinectFusion: integrate the
     views into ``volume`` (in place) one per call, each with a pose refined
     against the volume as it then stands.  The first ``refine_warmup`` frames
@@ -291,8 +295,16 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
     run of the front end; the volume's weight is then in units of pixel weight,
     and so is the ``min_weight`` tracking compares it with.
     ``view_weight_stats`` (``depth_frontend.new_weight_stats()``) gains the kept
-    pixels' count and weight."""
-    from .registration import pose_step, refine_pose_tsdf
+    pixels' count and weight.  ``refine_method`` "projective" tracks with
+    ``utils.registration.refine_pose_projective`` instead -- the model ray-cast
+    from the given pose, projective association, the gate ``max_dist`` in place
+    of the truncation band -- under the same fallback rules; ``refine_kw`` is
+    then its keyword arguments (an integer ``iterations`` means one level; a
+    ``stride`` other than 1 is an error: the pyramid is its way to fewer
+    points)."""
+    from .registration import pose_step, refine_pose_projective, refine_pose_tsdf
+    if refine_method not in ("tsdf", "projective"):
+        raise ValueError(f"refine_method must be 'tsdf' or 'projective', got {refine_method!r}")
     if view_weights is not None and depth_filter is None:
         raise ValueError("view_weights needs depth_filter: the weights come from that run's "
                          "points, normals and mask")
@@ -305,6 +317,11 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
     poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
     kw = dict(refine_kw or {})
     kw.setdefault("min_weight", float(min_weight))
+    if refine_method == "projective":
+        if int(kw.pop("stride", 1)) != 1:
+            raise ValueError("refine_method='projective' takes no stride")
+        if isinstance(kw.get("iterations"), int):
+            kw["iterations"] = (kw["iterations"],)
     max_rot, max_trans = (0.1, float(trunc)) if refine_max_step is None else refine_max_step
     used, records, t_i, t_r = [], [], 0.0, 0.0
     for i in range(poses.shape[0]):
@@ -321,8 +338,14 @@ def track_depth_views(volume, poses, intrinsics, H, W, depth_maps, trunc, color_
         if i >= int(refine_warmup):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = refine_pose_tsdf(z[0], given, intrinsics, volume, trunc, depth_min=depth_min,
-                                   depth_max=depth_max, device=dev, **kw_filter, **kw)
+            if refine_method == "projective":
+                out = refine_pose_projective(z[0], given, intrinsics, volume, trunc,
+                                             depth_min=depth_min, depth_max=depth_max,
+                                             **kw_filter, **kw)
+            else:
+                out = refine_pose_tsdf(z[0], given, intrinsics, volume, trunc,
+                                       depth_min=depth_min, depth_max=depth_max, device=dev,
+                                       **kw_filter, **kw)
             t_r += time.perf_counter() - t0
             rot, trans = pose_step(out["pose"], given)
             share = out["matched"] / out["n_points"] if out["n_points"] else 0.0
