@@ -2557,6 +2557,49 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
                            uint64_t workspace_doubles, double* sums, float* value,
                            uint8_t* matched, void* stream);
 
+/* ---- scores of many rigid hypotheses against a TSDF volume (not in the reference) ----
+ * The evaluation half of a global registration (utils/registration.py:
+ * global_register_points_tsdf): K rigid transforms, each applied to the same n
+ * points and scored against the volume's distance field, in one call.  Four
+ * exact integers per transform, so that the result depends neither on the order
+ * of the points nor on the order of the adds.
+ * tests/global_register_numpy.py restates the contract; scores equals it byte
+ * for byte.
+ *
+ * tsdf, weight, nx, ny, nz, origin3, spacing3: as for ucsa_tsdf_icp_sums.
+ * points [n][3] float32 and transforms [K][12] float32 (the rows of [R | t] of
+ * every hypothesis) are on the device; min_weight and max_tsdf are host
+ * scalars.  scores [K][4] int64 on the device is zeroed and written here.
+ * Per (transform k, point i), in float32, every operation as written, nothing
+ * fused, division correctly rounded: steps 1 to 5 of ucsa_tsdf_icp_sums with
+ * transform k (q, g, inside, the cell, observed, F; the gradient is not
+ * formed).  Then
+ *   inlier = inside && observed && fabsf(F) <= max_tsdf,
+ *   free   = inside && observed && F > max_tsdf: the point lies in space the
+ *            volume saw to be empty (a NaN F is neither),
+ *   e      = (int64)rintf(fabsf(F) * 1048576.0f) for an inlier, else 0: the
+ *            product is exact, the rounding half-to-even, e <= 2^20.
+ * scores[k] = (sum inlier, sum free, sum e, sum e*e) over the points.
+ * One lane per point in work-groups of 256, UCSA_TSDF_SCORE_TILE transforms per
+ * work-group (k_tsdf_score); each work-group adds its four numbers per transform
+ * to scores with 64-bit integer atomics.  No float atomics; every lane reaches
+ * the one barrier; the same bytes every run.  The entry point splits K over as
+ * many launches as the grid needs.  The inputs are never modified.
+ * Limits: tsdf, weight not NULL (0, 1); nx, ny, nz >= 2 and nx*ny*nz <= 2^31-1
+ * (2, 3, 4); origin finite (5); spacing finite and > 0 (6); n <= 2^23 (8), so
+ * that sum e*e stays below 2^63, points not NULL unless n == 0 (7);
+ * K <= 2^31-1 (10), transforms not NULL unless K == 0 (9); min_weight > 0 (11);
+ * 0 < max_tsdf < 1 (12): at 1 free space would count as inlier; scores not NULL
+ * unless K == 0 (13).  An argument error returns UCSA_ERR_ARG - index before
+ * any launch and nothing is written.  K == 0: nothing is done; n == 0: scores
+ * is zeroed and nothing that reads points is launched. */
+#define UCSA_TSDF_SCORE_TILE 16
+int32_t ucsa_tsdf_score_transforms(const float* tsdf, const float* weight, uint32_t nx,
+                                   uint32_t ny, uint32_t nz, const float* origin3,
+                                   const float* spacing3, const float* points, uint32_t n,
+                                   const float* transforms, uint32_t K, float min_weight,
+                                   float max_tsdf, int64_t* scores, void* stream);
+
 /* ---- projective ICP against a pair of maps (not in the reference) ----
  * KinectFusion's own tracker as one step: move the source points (and their
  * normals) by a rigid transform into the target camera's frame, project each

@@ -11,7 +11,9 @@ and the geometry as accuracy, completeness, chamfer and F-score.
         [--visible_from SCENE_ROOT [--visible_every N] [--visible_bias 0.01] \\
          [--visible_far F] [--visible_min_views K]] \\
         [--register [--register_max_dist M] [--register_iters N] \\
-         [--register_mode {plane,point}] [--register_samples N]]
+         [--register_mode {plane,point}] [--register_samples N]] \\
+        [--register_global [--register_global_rotations N] [--register_global_keep M] \\
+         [--register_global_voxel V]]
 
 Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
 read a mesh in the frame of the JSON poses in metres (what the export and fusion
@@ -65,10 +67,21 @@ ground truth before any score: ICP of the predicted vertices -- or, with
 surface -- against the ground-truth surface
 (``utils.registration.register_meshes``), from the frames as loaded: a local
 refinement within ``--register_max_dist`` (default 0.5), not a search for a
-coarse alignment.  The predicted vertices are moved by the result, and one
+coarse alignment (that is ``--register_global``, below).  The predicted vertices are moved by the result, and one
 ``register: {...}`` line carries the 4 x 4 ``transform``, ``rmse``, the
 ``matched`` share of the source points, ``rank`` (below 6: the ground truth
 did not constrain the motion) and ``iterations``.
+``--register_global`` (needs faces in both meshes) finds the coarse alignment that
+``--register`` starts from: a search over ``--register_global_rotations`` rotations
+(default 4 096) of the predicted surface against a TSDF volume made from the
+ground truth at ``--register_global_voxel`` (default: the ground truth's largest
+extent / 64), the best ``--register_global_keep`` (default 16) refined
+(``utils.registration.global_register_meshes``).  It runs before ``--register``
+when both are given; the predicted vertices are moved by the result, and one
+``register_global: {...}`` line carries the 4 x 4 ``transform``, the ``score``
+(inliers, points in free space, sum e, sum e^2), ``n_hypotheses``, ``rmse``,
+``rank`` and ``ambiguous`` (true: a symmetric target, another pose scores as
+well).
 Prints ``3d: {...}`` when both meshes carry labels, and ``geometry: {...}``."""
 import argparse
 import json
@@ -124,6 +137,15 @@ def parse_args(argv=None):
     p.add_argument("--register_samples", type=int, default=None, metavar="N",
                    help="align about N area-uniform samples of the predicted surface, not its "
                         "vertices")
+    p.add_argument("--register_global", action="store_true",
+                   help="find the coarse alignment of the prediction by a search over rotations "
+                        "before any score (and before --register)")
+    p.add_argument("--register_global_rotations", type=int, default=4096)
+    p.add_argument("--register_global_keep", type=int, default=16,
+                   help="the best hypotheses that are refined")
+    p.add_argument("--register_global_voxel", type=float, default=None,
+                   help="the voxel of the ground-truth volume, scene units "
+                        "(default: its largest extent / 64)")
     return p.parse_args(argv)
 
 
@@ -156,6 +178,31 @@ def register(a, pred, gv, gt_faces):
             "mode": a.register_mode, "points": out["n_points"]}
 
 
+def register_global(a, pred, gv, gt_faces):
+    """--register_global: move ``pred``'s vertices by the best of a search over
+    rotations -> the ``register_global:`` record"""
+    from ucsa_neural_rendering_amd.utils.registration import global_register_meshes
+    if gt_faces is None or not len(gt_faces) or pred["faces"] is None or not len(pred["faces"]):
+        raise SystemExit("--register_global needs faces in both meshes")
+    if a.register_global_rotations < 1 or a.register_global_keep < 1:
+        raise SystemExit("--register_global_rotations and --register_global_keep must be >= 1")
+    voxel = a.register_global_voxel
+    if voxel is None:
+        ok = gv[np.isfinite(gv).all(1)]
+        voxel = float((ok.max(0) - ok.min(0)).max()) / 64.0 if len(ok) else 0.0
+    if not voxel > 0:
+        raise SystemExit("--register_global_voxel must be > 0")
+    out = global_register_meshes(pred, {"verts": gv, "faces": gt_faces}, voxel,
+                                 seed=a.sample_seed, n_rotations=a.register_global_rotations,
+                                 keep=a.register_global_keep)
+    T = out["transform"]
+    pred["verts"] = (pred["verts"].astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    return {"transform": [[float(x) for x in row] for row in T], "score": list(out["score"]),
+            "n_hypotheses": out["n_hypotheses"], "ambiguous": out["ambiguous"],
+            "rmse": out["rmse"], "rank": out["rank"], "points": out["n_points"],
+            "voxel": voxel}
+
+
 def main(argv=None):
     a = parse_args(argv)
     if not (a.max_dist > 0 and a.threshold > 0):
@@ -167,6 +214,9 @@ def main(argv=None):
         T = np.loadtxt(a.gt_transform, dtype=np.float64).reshape(4, 4)
         gv = (gv.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
     rec = {}
+    if a.register_global:
+        rec["register_global"] = register_global(a, pred, gv, gt["faces"])
+        print("register_global: " + json.dumps(rec["register_global"]))
     if a.register:
         rec["register"] = register(a, pred, gv, gt["faces"])
         print("register: " + json.dumps(rec["register"]))

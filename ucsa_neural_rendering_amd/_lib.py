@@ -405,6 +405,9 @@ SIGNATURES = {
     "ucsa_tsdf_icp_sums": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f), C.POINTER(_f), _p,
                                        _u32, C.POINTER(_f), _f, _f, _f, _p, C.c_uint64, _p, _p,
                                        _p, _p]),
+    # ---- scores of K rigid hypotheses against a TSDF volume (four exact integers each) ----
+    "ucsa_tsdf_score_transforms": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                               C.POINTER(_f), _p, _u32, _p, _u32, _f, _f, _p, _p]),
     # ---- projective ICP against a pair of maps (the same 29 sums, a gather) ----
     "ucsa_projective_icp_sums": (C.c_int32, [_p, _p, _u32, _p, _p, _p, _u32, _u32, _u32, _f, _f,
                                              _f, _f, C.POINTER(_f), _f, _f, _p, C.c_uint64, _p,

@@ -9,7 +9,7 @@ The wrappers live in one module per family (``render``, ``backward``, ``train``,
 ``_args``; this file only re-exports them, so ``ops.NAME`` is the way in.
 ``raycast`` came after the surface of ``ops`` was frozen and is reached as a
 module: ``ops.raycast.raycast_mesh``; so is ``register``: ``ops.register.icp_sums``,
-``ops.register.tsdf_sums``, ``ops.register.projective_sums``; and ``depth``:
+``ops.register.tsdf_sums``, ``ops.register.projective_sums``, ``ops.register.tsdf_scores``; and ``depth``:
 ``ops.depth.depth_frontend``, ``ops.depth.pyramid_down``.
 """
 from .. import _lib

@@ -2,7 +2,8 @@
 grid of ``ops.triangle_grid``.  Reached as ``ops.register.icp_sums``.  The same
 step against a TSDF volume, without a mesh: ``ops.register.tsdf_sums``; and
 against a pair of vertex and normal maps, by projection:
-``ops.register.projective_sums``."""
+``ops.register.projective_sums``.  Many rigid hypotheses scored against a TSDF
+volume in one call, for a global search: ``ops.register.tsdf_scores``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,6 +18,8 @@ from ._args import _gpu, _mesh, _origin_spacing, _points3, _positive, _ptr, _str
 ICP_SUMS = 29
 MODES = {"plane": 0, "point": 1}
 _EDGE, _GRAZING = 4, 8  # ops.depth's mask bits (UCSA_DEPTH_EDGE, UCSA_DEPTH_GRAZING)
+TSDF_SCORE_TILE = 16    # transforms per work-group of k_tsdf_score (UCSA_TSDF_SCORE_TILE)
+TSDF_SCORE_MAX_POINTS = 1 << 23
 
 
 def workspace_rows(n: int) -> int:
@@ -178,6 +181,53 @@ def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
         _ptr(pts) if n else None, n, t12, trunc, min_weight, max_tsdf, _ptr(ws), ws_doubles,
         _ptr(sums), _ptr(value), _ptr(matched), _stream()), "ucsa_tsdf_icp_sums")
     return (sums, value, matched) if return_matches else sums
+
+
+def tsdf_scores(volume, points, transforms, min_weight: float = 1.0, max_tsdf: float = 0.75):
+    """The scores of K rigid hypotheses of ``points`` [N,3] (float32 on the GPU)
+    against the TSDF ``volume`` (``ops.tsdf_volume``'s dict) -> int64 [K,4] on the
+    device, in one call.  ``transforms`` is float32 [K,3,4] or [K,4,4] on the
+    volume's device (the first three rows are taken: q = R p + t); it stays on
+    the device because there can be millions.  Per transform the row is
+    (inliers, free, sum e, sum e^2) over the points: a moved point is sampled
+    as ``tsdf_sums`` samples it (inside the lattice, all eight corners of its
+    cell with weight >= ``min_weight``, the trilinear value F); it is an inlier
+    when |F| <= ``max_tsdf``, it lies in free space -- where the volume saw
+    nothing -- when F > ``max_tsdf``, and e = rint(|F| * 2^20) of an inlier.
+    All four are exact integers: the bytes depend neither on the order of the
+    points nor on anything else that varies between runs.  ``max_tsdf`` lies in
+    (0, 1): at 1 free space would count as inlier.  At most 2^23 points.
+    ``utils.registration.global_register_points_tsdf`` ranks hypotheses by
+    inliers - free, then sum e^2.  Contract of ucsa_tsdf_score_transforms
+    (include/ucsa_hip.h)."""
+    (nx, ny, nz), dev = volume_lattice(volume)
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
+                             f"{(nx, ny, nz)}")
+    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
+    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
+    n = int(pts.shape[0])
+    if n > TSDF_SCORE_MAX_POINTS:
+        raise _lib.UcsaError("points must have at most 2^23 rows")
+    T = _gpu(transforms, "transforms", torch.float32, (None, None, 4), device=dev)
+    if T.shape[1] not in (3, 4):
+        raise _lib.UcsaError(f"transforms must be [K,3,4] or [K,4,4], got {tuple(T.shape)}")
+    T = T[:, :3].contiguous()
+    K = int(T.shape[0])
+    if K > 0x7FFFFFFF:
+        raise _lib.UcsaError("transforms must have at most 2^31-1 rows")
+    min_weight = float(min_weight)
+    if not min_weight > 0:
+        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
+    max_tsdf = float(max_tsdf)
+    if not 0 < max_tsdf < 1:
+        raise _lib.UcsaError(f"max_tsdf must be in (0, 1), got {max_tsdf!r}")
+    scores = torch.empty((K, 4), dtype=torch.int64, device=dev)
+    check(lib().ucsa_tsdf_score_transforms(
+        _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
+        _ptr(pts) if n else None, n, _ptr(T) if K else None, K, min_weight, max_tsdf,
+        _ptr(scores) if K else None, _stream()), "ucsa_tsdf_score_transforms")
+    return scores
 
 
 def projective_sums(points, normals, target_points, target_normals, target_mask, intrinsics,

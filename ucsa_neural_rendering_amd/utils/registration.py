@@ -30,10 +30,14 @@ on a depth pyramid (``frame_maps``) against a second pair of maps -- the frame
 before it, or the model ray-cast from the last pose -- matched by projection, a
 gather in place of a search, with a distance and a normal-compatibility gate.
 
+``global_register_points_tsdf`` / ``global_register_meshes`` find the coarse
+alignment those loops start from: hypotheses over a rotation set scored against
+a TSDF volume in one call (``ops.register.tsdf_scores``), the best refined.
+
 Not here: scale, rejection of matches on open boundaries, normal compatibility
 gates in the mesh and TSDF routes, robust kernels beyond the ``max_dist``
-schedule, global (coarse) alignment: the start must lie within ``max_dist`` and
-a few degrees of the answer."""
+schedule: the local loops must start within ``max_dist`` (or ``trunc``) and a few
+degrees of the answer."""
 from __future__ import annotations
 
 import math
@@ -327,7 +331,7 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
     so the pose error, measured at the surface (translation plus angle times
     the distance to the surface), must stay below ``trunc``.  Anything coarser
     is the mesh route's job (``register_points`` with a ``max_dist_schedule``)
-    or global alignment, which is not here."""
+    or global alignment (``global_register_points_tsdf``)."""
     import torch
 
     from .. import ops
@@ -576,3 +580,228 @@ def refine_pose_projective(depth, pose, intrinsics, volume, trunc: float, iterat
     out = register_frames(src, dst, intrinsics, iterations=iterations, **kw)
     out["pose"] = np.asarray(pose, np.float64) @ out["transform"]
     return out
+
+
+# ---------------------------------------------------------------------------
+# global alignment: many hypotheses scored against a TSDF volume
+# ---------------------------------------------------------------------------
+_SF_PHI = math.sqrt(2.0)
+_SF_PSI = 1.533751168755204288118041
+
+
+def rotation_set(n: int):
+    """``n`` rotations spread evenly over SO(3) -> float64 [n,3,3], deterministic:
+    the super-Fibonacci spiral (Alexa 2022).  With s = i + 1/2, the unit
+    quaternion i is (sqrt(s/n) sin a, sqrt(s/n) cos a, sqrt(1 - s/n) sin b,
+    sqrt(1 - s/n) cos b) with a = 2 pi s / sqrt(2) and b = 2 pi s / psi,
+    psi = 1.5337511687552043 (the root of psi^4 = psi + 4).  Host, numpy; the
+    covering angle of ``rotation_set(4096)`` is measured in
+    tests/test_global_register_cpu.py."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"rotation_set needs n >= 1, got {n}")
+    s = np.arange(n, dtype=np.float64) + 0.5
+    r, R = np.sqrt(s / n), np.sqrt(1.0 - s / n)
+    a, b = 2.0 * math.pi * s / _SF_PHI, 2.0 * math.pi * s / _SF_PSI
+    x, y, z, w = r * np.sin(a), r * np.cos(a), R * np.sin(b), R * np.cos(b)
+    out = np.empty((n, 3, 3), np.float64)
+    out[:, 0, 0] = 1.0 - 2.0 * (y * y + z * z)
+    out[:, 0, 1] = 2.0 * (x * y - z * w)
+    out[:, 0, 2] = 2.0 * (x * z + y * w)
+    out[:, 1, 0] = 2.0 * (x * y + z * w)
+    out[:, 1, 1] = 1.0 - 2.0 * (x * x + z * z)
+    out[:, 1, 2] = 2.0 * (y * z - x * w)
+    out[:, 2, 0] = 2.0 * (x * z - y * w)
+    out[:, 2, 1] = 2.0 * (y * z + x * w)
+    out[:, 2, 2] = 1.0 - 2.0 * (x * x + y * y)
+    return out
+
+
+def surface_centroid(volume, trunc: float, min_weight: float = 1.0):
+    """The mean position of the voxels of a TSDF ``volume`` (numpy arrays or
+    tensors on any device) that lie within one voxel of its surface: weight >=
+    ``min_weight`` and |tsdf| * ``trunc`` <= the largest spacing, both in
+    float32 -> float64 [3].  The voxels' indices are summed as integers, so the
+    result is the same to the bit wherever the volume lives."""
+    tsdf, weight = volume["tsdf"], volume["weight"]
+    o = np.asarray(volume["origin"], np.float32).astype(np.float64).reshape(3)
+    h32 = np.broadcast_to(np.asarray(volume["spacing"], np.float32), (3,))
+    voxel, tr, mw = float(h32.max()), float(np.float32(trunc)), float(np.float32(min_weight))
+    if hasattr(tsdf, "detach"):                       # a tensor
+        band = (weight >= mw) & (tsdf.abs() * tr <= voxel)
+        idx = band.nonzero()
+        count, total = int(idx.shape[0]), idx.sum(0).cpu().numpy().astype(np.int64)
+    else:
+        t32, w32 = np.asarray(tsdf, np.float32), np.asarray(weight, np.float32)
+        band = (w32 >= np.float32(mw)) & (np.abs(t32) * np.float32(tr) <= np.float32(voxel))
+        idx = np.argwhere(band)
+        count, total = int(idx.shape[0]), idx.sum(0, dtype=np.int64)
+    if count == 0:
+        raise ValueError("surface_centroid: the volume holds no surface voxel")
+    return o + (total.astype(np.float64) / float(count)) * h32.astype(np.float64)
+
+
+def hypotheses(rotations, src_centroid, dst_centroid, offsets=None):
+    """Rigid hypotheses [R | t] -> float64 [K,3,4]: every rotation of ``rotations``
+    [n,3,3] with the translation that moves ``src_centroid`` onto
+    ``dst_centroid`` + offset, t = dst_centroid + offset - R . src_centroid.
+    ``offsets`` [M,3] (None: the one offset 0) multiplies K by M, for point sets
+    that overlap the target only partly; hypothesis r * M + m is rotation r with
+    offset m."""
+    R = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
+    off = np.zeros((1, 3)) if offsets is None else np.asarray(offsets, np.float64).reshape(-1, 3)
+    src = np.asarray(src_centroid, np.float64).reshape(3)
+    dst = np.asarray(dst_centroid, np.float64).reshape(3)
+    out = np.empty((R.shape[0], off.shape[0], 3, 4), np.float64)
+    out[..., :3] = R[:, None]
+    out[..., 3] = (dst + off)[None, :, :] - (R @ src)[:, None, :]
+    return out.reshape(-1, 3, 4)
+
+
+def rank_scores(scores):
+    """The order of ``ops.register.tsdf_scores``' rows [K,4], best first: inliers -
+    free descending, then sum e^2 ascending, then the index -> int64 [K]."""
+    s = np.asarray(scores, np.int64).reshape(-1, 4)
+    return np.lexsort((np.arange(s.shape[0]), s[:, 3], -(s[:, 0] - s[:, 1]))).astype(np.int64)
+
+
+def transform_distance(a, b, at):
+    """(radians, units) between two rigid transforms: the angle of the relative
+    rotation and how far apart they put the point ``at``"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    at = np.asarray(at, np.float64).reshape(3)
+    return rotation_angle(a[:3, :3] @ b[:3, :3].T), \
+        float(np.linalg.norm((a[:3, :3] @ at + a[:3, 3]) - (b[:3, :3] @ at + b[:3, 3])))
+
+
+def is_ambiguous(candidates, src_centroid, n_points: int, trunc: float,
+                 ambiguity_share: float = 0.02, min_angle: float = 0.1):
+    """``candidates`` (dicts with ``transform`` and ``score``, best first): does one
+    farther than (``min_angle`` rad or ``trunc`` units at the source's centroid)
+    from the first have a key inliers - free within ``ambiguity_share`` of the
+    points of the first's?"""
+    if not candidates:
+        return False
+    key = lambda c: int(c["score"][0]) - int(c["score"][1])
+    best = candidates[0]
+    for c in candidates[1:]:
+        rot, trans = transform_distance(c["transform"], best["transform"], src_centroid)
+        if (rot > min_angle or trans > trunc) and \
+                key(best) - key(c) <= ambiguity_share * n_points:
+            return True
+    return False
+
+
+def _float_rows(T):
+    return np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1, T.shape[-2], 4)[:, :3]
+                                .astype(np.float32))
+
+
+def global_register_points_tsdf(points, volume, trunc: float, coarse=None, coarse_trunc=None,
+                                n_rotations: int = 4096, offsets=None, keep: int = 16,
+                                max_tsdf: float = 0.75, coarse_iterations: int = 10,
+                                fine_iterations: int = 15, min_weight: float = 1.0,
+                                ambiguity_share: float = 0.02, rotations=None, device="cuda"):
+    """Align ``points`` [N,3] to the surface a TSDF ``volume`` holds from an unknown
+    pose: a search over rotations, not a refinement -> ``register_points_tsdf``'s
+    dict of the winner plus ``score`` (its four integers of
+    ``ops.register.tsdf_scores`` on ``volume``), ``n_hypotheses``, ``candidates``
+    (the refined hypotheses, best first: dicts with ``index``, ``transform``,
+    ``score``, ``coarse_score``) and ``ambiguous``.
+
+    1. ``hypotheses`` of ``rotation_set(n_rotations)`` (or ``rotations`` [n,3,3]),
+       the centroid of the finite points and ``surface_centroid`` of the coarse
+       volume, times ``offsets``, are scored in one ``tsdf_scores`` call on
+       ``coarse`` (a volume of the same surface with a wider band,
+       ``coarse_trunc``; None: ``volume`` itself) with the gate ``max_tsdf``.
+    2. They are ordered by ``rank_scores``: inliers - free, then sum e^2.  A point
+       that lands where the volume saw empty space counts against a hypothesis:
+       that is what tells a room's symmetric poses apart.
+    3. The first ``keep`` are refined by ``register_points_tsdf``:
+       ``coarse_iterations`` on the coarse volume, then ``fine_iterations`` on
+       ``volume``.
+    4. The refined transforms are scored on ``volume`` in one call and ordered
+       the same way; the first wins.
+
+    ``ambiguous`` (``is_ambiguous``): a candidate elsewhere -- more than 0.1 rad
+    or ``trunc`` away -- scores within ``ambiguity_share`` of the points of the
+    winner: a symmetric target, and the winner is one of several answers.  The
+    set's covering angle must lie inside the coarse loop's basin; the figures for
+    4 096 rotations are in docs/DESIGN_NOTEBOOK.md, section GR."""
+    import torch
+
+    from .. import ops
+    pts = _on_device(points, torch.float32, 3, device)
+    if coarse is None:
+        coarse, coarse_trunc = volume, trunc
+    elif coarse_trunc is None:
+        raise ValueError("a coarse volume needs its coarse_trunc")
+    host = pts.cpu().numpy().astype(np.float64)
+    host = host[np.isfinite(host).all(1)]
+    if host.shape[0] == 0:
+        raise ValueError("global_register_points_tsdf: no finite point")
+    src_c = host.mean(0)
+    R = rotation_set(n_rotations) if rotations is None else rotations
+    H = hypotheses(R, src_c, surface_centroid(coarse, coarse_trunc, min_weight), offsets)
+    to_dev = lambda a: torch.from_numpy(a).to(pts.device)
+    first = ops.register.tsdf_scores(coarse, pts, to_dev(_float_rows(H)), min_weight,
+                                     max_tsdf).cpu().numpy()
+    refined = []
+    for k in rank_scores(first)[:int(keep)]:
+        out = register_points_tsdf(pts, coarse, coarse_trunc, init=H[k],
+                                   iterations=coarse_iterations, min_weight=min_weight,
+                                   device=pts.device)
+        out = register_points_tsdf(pts, volume, trunc, init=out["transform"],
+                                   iterations=fine_iterations, min_weight=min_weight,
+                                   device=pts.device)
+        refined.append((int(k), out))
+    last = ops.register.tsdf_scores(
+        volume, pts, to_dev(_float_rows(np.stack([o["transform"] for _, o in refined]))),
+        min_weight, max_tsdf).cpu().numpy()
+    order = rank_scores(last)
+    candidates = [{"index": refined[j][0], "transform": refined[j][1]["transform"],
+                   "score": tuple(int(v) for v in last[j]),
+                   "coarse_score": tuple(int(v) for v in first[refined[j][0]])} for j in order]
+    result = dict(refined[int(order[0])][1])
+    result.update(score=candidates[0]["score"], n_hypotheses=int(H.shape[0]),
+                  candidates=candidates,
+                  ambiguous=is_ambiguous(candidates, src_c, int(pts.shape[0]), float(trunc),
+                                         ambiguity_share))
+    return result
+
+
+def global_register_meshes(src_mesh, dst_mesh, voxel: float, trunc=None, coarse_factor: float = 3,
+                           samples: int = 2048, seed: int = 0, device="cuda", **kw):
+    """Align the mesh ``src_mesh`` to ``dst_mesh`` (``load_mesh``'s dicts) from an
+    unknown pose -> ``global_register_points_tsdf``'s dict; ``transform`` moves
+    the source's vertices into the target's frame.  The fine volume is
+    ``utils.tsdf_fusion.volume_from_mesh`` of the target at ``voxel`` and
+    ``trunc`` (default 4 voxels), the coarse one the same at ``coarse_factor``
+    times both.  The source points are about ``samples`` area-uniform samples
+    (``ops.sample_mesh_surface`` with ``seed``), or with ``samples`` None the
+    source's vertices.  A volume made from a mesh is observed only within its
+    band, so no point counts as free there and hypotheses rank by inliers."""
+    import torch
+
+    from .. import ops
+    from .tsdf_fusion import volume_from_mesh
+    sv, sf = _mesh_arrays(src_mesh)
+    dv, df = _mesh_arrays(dst_mesh)
+    voxel = float(voxel)
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    dv_t, df_t = torch.as_tensor(dv).to(device), torch.as_tensor(df).to(device)
+    fine = volume_from_mesh(dv_t, df_t, voxel, trunc)
+    coarse = volume_from_mesh(dv_t, df_t, coarse_factor * voxel, coarse_factor * trunc)
+    if samples is None:
+        pts = torch.as_tensor(sv).to(device)
+    else:
+        sv_t, sf_t = torch.as_tensor(sv).to(device), torch.as_tensor(sf).to(device)
+        ok = ((sf >= 0) & (sf < sv.shape[0])).all(1)
+        tri = sv.astype(np.float64)[sf[ok]]
+        area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
+        area = float(area[np.isfinite(area)].sum())
+        if not area > 0.0:
+            raise ValueError("global_register_meshes: the source mesh has no area")
+        pts = ops.sample_mesh_surface(sv_t, sf_t, float(samples) / area, seed=int(seed))["points"]
+    return global_register_points_tsdf(pts, fine, trunc, coarse=coarse,
+                                       coarse_trunc=coarse_factor * trunc, device=device, **kw)
