@@ -2557,6 +2557,53 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
                            uint64_t workspace_doubles, double* sums, float* value,
                            uint8_t* matched, void* stream);
 
+/* ---- the same step for K transforms in one call (not in the reference) ----
+ * The lock-step half of a global registration (utils/registration.py:
+ * register_points_tsdf_batch): the normal equations of K rigid hypotheses of the
+ * same n points against the same volume from one launch, so that K loops advance
+ * together, one launch and one read per iteration.
+ * tests/test_gpu_lockstep.py checks every row against tests/tsdf_register_numpy.py
+ * and against ucsa_tsdf_icp_sums as int64 words.
+ *
+ * tsdf, weight, nx, ny, nz, origin3, spacing3, points, n, trunc, min_weight,
+ * max_tsdf: as for ucsa_tsdf_icp_sums.  transforms [K][12] float32 (the rows of
+ * [R | t] of every hypothesis) is on the device, like points.  sums [K][29]
+ * float64 on the device is written here.
+ * For every k < K, sums[k][0..28] are the 29 numbers ucsa_tsdf_icp_sums writes
+ * to its sums for transform k, all other arguments equal: steps 1 to 8 of its
+ * contract per point, the same float32 expressions in the same order, the same
+ * float64 terms and the same tree (rows padded with +0.0 to a multiple of 256,
+ * eight levels of adjacent pairs per group, repeated on the group results).
+ * The bytes are equal, not close.  A row depends on its own transform alone,
+ * not on K, on its position in the batch or on its neighbours.  There is no
+ * value and no matched output (step 9): they would be K x n.
+ * One lane per point in work-groups of 256, UCSA_TSDF_ICP_BATCH_TILE transforms
+ * per work-group along the grid's x axis (k_tsdf_icp_sums_batch); each
+ * (work-group, transform) writes its own 29 doubles, then k_icp_reduce_batch
+ * while more than one row per transform is left.  Every lane reaches the one
+ * barrier; no atomics; the same bytes every run.  The inputs are never modified.
+ * workspace: the stages' rows, K times those of ucsa_tsdf_icp_sums:
+ * workspace_doubles >= K * rows(n) * 29 with rows(n) the sum of the counts
+ * c_0 = ceil(n / 256), c_{j+1} = ceil(c_j / 256) that are greater than 1
+ * (0 for n <= 256: workspace may then be NULL).
+ * Limits: tsdf, weight not NULL (0, 1); nx, ny, nz >= 2 and nx*ny*nz <= 2^31-1
+ * (2, 3, 4); origin finite (5); spacing finite and > 0 (6); n <= 2^23 (8),
+ * points not NULL unless n == 0 (7); K <= UCSA_TSDF_ICP_BATCH_MAX (10): with
+ * n <= 2^23 that is at most 2^7 tiles by 2^15 work-groups, one launch, which is
+ * never split; transforms not NULL unless K == 0 (9); trunc > 0 and finite
+ * (11); min_weight > 0 (12); 0 < max_tsdf <= 1 (13); the workspace (14, 15);
+ * sums not NULL unless K == 0 (16).  An argument error returns UCSA_ERR_ARG -
+ * index before any launch and nothing is written.  K == 0: nothing is done;
+ * n == 0: all K rows are 29 times +0.0. */
+#define UCSA_TSDF_ICP_BATCH_TILE 8
+#define UCSA_TSDF_ICP_BATCH_MAX 1024
+int32_t ucsa_tsdf_icp_sums_batch(const float* tsdf, const float* weight, uint32_t nx, uint32_t ny,
+                                 uint32_t nz, const float* origin3, const float* spacing3,
+                                 const float* points, uint32_t n, const float* transforms,
+                                 uint32_t K, float trunc, float min_weight, float max_tsdf,
+                                 double* workspace, uint64_t workspace_doubles, double* sums,
+                                 void* stream);
+
 /* ---- scores of many rigid hypotheses against a TSDF volume (not in the reference) ----
  * The evaluation half of a global registration (utils/registration.py:
  * global_register_points_tsdf): K rigid transforms, each applied to the same n

@@ -13,7 +13,7 @@ and the geometry as accuracy, completeness, chamfer and F-score.
         [--register [--register_max_dist M] [--register_iters N] \\
          [--register_mode {plane,point}] [--register_samples N]] \\
         [--register_global [--register_global_rotations N] [--register_global_keep M] \\
-         [--register_global_voxel V]]
+         [--register_global_voxel V] [--register_global_lockstep]]
 
 Both meshes must end in one frame.  ``--pred_pose_frame`` / ``--gt_pose_frame``
 read a mesh in the frame of the JSON poses in metres (what the export and fusion
@@ -76,7 +76,9 @@ did not constrain the motion) and ``iterations``.
 (default 4 096) of the predicted surface against a TSDF volume made from the
 ground truth at ``--register_global_voxel`` (default: the ground truth's largest
 extent / 64), the best ``--register_global_keep`` (default 16) refined
-(``utils.registration.global_register_meshes``).  It runs before ``--register``
+(``utils.registration.global_register_meshes``); with
+``--register_global_lockstep`` they are refined together, one launch per
+iteration for all of them, to the same result bit for bit.  It runs before ``--register``
 when both are given; the predicted vertices are moved by the result, and one
 ``register_global: {...}`` line carries the 4 x 4 ``transform``, the ``score``
 (inliers, points in free space, sum e, sum e^2), ``n_hypotheses``, ``rmse``,
@@ -146,6 +148,9 @@ def parse_args(argv=None):
     p.add_argument("--register_global_voxel", type=float, default=None,
                    help="the voxel of the ground-truth volume, scene units "
                         "(default: its largest extent / 64)")
+    p.add_argument("--register_global_lockstep", action="store_true",
+                   help="refine the kept hypotheses in lock step: the same result, one launch "
+                        "per iteration for all of them")
     return p.parse_args(argv)
 
 
@@ -194,7 +199,7 @@ def register_global(a, pred, gv, gt_faces):
         raise SystemExit("--register_global_voxel must be > 0")
     out = global_register_meshes(pred, {"verts": gv, "faces": gt_faces}, voxel,
                                  seed=a.sample_seed, n_rotations=a.register_global_rotations,
-                                 keep=a.register_global_keep)
+                                 keep=a.register_global_keep, lockstep=a.register_global_lockstep)
     T = out["transform"]
     pred["verts"] = (pred["verts"].astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
     return {"transform": [[float(x) for x in row] for row in T], "score": list(out["score"]),

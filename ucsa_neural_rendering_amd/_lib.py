@@ -405,6 +405,10 @@ SIGNATURES = {
     "ucsa_tsdf_icp_sums": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f), C.POINTER(_f), _p,
                                        _u32, C.POINTER(_f), _f, _f, _f, _p, C.c_uint64, _p, _p,
                                        _p, _p]),
+    # ---- the same step for K transforms on the device in one call: [K][29] sums ----
+    "ucsa_tsdf_icp_sums_batch": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                             C.POINTER(_f), _p, _u32, _p, _u32, _f, _f, _f, _p,
+                                             C.c_uint64, _p, _p]),
     # ---- scores of K rigid hypotheses against a TSDF volume (four exact integers each) ----
     "ucsa_tsdf_score_transforms": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
                                                C.POINTER(_f), _p, _u32, _p, _u32, _f, _f, _p, _p]),

@@ -4,7 +4,9 @@
 // it byte for byte.  The same step against a TSDF volume, ucsa_tsdf_icp_sums
 // (k_tsdf_icp_sums, further down), shares the reduction and the reduce kernel,
 // and so does the step against a pair of vertex and normal maps by projection,
-// ucsa_projective_icp_sums (k_projective_icp_sums, after it).
+// ucsa_projective_icp_sums (k_projective_icp_sums, after it).  The TSDF step for
+// K transforms in one launch, ucsa_tsdf_icp_sums_batch (k_tsdf_icp_sums_batch,
+// k_icp_reduce_batch), sits between the two and forms the same tree per row.
 //
 // k_icp_sums<MODE>  a lane per point in work-groups of 256: the point is moved by
 //                   [R | t], the nearest-triangle search of triangle_grid.hip
@@ -309,6 +311,158 @@ __global__ void __launch_bounds__(PG_THREADS) k_tsdf_icp_sums(const float* __res
   icp_finish(sh, out);
 }
 
+// ---- the same step for K transforms in one launch: ucsa_tsdf_icp_sums_batch ----
+// k_tsdf_icp_sums_batch  shaped like k_tsdf_score (tsdf_score.hip): a lane per
+//                  point in work-groups of 256 points (blockIdx.y), a tile of
+//                  TB_TILE transforms per work-group (blockIdx.x).  The point is
+//                  loaded once.  The loop over the tile is uniform, and so is the
+//                  address of a transform's twelve floats: they arrive as scalar
+//                  loads.  Per transform the body is k_tsdf_icp_sums' (restated
+//                  here: that kernel is not touched): the move, the cell, the
+//                  sixteen floats gathered before their first use (as eight
+//                  8-byte loads, the corners k = 0, 1 being neighbours in memory,
+//                  as in k_tsdf_score), F, the gradient, the row, and the 29
+//                  terms through icp_put into the transform's own [29][4] of
+//                  LDS.  Behind the one barrier a lane per (transform, sum) adds
+//                  the four waves as (w0 + w1) + (w2 + w3) and writes the sum to
+//                  row (transform, work-group) of the stage's output.
+// k_icp_reduce_batch  k_icp_reduce with the transform on blockIdx.y; k_icp_reduce
+//                  itself is as it was.
+//
+// A stage's output is [K][count][29], count its work-groups along the points; the
+// stages follow one another in the workspace as in ucsa_tsdf_icp_sums, each K
+// times as large, and the last (count == 1) is `sums` [K][29].
+//
+// No atomics: the same operands meet in the same tree as in the single call, so a
+// row holds the same bits.  The barrier is reached by every lane: the loop's trip
+// count comes from blockIdx.x and K alone, a lane with i >= n holds a NaN point
+// (outside every lattice) and nothing returns early.
+//
+// Why every index is in range: as in k_tsdf_icp_sums, no float is converted to
+// an integer and no index is formed before `inside` holds, that is
+// 0 <= g_a <= n_a - 1 on every axis (a NaN fails both comparisons).  Then
+// fl_a = min(floor(g_a), n_a - 2) is an integer in [0, n_a - 2] (the host checks
+// n_a >= 2), the cell's far corner is a lattice point and its linear index is at
+// most nx*ny*nz - 1 <= 2^31 - 2, so the uint32 products do not wrap; an 8-byte
+// load at a corner with k = 0 ends with the corner at k = 1, inside the array.
+// A transform's index first + t is below K by the loop's bound (the host sizes
+// the grid so that first < K); a point's index is below n before it is read; a
+// row (k, group) with k < K and group < count is below K * count, which the host
+// checks against the workspace.
+constexpr uint32_t TB_TILE = UCSA_TSDF_ICP_BATCH_TILE;  // transforms per work-group
+
+__global__ void __launch_bounds__(PG_THREADS) k_tsdf_icp_sums_batch(
+    const float* __restrict__ tsdf, const float* __restrict__ weight, TsdfLattice L,
+    const float* __restrict__ points, uint32_t n, const float* __restrict__ transforms, uint32_t K,
+    float trunc, float min_weight, float max_tsdf, double* __restrict__ out) {
+  __shared__ double sh[TB_TILE * ICP_SUMS * 4u];            // [transform][sum][wave]
+  const uint32_t i = blockIdx.y * PG_THREADS + threadIdx.x;  // < 2^23 + 256
+  float x = NAN, y = NAN, z = NAN;  // no point: outside every lattice
+  if (i < n) {
+    x = points[3ull * i];
+    y = points[3ull * i + 1u];
+    z = points[3ull * i + 2u];
+  }
+  const uint32_t first = blockIdx.x * TB_TILE;  // < K: the host sizes the grid
+  const uint32_t count = K - first < TB_TILE ? K - first : TB_TILE;
+  const uint32_t sj = L.n[2], si = L.n[1] * L.n[2];
+#pragma unroll 1
+  for (uint32_t t = 0; t < count; ++t) {
+    const float* __restrict__ T = transforms + 12ull * (first + t);  // uniform: scalar loads
+    float q[3];
+    q[0] = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+    q[1] = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+    q[2] = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    float g[3];
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      g[a] = (q[a] - L.o[a]) / L.h[a];
+      inside = inside && g[a] >= 0.0f && g[a] <= (float)(L.n[a] - 1u);
+    }
+    float f[3] = {0.0f, 0.0f, 0.0f};
+    float w[8], v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) w[c] = v[c] = 0.0f;
+    if (inside) {
+      uint32_t c[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const float fl = fminf(floorf(g[a]), (float)(L.n[a] - 2u));
+        c[a] = (uint32_t)fl;
+        f[a] = g[a] - fl;
+      }
+      const uint32_t base = (c[0] * L.n[1] + c[1]) * L.n[2] + c[2];
+      // v[4i + 2j + k]: both arrays, all eight 8-byte loads before the first use
+#pragma unroll
+      for (uint32_t c4 = 0; c4 < 4u; ++c4) {
+        const uint32_t at = base + ((c4 & 2u) ? si : 0u) + ((c4 & 1u) ? sj : 0u);
+        float2 pw, pv;
+        __builtin_memcpy(&pw, weight + at, sizeof(float2));
+        __builtin_memcpy(&pv, tsdf + at, sizeof(float2));
+        w[2u * c4] = pw.x, w[2u * c4 + 1u] = pw.y;
+        v[2u * c4] = pv.x, v[2u * c4 + 1u] = pv.y;
+      }
+    }
+    bool observed = inside;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) observed = observed && w[c] >= min_weight;
+    const float c00 = ti_lerp(v[0], v[1], f[2]), c01 = ti_lerp(v[2], v[3], f[2]);
+    const float c10 = ti_lerp(v[4], v[5], f[2]), c11 = ti_lerp(v[6], v[7], f[2]);
+    const float c_0 = ti_lerp(c00, c01, f[1]), c_1 = ti_lerp(c10, c11, f[1]);
+    const float F = ti_lerp(c_0, c_1, f[0]);
+    float G[3];
+    G[0] = c_1 - c_0;
+    G[1] = ti_lerp(c01 - c00, c11 - c10, f[0]);
+    G[2] = ti_lerp(ti_lerp(v[1] - v[0], v[3] - v[2], f[1]), ti_lerp(v[5] - v[4], v[7] - v[6], f[1]),
+                   f[0]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) G[a] = G[a] / L.h[a];
+    const float ln = sqrtf((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+    const bool matched = observed && ln > 0.0f && isfinite(ln) && fabsf(F) <= max_tsdf;
+    float V[8][1];  // J (0..5), r (6) and 1 (7); unused bits of an unmatched row are selected away
+    icp_row<1>(q[0], q[1], q[2], 0.0f, 0.0f, 0.0f, G[0] / ln, G[1] / ln, G[2] / ln, V, 0);
+    V[6][0] = -(F * trunc);
+    double* row = sh + t * (ICP_SUMS * 4u);
+    uint32_t col = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int b = a; b < 6; ++b) icp_put(icp_term<1>(matched, V[a], V[b]), col++, row);
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) icp_put(icp_term<1>(matched, V[a], V[6]), col++, row);
+    icp_put(icp_term<1>(matched, V[6], V[6]), col++, row);
+    icp_put(icp_term<1>(matched, V[7], V[7]), col++, row);
+  }
+  __syncthreads();
+  const uint32_t c = threadIdx.x;  // (transform c / 29, sum c % 29)
+  if (c < count * ICP_SUMS) {
+    const uint32_t t = c / ICP_SUMS, s = c - t * ICP_SUMS;
+    const double* p = sh + 4u * c;
+    out[((uint64_t)(first + t) * gridDim.y + blockIdx.y) * ICP_SUMS + s] =
+        (p[0] + p[1]) + (p[2] + p[3]);
+  }
+}
+
+// stage `in` [K][count][29] -> `out` [K][gridDim.x][29]; blockIdx.y is the transform
+__global__ void __launch_bounds__(PG_THREADS) k_icp_reduce_batch(const double* __restrict__ in,
+                                                                 uint32_t count,
+                                                                 double* __restrict__ out) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  const uint32_t row = blockIdx.x * PG_THREADS + threadIdx.x;
+  const bool live = row < count;
+  const double* mine = in + (uint64_t)blockIdx.y * count * ICP_SUMS;
+#pragma unroll 1
+  for (uint32_t c = 0; c < ICP_SUMS; ++c)
+    icp_put(live ? mine[(uint64_t)row * ICP_SUMS + c] : 0.0, c, sh);
+  __syncthreads();
+  const uint32_t c = threadIdx.x;
+  if (c < ICP_SUMS)
+    out[((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * ICP_SUMS + c] =
+        (sh[4u * c] + sh[4u * c + 1u]) + (sh[4u * c + 2u] + sh[4u * c + 3u]);
+}
+
 // ---- one step of projective ICP against a pair of maps: ucsa_projective_icp_sums ----
 // k_projective_icp_sums  a lane per point in work-groups of 256: the point (and
 //                  its normal) is moved by [R | t], projected into the target
@@ -496,6 +650,54 @@ extern "C" int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, ui
     const double* in = out;
     out = next == 1u ? sums : out + (uint64_t)count * ICP_SUMS;
     hipLaunchKernelGGL(k_icp_reduce, dim3(next), dim3(PG_THREADS), 0, s, in, count, out);
+    count = next;
+  }
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_tsdf_icp_sums_batch(const float* tsdf, const float* weight, uint32_t nx,
+                                            uint32_t ny, uint32_t nz, const float* origin3,
+                                            const float* spacing3, const float* points, uint32_t n,
+                                            const float* transforms, uint32_t K, float trunc,
+                                            float min_weight, float max_tsdf, double* workspace,
+                                            uint64_t workspace_doubles, double* sums,
+                                            void* stream) {
+  UCSA_CHECK_ARG(tsdf, 0);
+  UCSA_CHECK_ARG(weight, 1);
+  UCSA_CHECK_ARG(nx >= 2 && ny >= 1 && nz >= 1 && (uint64_t)nx * ny * nz <= 0x7FFFFFFFull, 2);
+  UCSA_CHECK_ARG(ny >= 2, 3);
+  UCSA_CHECK_ARG(nz >= 2, 4);
+  UCSA_CHECK_ARG(origin3 && pg_host_finite(origin3[0]) && pg_host_finite(origin3[1]) &&
+                     pg_host_finite(origin3[2]), 5);
+  UCSA_CHECK_ARG(spacing3, 6);
+  for (int a = 0; a < 3; ++a) UCSA_CHECK_ARG(spacing3[a] > 0.0f && pg_host_finite(spacing3[a]), 6);
+  UCSA_CHECK_ARG(n <= (1u << 23), 8);
+  UCSA_CHECK_ARG(n == 0 || points, 7);
+  UCSA_CHECK_ARG(K <= UCSA_TSDF_ICP_BATCH_MAX, 10);
+  UCSA_CHECK_ARG(K == 0 || transforms, 9);
+  UCSA_CHECK_ARG(trunc > 0.0f && pg_host_finite(trunc), 11);
+  UCSA_CHECK_ARG(min_weight > 0.0f, 12);
+  UCSA_CHECK_ARG(max_tsdf > 0.0f && max_tsdf <= 1.0f, 13);
+  const uint64_t ws_rows = (uint64_t)K * icp_workspace_rows(n);  // <= 2^10 * (2^15 + 2^7)
+  UCSA_CHECK_ARG(ws_rows == 0 || workspace, 14);
+  UCSA_CHECK_ARG(workspace_doubles >= ws_rows * ICP_SUMS, 15);
+  UCSA_CHECK_ARG(K == 0 || sums, 16);
+  if (K == 0) return 0;
+  TsdfLattice L;
+  L.n[0] = nx, L.n[1] = ny, L.n[2] = nz;
+  for (int a = 0; a < 3; ++a) L.o[a] = origin3[a], L.h[a] = spacing3[a];
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t count = n ? ucsa_div_up(n, PG_THREADS) : 1u;  // <= 2^15; n == 0 gives +0.0
+  const uint32_t tiles = ucsa_div_up(K, TB_TILE);        // <= 2^7: one launch, at most 2^22 groups
+  double* out = count == 1u ? sums : workspace;
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_tsdf_icp_sums_batch, dim3(tiles, count), dim3(PG_THREADS), 0, s, tsdf,
+                     weight, L, points, n, transforms, K, trunc, min_weight, max_tsdf, out);
+  while (count > 1u) {  // at most two passes for n <= 2^23
+    const uint32_t next = ucsa_div_up(count, PG_THREADS);
+    const double* in = out;
+    out = next == 1u ? sums : out + (uint64_t)K * count * ICP_SUMS;
+    hipLaunchKernelGGL(k_icp_reduce_batch, dim3(next, K), dim3(PG_THREADS), 0, s, in, count, out);
     count = next;
   }
   return ucsa_launch_status();

@@ -3,7 +3,8 @@ grid of ``ops.triangle_grid``.  Reached as ``ops.register.icp_sums``.  The same
 step against a TSDF volume, without a mesh: ``ops.register.tsdf_sums``; and
 against a pair of vertex and normal maps, by projection:
 ``ops.register.projective_sums``.  Many rigid hypotheses scored against a TSDF
-volume in one call, for a global search: ``ops.register.tsdf_scores``."""
+volume in one call, for a global search: ``ops.register.tsdf_scores``; the TSDF
+step for K hypotheses in one call: ``ops.register.tsdf_sums_batch``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,6 +21,8 @@ MODES = {"plane": 0, "point": 1}
 _EDGE, _GRAZING = 4, 8  # ops.depth's mask bits (UCSA_DEPTH_EDGE, UCSA_DEPTH_GRAZING)
 TSDF_SCORE_TILE = 16    # transforms per work-group of k_tsdf_score (UCSA_TSDF_SCORE_TILE)
 TSDF_SCORE_MAX_POINTS = 1 << 23
+TSDF_SUMS_BATCH_TILE = 8     # transforms per work-group of k_tsdf_icp_sums_batch
+TSDF_SUMS_BATCH_MAX = 1024   # transforms per call (UCSA_TSDF_ICP_BATCH_MAX)
 
 
 def workspace_rows(n: int) -> int:
@@ -181,6 +184,52 @@ def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
         _ptr(pts) if n else None, n, t12, trunc, min_weight, max_tsdf, _ptr(ws), ws_doubles,
         _ptr(sums), _ptr(value), _ptr(matched), _stream()), "ucsa_tsdf_icp_sums")
     return (sums, value, matched) if return_matches else sums
+
+
+def tsdf_sums_batch(volume, points, transforms, trunc: float, min_weight: float = 1.0,
+                    max_tsdf: float = 1.0):
+    """``tsdf_sums`` for K rigid hypotheses of the same ``points`` [N,3] (float32
+    on the GPU) against the same TSDF ``volume`` in one call -> float64 [K,29] on
+    the device.  ``transforms`` is float32 [K,3,4] or [K,4,4] on the volume's
+    device, as for ``tsdf_scores`` (the first three rows are taken: q = R p + t).
+    Row k holds, as int64 words, what ``tsdf_sums(volume, points, transforms[k],
+    trunc, min_weight, max_tsdf)`` returns: the same float32 expressions and the
+    same tree per row, whatever K and wherever the row stands in the batch.
+    There are no per-point outputs.  At most 2^23 points and
+    ``TSDF_SUMS_BATCH_MAX`` transforms; K = 0 gives an empty result.
+    ``utils.registration.register_points_tsdf_batch`` iterates K loops in lock
+    step on it.  Contract of ucsa_tsdf_icp_sums_batch (include/ucsa_hip.h)."""
+    (nx, ny, nz), dev = volume_lattice(volume)
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
+                             f"{(nx, ny, nz)}")
+    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
+    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
+    n = int(pts.shape[0])
+    if n > TSDF_SCORE_MAX_POINTS:
+        raise _lib.UcsaError("points must have at most 2^23 rows")
+    T = _gpu(transforms, "transforms", torch.float32, (None, None, 4), device=dev)
+    if T.shape[1] not in (3, 4):
+        raise _lib.UcsaError(f"transforms must be [K,3,4] or [K,4,4], got {tuple(T.shape)}")
+    T = T[:, :3].contiguous()
+    K = int(T.shape[0])
+    if K > TSDF_SUMS_BATCH_MAX:
+        raise _lib.UcsaError(f"transforms must have at most {TSDF_SUMS_BATCH_MAX} rows, got {K}")
+    trunc = _positive(trunc, "trunc")
+    min_weight = float(min_weight)
+    if not min_weight > 0:
+        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
+    max_tsdf = float(max_tsdf)
+    if not 0 < max_tsdf <= 1:
+        raise _lib.UcsaError(f"max_tsdf must be in (0, 1], got {max_tsdf!r}")
+    ws_doubles = K * ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    sums = torch.empty((K, ICP_SUMS), dtype=torch.float64, device=dev)
+    check(lib().ucsa_tsdf_icp_sums_batch(
+        _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
+        _ptr(pts) if n else None, n, _ptr(T) if K else None, K, trunc, min_weight, max_tsdf,
+        _ptr(ws), ws_doubles, _ptr(sums) if K else None, _stream()), "ucsa_tsdf_icp_sums_batch")
+    return sums
 
 
 def tsdf_scores(volume, points, transforms, min_weight: float = 1.0, max_tsdf: float = 0.75):

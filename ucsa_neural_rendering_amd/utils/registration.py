@@ -32,7 +32,9 @@ gather in place of a search, with a distance and a normal-compatibility gate.
 
 ``global_register_points_tsdf`` / ``global_register_meshes`` find the coarse
 alignment those loops start from: hypotheses over a rotation set scored against
-a TSDF volume in one call (``ops.register.tsdf_scores``), the best refined.
+a TSDF volume in one call (``ops.register.tsdf_scores``), the best refined --
+one after another, or with ``lockstep`` all together
+(``register_points_tsdf_batch`` over ``ops.register.tsdf_sums_batch``).
 
 Not here: scale, rejection of matches on open boundaries, normal compatibility
 gates in the mesh and TSDF routes, robust kernels beyond the ``max_dist``
@@ -358,6 +360,102 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
     return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
             "iterations": done, "converged": converged, "history": history,
             "n_points": int(pts.shape[0])}
+
+
+def _float_rows(T):
+    """float64 [K,3,4] or [K,4,4] -> the float32 rows [K,3,4] a kernel reads: the
+    rounding of ``ops.register``'s ``_transform12``"""
+    T = np.asarray(T, np.float64)
+    return np.ascontiguousarray(T.reshape(-1, T.shape[-2], 4)[:, :3].astype(np.float32))
+
+
+def lockstep_loop(sums_fn, inits, iterations: int = 30, max_tsdf: float = 1.0,
+                  max_tsdf_schedule=None, tol_rot: float = 1e-6, tol_trans: float = 1e-6,
+                  rcond: float = 1e-8, n_points: int = 0):
+    """``register_points_tsdf``'s loop for K starts ``inits`` (4x4 or 3x4 each) in
+    lock step, over ``sums_fn(transforms, max_tsdf)``: float32 [A,3,4] (the still
+    active hypotheses' transforms, rounded as the single loop rounds them) and
+    the iteration's gate -> float64 [A,29], row a what ``tsdf_sums`` gives for
+    transform a -> a list of K dicts, each what the single loop returns for its
+    start.  Host arithmetic only: per row the same ``normal_equations``,
+    ``solve_step`` and ``compose`` calls as the single loop, one row after
+    another (a batched eigen-decomposition need not give the same bits), so
+    with a ``sums_fn`` whose rows are exact the results are equal bit for bit.
+    A hypothesis that meets its exit test leaves the active set; ``sums_fn`` is
+    called once per iteration while any is active."""
+    T = [compose(np.asarray(t, np.float64), np.zeros(6)) for t in inits]
+    K = len(T)
+    schedule = [float(max_tsdf)] if max_tsdf_schedule is None else \
+        [float(m) for m in max_tsdf_schedule]
+    history = [[] for _ in range(K)]
+    rank, converged, done = [0] * K, [False] * K, [0] * K
+    active = list(range(K))
+    for k in range(int(iterations)):
+        if not active:
+            break
+        mt = schedule[min(k, len(schedule) - 1)]
+        rows = np.asarray(sums_fn(_float_rows(np.stack([T[j] for j in active])), mt), np.float64)
+        if rows.shape != (len(active), SUMS):
+            raise ValueError(f"sums_fn must return [{len(active)},{SUMS}], got {rows.shape}")
+        still = []
+        for a, j in enumerate(active):
+            sums = rows[a].copy()
+            _, _, sse, count = normal_equations(sums)
+            xi, rank[j] = solve_step(sums, rcond)
+            T[j] = compose(T[j], xi)
+            done[j] = k + 1
+            om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
+            history[j].append({"matched": int(round(count)),
+                               "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
+                               "omega": om, "upsilon": up, "max_tsdf": mt, "sums": sums})
+            if count > 0 and om <= tol_rot and up <= tol_trans:
+                converged[j] = True
+            else:
+                still.append(j)
+        active = still
+    out = []
+    for j in range(K):
+        last = history[j][-1] if history[j] else {"matched": 0, "rmse": float("nan")}
+        out.append({"transform": T[j], "rmse": last["rmse"], "matched": last["matched"],
+                    "rank": rank[j], "iterations": done[j], "converged": converged[j],
+                    "history": history[j], "n_points": int(n_points)})
+    return out
+
+
+def register_points_tsdf_batch(points, volume, trunc: float, inits, iterations: int = 30,
+                               min_weight: float = 1.0, max_tsdf: float = 1.0,
+                               max_tsdf_schedule=None, tol_rot: float = 1e-6,
+                               tol_trans: float = 1e-6, rcond: float = 1e-8, device="cuda",
+                               sums_fn=None):
+    """``register_points_tsdf`` from K starts ``inits`` ([K,4,4] or a sequence of
+    4x4 / 3x4) in lock step -> a list of K dicts, entry k exactly -- keys, values
+    and bits: ``transform``, every ``history[i]["sums"]``, ``iterations``,
+    ``converged``, ``matched``, ``rank``, ``rmse`` -- what
+    ``register_points_tsdf(points, volume, trunc, init=inits[k], ...)`` returns.
+    Each iteration is one ``ops.register.tsdf_sums_batch`` call for all
+    hypotheses still active (their float64 transforms rounded to float32 and
+    uploaded in one copy), one read of [active, 29] doubles, and per row the
+    single loop's host step; a hypothesis that converges leaves the batch.  K
+    loops then cost max(iterations) launches and reads, not their sum.
+    ``max_tsdf_schedule`` is indexed by the iteration, which all active
+    hypotheses share.  At most ``ops.register.TSDF_SUMS_BATCH_MAX`` starts.
+    ``sums_fn`` replaces the device call (``lockstep_loop``'s argument; then
+    ``points`` and ``volume`` are only counted, and no GPU is needed)."""
+    if sums_fn is None:
+        import torch
+
+        from .. import ops
+        pts = _on_device(points, torch.float32, 3, device)
+        n = int(pts.shape[0])
+
+        def sums_fn(rows, mt):
+            T = torch.from_numpy(rows).to(pts.device)
+            return ops.register.tsdf_sums_batch(volume, pts, T, trunc, min_weight,
+                                                mt).cpu().numpy()
+    else:
+        n = int(np.asarray(points).reshape(-1, 3).shape[0])
+    return lockstep_loop(sums_fn, list(inits), iterations, max_tsdf, max_tsdf_schedule, tol_rot,
+                         tol_trans, rcond, n_points=n)
 
 
 def refine_pose_tsdf(depth, pose, intrinsics, volume, trunc: float, stride: int = 1,
@@ -692,16 +790,12 @@ def is_ambiguous(candidates, src_centroid, n_points: int, trunc: float,
     return False
 
 
-def _float_rows(T):
-    return np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1, T.shape[-2], 4)[:, :3]
-                                .astype(np.float32))
-
-
 def global_register_points_tsdf(points, volume, trunc: float, coarse=None, coarse_trunc=None,
                                 n_rotations: int = 4096, offsets=None, keep: int = 16,
                                 max_tsdf: float = 0.75, coarse_iterations: int = 10,
                                 fine_iterations: int = 15, min_weight: float = 1.0,
-                                ambiguity_share: float = 0.02, rotations=None, device="cuda"):
+                                ambiguity_share: float = 0.02, rotations=None, device="cuda",
+                                lockstep: bool = False):
     """Align ``points`` [N,3] to the surface a TSDF ``volume`` holds from an unknown
     pose: a search over rotations, not a refinement -> ``register_points_tsdf``'s
     dict of the winner plus ``score`` (its four integers of
@@ -719,7 +813,12 @@ def global_register_points_tsdf(points, volume, trunc: float, coarse=None, coars
        that is what tells a room's symmetric poses apart.
     3. The first ``keep`` are refined by ``register_points_tsdf``:
        ``coarse_iterations`` on the coarse volume, then ``fine_iterations`` on
-       ``volume``.
+       ``volume``.  With ``lockstep`` the two phases are each one
+       ``register_points_tsdf_batch`` over all kept hypotheses (at most
+       ``ops.register.TSDF_SUMS_BATCH_MAX`` of them): one launch and one read
+       per iteration instead of one per hypothesis and iteration.  The phases
+       are independent per hypothesis either way and the returned dict is
+       equal bit for bit.
     4. The refined transforms are scored on ``volume`` in one call and ordered
        the same way; the first wins.
 
@@ -747,14 +846,24 @@ def global_register_points_tsdf(points, volume, trunc: float, coarse=None, coars
     first = ops.register.tsdf_scores(coarse, pts, to_dev(_float_rows(H)), min_weight,
                                      max_tsdf).cpu().numpy()
     refined = []
-    for k in rank_scores(first)[:int(keep)]:
-        out = register_points_tsdf(pts, coarse, coarse_trunc, init=H[k],
-                                   iterations=coarse_iterations, min_weight=min_weight,
-                                   device=pts.device)
-        out = register_points_tsdf(pts, volume, trunc, init=out["transform"],
-                                   iterations=fine_iterations, min_weight=min_weight,
-                                   device=pts.device)
-        refined.append((int(k), out))
+    kept = rank_scores(first)[:int(keep)]
+    if lockstep:
+        outs = register_points_tsdf_batch(pts, coarse, coarse_trunc, [H[k] for k in kept],
+                                          iterations=coarse_iterations, min_weight=min_weight,
+                                          device=pts.device)
+        outs = register_points_tsdf_batch(pts, volume, trunc, [o["transform"] for o in outs],
+                                          iterations=fine_iterations, min_weight=min_weight,
+                                          device=pts.device)
+        refined = [(int(k), o) for k, o in zip(kept, outs)]
+    else:
+        for k in kept:
+            out = register_points_tsdf(pts, coarse, coarse_trunc, init=H[k],
+                                       iterations=coarse_iterations, min_weight=min_weight,
+                                       device=pts.device)
+            out = register_points_tsdf(pts, volume, trunc, init=out["transform"],
+                                       iterations=fine_iterations, min_weight=min_weight,
+                                       device=pts.device)
+            refined.append((int(k), out))
     last = ops.register.tsdf_scores(
         volume, pts, to_dev(_float_rows(np.stack([o["transform"] for _, o in refined]))),
         min_weight, max_tsdf).cpu().numpy()
