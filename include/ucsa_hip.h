@@ -2715,6 +2715,73 @@ int32_t ucsa_projective_icp_sums(const float* points, const float* normals, uint
                                  double* workspace, uint64_t workspace_doubles, double* sums,
                                  int32_t* pixel, float* residual, void* stream);
 
+/* ---- the two frame trackers' steps with a weight per row (not in the reference) ----
+ * Iteratively reweighted least squares for ucsa_projective_icp_sums and
+ * ucsa_tsdf_icp_sums: a robust kernel (Huber, Tukey) on the residual and an
+ * optional weight per source point (ucsa_depth_confidence's, for one), so that a
+ * pair that passes the gates but belongs to something the target does not show
+ * stops pulling on the pose.  The siblings are untouched; these are new entry
+ * points over new kernels.  tests/robust_numpy.py restates the contract; sums
+ * (as int64 words), the weights and the per-point outputs equal it bit for bit.
+ *
+ * Each takes its sibling's arguments, with the same meaning, and in addition
+ * point_weight [n] float32 on the device or NULL (every p = 1), robust_kind
+ * (UCSA_ROBUST_NONE / HUBER / TUKEY), robust_scale (a host float in the
+ * residual's units: Huber's k, Tukey's c; not read for NONE) and the optional
+ * output weight_out [n] float32 (NULL: not written).
+ * Per point i < n: the sibling's steps up to and including the gates and the
+ * row (J, r) -- steps 1 to 9 of ucsa_projective_icp_sums, 1 to 7 of
+ * ucsa_tsdf_icp_sums -- operand for operand.  Then, in float32, each operation
+ * rounded once, division and sqrt correctly rounded:
+ *   a   = fabsf(r).
+ *   rho = 1 for NONE;
+ *         Huber: 1 if a <= k, else k / a;
+ *         Tukey: t = a / c, u = 1 - t*t, rho = u*u if a < c, else 0.
+ *   p   = point_weight[i], or 1; a p that is not finite and > 0 gives w = 0: the
+ *         point takes no part (ucsa_tsdf_integrate_weighted's rule for a pixel).
+ *   w   = p * rho.
+ *   The row counts iff it matched and w > 0.
+ *   s   = sqrtf(w); J_k <- s*J_k for the six entries and r <- s*r.  The row's 1
+ *         stays 1.
+ * The 29 float64 terms of a row that counts are the siblings' products of the
+ * scaled floats (exact in float64), +0.0 by a select otherwise, and the tree is
+ * the siblings': sums[0..20] = sum w J^T J, sums[21..26] = sum w J^T r,
+ * sums[27] = sum w r^2, sums[28] = the rows that count.  With NONE and no
+ * point_weight s = 1, a product by 1 is exact, and the sums are the sibling's
+ * as int64 words.
+ * weight_out[i] = w for a row that counts, +0.0 otherwise.  The siblings'
+ * per-point outputs report the geometric match whatever the weight: pixel /
+ * residual (the unscaled r) and value / matched.
+ * One lane per point in work-groups of 256 (k_projective_icp_sums_weighted,
+ * k_tsdf_icp_sums_weighted), the weight loaded with the point, then k_icp_reduce
+ * while more than one row is left.  Every lane reaches the one barrier; no
+ * atomics; the same bytes every run.  The inputs are never modified.
+ * Limits: the siblings', at the siblings' indices up to min_cos (15) and
+ * max_tsdf (12); then robust_kind one of the three (17; 14), robust_scale
+ * finite and > 0 unless NONE (18; 15), the workspace (19, 20; 16, 17), sums
+ * (21; 18).  An argument error returns UCSA_ERR_ARG - index before any launch
+ * and nothing is written. */
+#define UCSA_ROBUST_NONE 0
+#define UCSA_ROBUST_HUBER 1
+#define UCSA_ROBUST_TUKEY 2
+int32_t ucsa_projective_icp_sums_weighted(const float* points, const float* normals, uint32_t n,
+                                          const float* target_points, const float* target_normals,
+                                          const uint8_t* target_mask, uint32_t H, uint32_t W,
+                                          uint32_t reject, float fx, float fy, float cx, float cy,
+                                          const float* transform, float max_dist, float min_cos,
+                                          const float* point_weight, int32_t robust_kind,
+                                          float robust_scale, double* workspace,
+                                          uint64_t workspace_doubles, double* sums, int32_t* pixel,
+                                          float* residual, float* weight_out, void* stream);
+int32_t ucsa_tsdf_icp_sums_weighted(const float* tsdf, const float* weight, uint32_t nx,
+                                    uint32_t ny, uint32_t nz, const float* origin3,
+                                    const float* spacing3, const float* points, uint32_t n,
+                                    const float* transform, float trunc, float min_weight,
+                                    float max_tsdf, const float* point_weight, int32_t robust_kind,
+                                    float robust_scale, double* workspace,
+                                    uint64_t workspace_doubles, double* sums, float* value,
+                                    uint8_t* matched, float* weight_out, void* stream);
+
 /* ---- The depth front end: bilateral filter, points, normals, edge rejection
  * (not in the reference) -----------------------------------------------------
  * What KinectFusion does to a depth frame before it integrates or tracks it

@@ -11,7 +11,8 @@ first stage of the mapping-based pseudo-label baseline.
         [--refine_poses [--refine_warmup K] [--refine_iters N] [--refine_stride S] \\
          [--refine_min_matched SHARE] [--refine_method {tsdf,projective}] \\
          [--poses_out FILE.npy]] [--odometry] [--depth_filter SPEC] \\
-        [--view_weights SPEC]
+        [--view_weights SPEC] \\
+        [--refine_robust {none,huber,tukey} --refine_robust_scale S[,S...]]
 
 Reads the frames of transforms_train.json (every ``--every``-th): the poses,
 ``depth/<stem>.png`` (uint16 millimetres, 0 = no measurement; scene units as
@@ -68,7 +69,17 @@ at w = 0.3 it holds 0.3 -- and ``--min_weight`` is in those units and may be a
 fraction: ``cos_floor`` times the range factor at the farthest depth (0.1 with
 the default filter, whose sigma_z2 is 0) keeps every voxel seen once, as 1 does
 without weights; k times the printed mean asks for about k average views.  The
-default stays 1.  Without the flag nothing changes.  Prints one JSON line last."""
+default stays 1.  Without the flag nothing changes.  ``--refine_robust huber`` or
+``tukey`` with ``--refine_robust_scale`` (metres; Huber's k or Tukey's c on the
+point-to-plane residual) down-weights the pairs of ``--refine_poses`` and
+``--odometry`` that pass the gates but do not fit -- something moved, or is in
+the frame and not in the model (``utils.registration``: iteratively reweighted
+least squares).  The scale is one number or a comma-separated list: per pyramid
+level, finest first, for the projective trackers (``--odometry`` has three
+levels, ``--refine_method projective`` one), per iteration with the last value
+held for ``--refine_method tsdf``.  The ``refine:`` / ``odometry:`` lines echo
+both.  For tracking from a pose already close: Tukey narrows the basin.  Without
+the flags nothing changes.  Prints one JSON line last."""
 import argparse
 import json
 import os
@@ -128,6 +139,11 @@ def parse_args(argv=None):
                    help="'default' or field=value,... of utils.depth_frontend.ViewWeights "
                         "(cos_floor, sigma_depth, sigma_z2; needs --depth_filter): weight "
                         "every pixel by range and viewing angle (default: off)")
+    p.add_argument("--refine_robust", choices=("none", "huber", "tukey"), default="none",
+                   help="robust kernel of --refine_poses / --odometry (default: none)")
+    p.add_argument("--refine_robust_scale", default=None, metavar="S[,S...]",
+                   help="its scale in metres: one value, or a list (per level, finest first, "
+                        "for the projective trackers; per iteration for the tsdf tracker)")
     return p.parse_args(argv)
 
 
@@ -152,8 +168,23 @@ def main(argv=None):
         raise SystemExit("--poses_out needs --refine_poses or --odometry")
     if a.refine_method == "projective" and a.refine_stride != 1:
         raise SystemExit("--refine_method projective takes no --refine_stride")
+    if (a.refine_robust != "none") != (a.refine_robust_scale is not None):
+        raise SystemExit("--refine_robust huber|tukey and --refine_robust_scale come as a pair")
+    if a.refine_robust != "none" and not (a.refine_poses or a.odometry):
+        raise SystemExit("--refine_robust needs --refine_poses or --odometry")
     fr = read_frames(a.scene_root)
     uom = fr["one_m_to_scene_uom"]
+    robust = {}
+    if a.refine_robust != "none":
+        try:
+            scales = [float(v) * uom for v in a.refine_robust_scale.split(",")]
+        except ValueError:
+            raise SystemExit("--refine_robust_scale takes S[,S...] in metres")
+        if not all(v > 0 and np.isfinite(v) for v in scales):
+            raise SystemExit("--refine_robust_scale must be > 0")
+        robust = {"robust": a.refine_robust,
+                  "robust_scale": scales[0] if len(scales) == 1 else scales}
+        echo = {"robust": a.refine_robust, "robust_scale": scales}
     keep = list(range(0, len(fr["stems"]), a.every))
     stems = [fr["stems"][i] for i in keep]
     poses = fr["poses"][keep]
@@ -173,7 +204,8 @@ def main(argv=None):
     if a.refine_poses:
         refine = {"refine_poses": True, "refine_warmup": a.refine_warmup,
                   "refine_min_matched": a.refine_min_matched,
-                  "refine_kw": {"iterations": a.refine_iters, "stride": a.refine_stride}}
+                  "refine_kw": {"iterations": a.refine_iters, "stride": a.refine_stride,
+                                **robust}}
         if a.refine_method != "tsdf":
             refine["refine_method"] = a.refine_method
             if a.depth_filter is None:   # the thresholds' defaults are metres
@@ -188,7 +220,7 @@ def main(argv=None):
         from ucsa_neural_rendering_amd.utils.registration import odometry
         odo = odometry((depth(i) for i in range(len(stems))), fr["intrinsics"],
                        depth_filter=refine.get("depth_filter", DepthFilter().scaled(uom)),
-                       filtered=a.depth_filter is not None)
+                       filtered=a.depth_filter is not None, **robust)
         first = np.asarray(poses[0], np.float64)
         poses = np.stack([first @ p for p in odo["poses"]])
         recs = [r for r in odo["records"] if r is not None]
@@ -196,6 +228,8 @@ def main(argv=None):
         walked = {"frames": len(stems), "fallbacks": odo["fallbacks"],
                   "matched_median": med([r["matched"] for r in recs]),
                   "rmse_median": med([r["rmse"] for r in recs if np.isfinite(r["rmse"])])}
+        if robust:
+            walked.update(echo)
         print("odometry: " + json.dumps(walked))
     if a.view_weights is not None:
         from ucsa_neural_rendering_amd.utils.depth_frontend import (ViewWeights,
@@ -223,6 +257,8 @@ def main(argv=None):
                    "step_units_median": med([r["step"][1] for r in recs]),
                    "step_units_max": max([r["step"][1] for r in recs], default=None),
                    "rmse_median": med(rmse)}
+        if robust:
+            tracked.update(echo)
         print("refine: " + json.dumps(tracked))
     if a.poses_out is not None:
         os.makedirs(os.path.dirname(os.path.abspath(a.poses_out)), exist_ok=True)

@@ -416,6 +416,15 @@ SIGNATURES = {
     "ucsa_projective_icp_sums": (C.c_int32, [_p, _p, _u32, _p, _p, _p, _u32, _u32, _u32, _f, _f,
                                              _f, _f, C.POINTER(_f), _f, _f, _p, C.c_uint64, _p,
                                              _p, _p, _p]),
+    # ---- the two frame trackers' steps with a weight per row (robust kernel, point weights) ----
+    "ucsa_projective_icp_sums_weighted": (C.c_int32, [_p, _p, _u32, _p, _p, _p, _u32, _u32, _u32,
+                                                      _f, _f, _f, _f, C.POINTER(_f), _f, _f, _p,
+                                                      C.c_int32, _f, _p, C.c_uint64, _p, _p, _p,
+                                                      _p, _p]),
+    "ucsa_tsdf_icp_sums_weighted": (C.c_int32, [_p, _p, _u32, _u32, _u32, C.POINTER(_f),
+                                                C.POINTER(_f), _p, _u32, C.POINTER(_f), _f, _f, _f,
+                                                _p, C.c_int32, _f, _p, C.c_uint64, _p, _p, _p, _p,
+                                                _p]),
     # ---- the depth front end (bilateral filter, points, normals, edge rejection) ----
     "ucsa_depth_filter": (C.c_int32, [_p, _u32, _u32, _u32, _p, _u32, _p, _f, _f, _f, _f, _p, _p]),
     "ucsa_depth_normals": (C.c_int32, [_p, _u32, _u32, _u32, _f, _f, _f, _f, _f, _f, _f, _f, _f,

@@ -7,6 +7,9 @@
 // ucsa_projective_icp_sums (k_projective_icp_sums, after it).  The TSDF step for
 // K transforms in one launch, ucsa_tsdf_icp_sums_batch (k_tsdf_icp_sums_batch,
 // k_icp_reduce_batch), sits between the two and forms the same tree per row.
+// The two frame trackers' steps with a weight per row (a robust kernel on the
+// residual, a weight per point), ucsa_projective_icp_sums_weighted and
+// ucsa_tsdf_icp_sums_weighted, come last: sibling kernels, the same reduction.
 //
 // k_icp_sums<MODE>  a lane per point in work-groups of 256: the point is moved by
 //                   [R | t], the nearest-triangle search of triangle_grid.hip
@@ -555,7 +558,317 @@ __global__ void __launch_bounds__(PG_THREADS) k_projective_icp_sums(
   icp_finish(sh, out);
 }
 
+// ---- the two frame trackers' steps with a weight per row: iteratively reweighted
+// least squares (ucsa_projective_icp_sums_weighted, ucsa_tsdf_icp_sums_weighted) ----
+// k_projective_icp_sums_weighted, k_tsdf_icp_sums_weighted
+//                  the bodies of k_projective_icp_sums and k_tsdf_icp_sums up to
+//                  the gates and the row (J, r), restated here operand for
+//                  operand (those kernels are not touched), then the row's
+//                  weight w = p * rho(|r|) in float32 (icp_robust_weight), the
+//                  row scaled by sqrtf(w), and the 29 terms through icp_term /
+//                  icp_put / icp_finish as they are.  A product by sqrt(w) = 1
+//                  is exact, so without weights the sums are the siblings' bits;
+//                  slot 27 is sum w r^2 and slot 28 the rows with w > 0.
+//
+// The point's weight is loaded with the point, before the gathers: it is on no
+// dependent path.  A lane with i >= n loads nothing, holds +0.0 for all 29 terms
+// and still reaches the one barrier; no index is formed before `inside` holds,
+// exactly as in the siblings (their range arguments apply word for word: the
+// indices are the same expressions).  weight_out[i] is the lane's own slot.
+// No atomics.
+struct RobustArgs {
+  const float* point_weight;  // [n] or NULL: 1
+  float* weight_out;          // [n] or NULL
+  int32_t kind;               // UCSA_ROBUST_NONE / HUBER / TUKEY
+  float scale;                // k or c, in the residual's units
+};
+
+// w = p * rho(|r|): each operation rounded once.  p that is not finite and > 0
+// gives 0: the row takes no part (ucsa_tsdf_integrate_weighted's rule for a pixel).
+__device__ __forceinline__ float icp_robust_weight(float r, float p, int32_t kind, float scale) {
+  const float a = fabsf(r);
+  float rho = 1.0f;
+  if (kind == UCSA_ROBUST_HUBER) {
+    rho = a <= scale ? 1.0f : scale / a;
+  } else if (kind == UCSA_ROBUST_TUKEY) {
+    const float t = a / scale;
+    const float u = 1.0f - t * t;
+    rho = a < scale ? u * u : 0.0f;
+  }
+  const bool usable = p > 0.0f && isfinite(p);
+  return usable ? p * rho : 0.0f;
+}
+
+// scale the row by sqrt(w), report the weight and reduce the 29 terms
+__device__ __forceinline__ void icp_weighted_finish(bool matched, bool live, uint32_t i, float p,
+                                                    const RobustArgs& Q, float (*V)[1], double* sh,
+                                                    double* __restrict__ out) {
+  const float w = icp_robust_weight(V[6][0], p, Q.kind, Q.scale);
+  const bool counts = matched && w > 0.0f;
+  if (live && Q.weight_out) Q.weight_out[i] = counts ? w : 0.0f;
+  const float s = sqrtf(w);
+#pragma unroll
+  for (int a = 0; a < 7; ++a) V[a][0] = s * V[a][0];
+  uint32_t col = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int b = a; b < 6; ++b) icp_put(icp_term<1>(counts, V[a], V[b]), col++, sh);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) icp_put(icp_term<1>(counts, V[a], V[6]), col++, sh);
+  icp_put(icp_term<1>(counts, V[6], V[6]), col++, sh);
+  icp_put(icp_term<1>(counts, V[7], V[7]), col++, sh);
+  icp_finish(sh, out);
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_tsdf_icp_sums_weighted(
+    const float* __restrict__ tsdf, const float* __restrict__ weight, TsdfLattice L,
+    const float* __restrict__ points, uint32_t n, Rigid T, float trunc, float min_weight,
+    float max_tsdf, RobustArgs Q, double* __restrict__ out, float* __restrict__ value,
+    uint8_t* __restrict__ match) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  const uint32_t i = blockIdx.x * PG_THREADS + threadIdx.x;  // < 2^31 + 256
+  const bool live = i < n;
+  float q[3] = {NAN, NAN, NAN};
+  float p = 0.0f;
+  if (live) {
+    const float x = points[3ull * i], y = points[3ull * i + 1u], z = points[3ull * i + 2u];
+    p = Q.point_weight ? Q.point_weight[i] : 1.0f;
+    q[0] = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    q[1] = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    q[2] = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+  }
+  float g[3];
+  bool inside = live;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    g[a] = (q[a] - L.o[a]) / L.h[a];
+    inside = inside && g[a] >= 0.0f && g[a] <= (float)(L.n[a] - 1u);
+  }
+  float f[3] = {0.0f, 0.0f, 0.0f};
+  float w[8], v[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) w[c] = v[c] = 0.0f;
+  if (inside) {
+    uint32_t c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float fl = fminf(floorf(g[a]), (float)(L.n[a] - 2u));
+      c[a] = (uint32_t)fl;
+      f[a] = g[a] - fl;
+    }
+    const uint32_t sj = L.n[2], si = L.n[1] * L.n[2];
+    const uint32_t base = (c[0] * L.n[1] + c[1]) * L.n[2] + c[2];
+    // v[4i + 2j + k]: both arrays, all sixteen loads before the first use
+#pragma unroll
+    for (uint32_t c8 = 0; c8 < 8u; ++c8) {
+      const uint32_t at = base + ((c8 & 4u) ? si : 0u) + ((c8 & 2u) ? sj : 0u) + (c8 & 1u);
+      w[c8] = weight[at];
+      v[c8] = tsdf[at];
+    }
+  }
+  bool observed = inside;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) observed = observed && w[c] >= min_weight;
+  const float c00 = ti_lerp(v[0], v[1], f[2]), c01 = ti_lerp(v[2], v[3], f[2]);
+  const float c10 = ti_lerp(v[4], v[5], f[2]), c11 = ti_lerp(v[6], v[7], f[2]);
+  const float c_0 = ti_lerp(c00, c01, f[1]), c_1 = ti_lerp(c10, c11, f[1]);
+  const float F = ti_lerp(c_0, c_1, f[0]);
+  float G[3];
+  G[0] = c_1 - c_0;
+  G[1] = ti_lerp(c01 - c00, c11 - c10, f[0]);
+  G[2] = ti_lerp(ti_lerp(v[1] - v[0], v[3] - v[2], f[1]), ti_lerp(v[5] - v[4], v[7] - v[6], f[1]),
+                 f[0]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) G[a] = G[a] / L.h[a];
+  const float ln = sqrtf((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+  const bool matched = observed && ln > 0.0f && isfinite(ln) && fabsf(F) <= max_tsdf;
+  if (live) {
+    if (value) value[i] = observed ? F : NAN;
+    if (match) match[i] = matched ? 1 : 0;
+  }
+  float V[8][1];  // J (0..5), r (6) and 1 (7); unused bits of an unmatched row are selected away
+  icp_row<1>(q[0], q[1], q[2], 0.0f, 0.0f, 0.0f, G[0] / ln, G[1] / ln, G[2] / ln, V, 0);
+  V[6][0] = -(F * trunc);
+  icp_weighted_finish(matched, live, i, p, Q, V, sh, out);
+}
+
+__global__ void __launch_bounds__(PG_THREADS) k_projective_icp_sums_weighted(
+    const float* __restrict__ points, const float* __restrict__ normals, uint32_t n, ProjTarget G,
+    Rigid T, float limit2, float min_cos, RobustArgs Q, double* __restrict__ out,
+    int32_t* __restrict__ pixel, float* __restrict__ residual) {
+  __shared__ double sh[ICP_SUMS * 4u];
+  const uint32_t i = blockIdx.x * PG_THREADS + threadIdx.x;  // < 2^31 + 256
+  const bool live = i < n;
+  float q[3] = {NAN, NAN, NAN}, m[3] = {0.0f, 0.0f, 0.0f};
+  float p = 0.0f;
+  if (live) {
+    const float x = points[3ull * i], y = points[3ull * i + 1u], z = points[3ull * i + 2u];
+    p = Q.point_weight ? Q.point_weight[i] : 1.0f;
+    q[0] = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+    q[1] = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+    q[2] = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+    if (normals) {
+      const float s0 = normals[3ull * i], s1 = normals[3ull * i + 1u], s2 = normals[3ull * i + 2u];
+      m[0] = (T.m[0] * s0 + T.m[1] * s1) + T.m[2] * s2;
+      m[1] = (T.m[4] * s0 + T.m[5] * s1) + T.m[6] * s2;
+      m[2] = (T.m[8] * s0 + T.m[9] * s1) + T.m[10] * s2;
+    }
+  }
+  bool inside = live && q[2] > 0.0f;
+  float u = 0.0f, v = 0.0f;
+  if (inside) {
+    u = floorf((G.fx * q[0]) / q[2] + G.cx);
+    v = floorf((G.fy * q[1]) / q[2] + G.cy);
+    inside = u >= 0.0f && u < (float)G.W && v >= 0.0f && v < (float)G.H;
+  }
+  float c[3] = {0.0f, 0.0f, 0.0f}, nt[3] = {0.0f, 0.0f, 0.0f};
+  uint32_t mk = 0u, pix = 0u;
+  if (inside) {
+    pix = (uint32_t)v * G.W + (uint32_t)u;
+    // all seven loads before the first use
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      c[a] = G.points[3ull * pix + a];
+      nt[a] = G.normals[3ull * pix + a];
+    }
+    mk = G.mask[pix];
+  }
+  bool matched = inside && (mk & UCSA_DEPTH_NORMAL) != 0u && (mk & G.reject) == 0u;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) matched = matched && isfinite(c[a]) && isfinite(nt[a]);
+  float d[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) d[a] = c[a] - q[a];
+  const float dist2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+  matched = matched && dist2 <= limit2;
+  if (normals) matched = matched && (m[0] * nt[0] + m[1] * nt[1]) + m[2] * nt[2] >= min_cos;
+  float V[8][1];  // J (0..5), r (6) and 1 (7); unused bits of an unmatched row are selected away
+  icp_row<1>(q[0], q[1], q[2], d[0], d[1], d[2], nt[0], nt[1], nt[2], V, 0);
+  if (live) {
+    if (pixel) pixel[i] = matched ? (int32_t)pix : -1;
+    if (residual) residual[i] = matched ? V[6][0] : NAN;  // the unscaled r
+  }
+  icp_weighted_finish(matched, live, i, p, Q, V, sh, out);
+}
+
+// the robust arguments' checks, shared by the two entry points: 0, or 1 (kind), 2 (scale)
+int icp_robust_args(int32_t kind, float scale) {
+  if (kind != UCSA_ROBUST_NONE && kind != UCSA_ROBUST_HUBER && kind != UCSA_ROBUST_TUKEY) return 1;
+  if (kind != UCSA_ROBUST_NONE && !(scale > 0.0f && pg_host_finite(scale))) return 2;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int32_t ucsa_projective_icp_sums_weighted(
+    const float* points, const float* normals, uint32_t n, const float* target_points,
+    const float* target_normals, const uint8_t* target_mask, uint32_t H, uint32_t W,
+    uint32_t reject, float fx, float fy, float cx, float cy, const float* transform,
+    float max_dist, float min_cos, const float* point_weight, int32_t robust_kind,
+    float robust_scale, double* workspace, uint64_t workspace_doubles, double* sums,
+    int32_t* pixel, float* residual, float* weight_out, void* stream) {
+  UCSA_CHECK_ARG(n <= 0x7FFFFFFFu, 2);
+  UCSA_CHECK_ARG(n == 0 || points, 0);
+  UCSA_CHECK_ARG(target_points, 3);
+  UCSA_CHECK_ARG(target_normals, 4);
+  UCSA_CHECK_ARG(target_mask, 5);
+  UCSA_CHECK_ARG(H >= 1 && H <= 16384, 6);
+  UCSA_CHECK_ARG(W >= 1 && W <= 16384, 7);
+  UCSA_CHECK_ARG((reject & ~(UCSA_DEPTH_EDGE | UCSA_DEPTH_GRAZING)) == 0u, 8);
+  UCSA_CHECK_ARG(fx > 0.0f && pg_host_finite(fx), 9);
+  UCSA_CHECK_ARG(fy > 0.0f && pg_host_finite(fy), 10);
+  UCSA_CHECK_ARG(pg_host_finite(cx), 11);
+  UCSA_CHECK_ARG(pg_host_finite(cy), 12);
+  UCSA_CHECK_ARG(transform, 13);
+  const float limit2 = max_dist * max_dist;
+  UCSA_CHECK_ARG(max_dist > 0.0f && pg_host_finite(max_dist) && pg_host_finite(limit2), 14);
+  UCSA_CHECK_ARG(min_cos >= -1.0f && min_cos <= 1.0f, 15);
+  const int bad = icp_robust_args(robust_kind, robust_scale);
+  UCSA_CHECK_ARG(bad != 1, 17);
+  UCSA_CHECK_ARG(bad != 2, 18);
+  const uint64_t ws_rows = icp_workspace_rows(n);
+  UCSA_CHECK_ARG(ws_rows == 0 || workspace, 19);
+  UCSA_CHECK_ARG(workspace_doubles >= ws_rows * ICP_SUMS, 20);
+  UCSA_CHECK_ARG(sums, 21);
+  ProjTarget G;
+  G.points = target_points, G.normals = target_normals, G.mask = target_mask;
+  G.H = H, G.W = W, G.reject = reject;
+  G.fx = fx, G.fy = fy, G.cx = cx, G.cy = cy;
+  Rigid T;
+  for (int k = 0; k < 12; ++k) T.m[k] = transform[k];
+  RobustArgs Q;
+  Q.point_weight = point_weight, Q.weight_out = weight_out;
+  Q.kind = robust_kind, Q.scale = robust_kind == UCSA_ROBUST_NONE ? 1.0f : robust_scale;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t count = n ? ucsa_div_up(n, PG_THREADS) : 1u;  // at least one stage: n == 0 gives +0.0
+  double* out = count == 1u ? sums : workspace;
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_projective_icp_sums_weighted, dim3(count), dim3(PG_THREADS), 0, s, points,
+                     normals, n, G, T, limit2, min_cos, Q, out, pixel, residual);
+  while (count > 1u) {  // as in ucsa_icp_sums: at most three passes for n < 2^31
+    const uint32_t next = ucsa_div_up(count, PG_THREADS);
+    const double* in = out;
+    out = next == 1u ? sums : out + (uint64_t)count * ICP_SUMS;
+    hipLaunchKernelGGL(k_icp_reduce, dim3(next), dim3(PG_THREADS), 0, s, in, count, out);
+    count = next;
+  }
+  return ucsa_launch_status();
+}
+
+extern "C" int32_t ucsa_tsdf_icp_sums_weighted(
+    const float* tsdf, const float* weight, uint32_t nx, uint32_t ny, uint32_t nz,
+    const float* origin3, const float* spacing3, const float* points, uint32_t n,
+    const float* transform, float trunc, float min_weight, float max_tsdf,
+    const float* point_weight, int32_t robust_kind, float robust_scale, double* workspace,
+    uint64_t workspace_doubles, double* sums, float* value, uint8_t* matched, float* weight_out,
+    void* stream) {
+  UCSA_CHECK_ARG(tsdf, 0);
+  UCSA_CHECK_ARG(weight, 1);
+  UCSA_CHECK_ARG(nx >= 2 && ny >= 1 && nz >= 1 && (uint64_t)nx * ny * nz <= 0x7FFFFFFFull, 2);
+  UCSA_CHECK_ARG(ny >= 2, 3);
+  UCSA_CHECK_ARG(nz >= 2, 4);
+  UCSA_CHECK_ARG(origin3 && pg_host_finite(origin3[0]) && pg_host_finite(origin3[1]) &&
+                     pg_host_finite(origin3[2]), 5);
+  UCSA_CHECK_ARG(spacing3, 6);
+  for (int a = 0; a < 3; ++a) UCSA_CHECK_ARG(spacing3[a] > 0.0f && pg_host_finite(spacing3[a]), 6);
+  UCSA_CHECK_ARG(n <= 0x7FFFFFFFu, 8);
+  UCSA_CHECK_ARG(n == 0 || points, 7);
+  UCSA_CHECK_ARG(transform, 9);
+  UCSA_CHECK_ARG(trunc > 0.0f && pg_host_finite(trunc), 10);
+  UCSA_CHECK_ARG(min_weight > 0.0f, 11);
+  UCSA_CHECK_ARG(max_tsdf > 0.0f && max_tsdf <= 1.0f, 12);
+  const int bad = icp_robust_args(robust_kind, robust_scale);
+  UCSA_CHECK_ARG(bad != 1, 14);
+  UCSA_CHECK_ARG(bad != 2, 15);
+  const uint64_t ws_rows = icp_workspace_rows(n);
+  UCSA_CHECK_ARG(ws_rows == 0 || workspace, 16);
+  UCSA_CHECK_ARG(workspace_doubles >= ws_rows * ICP_SUMS, 17);
+  UCSA_CHECK_ARG(sums, 18);
+  TsdfLattice L;
+  L.n[0] = nx, L.n[1] = ny, L.n[2] = nz;
+  for (int a = 0; a < 3; ++a) L.o[a] = origin3[a], L.h[a] = spacing3[a];
+  Rigid T;
+  for (int k = 0; k < 12; ++k) T.m[k] = transform[k];
+  RobustArgs Q;
+  Q.point_weight = point_weight, Q.weight_out = weight_out;
+  Q.kind = robust_kind, Q.scale = robust_kind == UCSA_ROBUST_NONE ? 1.0f : robust_scale;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t count = n ? ucsa_div_up(n, PG_THREADS) : 1u;  // at least one stage: n == 0 gives +0.0
+  double* out = count == 1u ? sums : workspace;
+  UCSA_CLEAR_ERR();
+  hipLaunchKernelGGL(k_tsdf_icp_sums_weighted, dim3(count), dim3(PG_THREADS), 0, s, tsdf, weight, L,
+                     points, n, T, trunc, min_weight, max_tsdf, Q, out, value, matched);
+  while (count > 1u) {  // as in ucsa_icp_sums: at most three passes for n < 2^31
+    const uint32_t next = ucsa_div_up(count, PG_THREADS);
+    const double* in = out;
+    out = next == 1u ? sums : out + (uint64_t)count * ICP_SUMS;
+    hipLaunchKernelGGL(k_icp_reduce, dim3(next), dim3(PG_THREADS), 0, s, in, count, out);
+    count = next;
+  }
+  return ucsa_launch_status();
+}
 
 extern "C" int32_t ucsa_projective_icp_sums(const float* points, const float* normals, uint32_t n,
                                             const float* target_points,

@@ -137,6 +137,28 @@ def icp_sums(grid, verts, faces, unit_normal, points, transform, max_dist: float
     return (sums, face, dist2) if return_matches else sums
 
 
+def _tsdf_step_args(volume, points, transform, trunc, min_weight, max_tsdf):
+    """the checked arguments ``tsdf_sums`` and ``tsdf_sums_weighted`` share"""
+    (nx, ny, nz), dev = volume_lattice(volume)
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
+                             f"{(nx, ny, nz)}")
+    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
+    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
+    n = int(pts.shape[0])
+    if n > 0x7FFFFFFF:
+        raise _lib.UcsaError("points must have at most 2^31-1 rows")
+    t12 = _transform12(transform)
+    trunc = _positive(trunc, "trunc")
+    min_weight = float(min_weight)
+    if not min_weight > 0:
+        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
+    max_tsdf = float(max_tsdf)
+    if not 0 < max_tsdf <= 1:
+        raise _lib.UcsaError(f"max_tsdf must be in (0, 1], got {max_tsdf!r}")
+    return (nx, ny, nz), dev, origin, spacing, pts, n, t12, trunc, min_weight, max_tsdf
+
+
 def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
               max_tsdf: float = 1.0, return_matches: bool = False):
     """The normal equations of one point-to-plane ICP step of ``points`` [N,3]
@@ -157,23 +179,8 @@ def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
     truncation distance the volume was integrated with.  ``value`` is F where
     the cell is observed and NaN elsewhere.  Contract of ucsa_tsdf_icp_sums
     (include/ucsa_hip.h)."""
-    (nx, ny, nz), dev = volume_lattice(volume)
-    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
-        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
-                             f"{(nx, ny, nz)}")
-    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
-    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
-    n = int(pts.shape[0])
-    if n > 0x7FFFFFFF:
-        raise _lib.UcsaError("points must have at most 2^31-1 rows")
-    t12 = _transform12(transform)
-    trunc = _positive(trunc, "trunc")
-    min_weight = float(min_weight)
-    if not min_weight > 0:
-        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
-    max_tsdf = float(max_tsdf)
-    if not 0 < max_tsdf <= 1:
-        raise _lib.UcsaError(f"max_tsdf must be in (0, 1], got {max_tsdf!r}")
+    (nx, ny, nz), dev, origin, spacing, pts, n, t12, trunc, min_weight, max_tsdf = \
+        _tsdf_step_args(volume, points, transform, trunc, min_weight, max_tsdf)
     ws_doubles = ICP_SUMS * workspace_rows(n)
     ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
     sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
@@ -279,30 +286,9 @@ def tsdf_scores(volume, points, transforms, min_weight: float = 1.0, max_tsdf: f
     return scores
 
 
-def projective_sums(points, normals, target_points, target_normals, target_mask, intrinsics,
-                    transform, max_dist: float, min_cos: float = 0.0,
-                    reject: int = _EDGE | _GRAZING, return_matches: bool = False):
-    """The normal equations of one projective point-to-plane ICP step of
-    ``points`` [N,3] (float32 on the GPU) against a pair of maps -> ``sums``
-    float64 [29] on the device, or (``sums``, ``pixel`` int32 [N], ``residual``
-    float32 [N]) with ``return_matches``.  The maps are ``target_points`` and
-    ``target_normals`` [H,W,3] float32 in the target camera's frame and
-    ``target_mask`` [H,W] uint8 (``ops.depth.depth_normals``' outputs for one
-    frame, or a model ray-cast dressed the same way); ``intrinsics`` (fx, fy,
-    cx, cy) is the target camera.  One call moves every point by ``transform``
-    (a 3x4 or 4x4 array-like on the host, converted to float32: source frame ->
-    target camera frame, q = R p + t), projects q into the target image with
-    ``ops.integrate_tsdf``'s expression and gathers the pixel it falls in: no
-    search.  The pair matches when the pixel has a normal (mask bit 2), carries
-    no bit of ``reject`` (a set of EDGE (4) | GRAZING (8)), its six floats are
-    finite, the target point c lies within ``max_dist`` of q and -- with source
-    ``normals`` [N,3]; None: no such gate -- the rotated source normal and the
-    target normal nt have a cosine >= ``min_cos``.  Over the matched points
-    r = nt . (c - q) and J = (q x nt, nt) are summed as ``icp_sums`` does in mode
-    "plane": the same 29 float64 numbers in the same tree, so
-    ``utils.registration.solve_step`` and ``compose`` take them unchanged.
-    ``pixel`` is the matched pixel's row-major index or -1, ``residual`` r or
-    NaN.  Contract of ucsa_projective_icp_sums (include/ucsa_hip.h)."""
+def _projective_step_args(points, normals, target_points, target_normals, target_mask,
+                          intrinsics, transform, max_dist, min_cos, reject):
+    """the checked arguments ``projective_sums`` and ``projective_sums_weighted`` share"""
     pts = _points3(points, "points")
     dev = pts.device
     n = int(pts.shape[0])
@@ -328,6 +314,36 @@ def projective_sums(points, normals, target_points, target_normals, target_mask,
         raise _lib.UcsaError(f"min_cos must be in [-1, 1], got {min_cos!r}")
     if isinstance(reject, bool) or not isinstance(reject, int) or reject & ~(_EDGE | _GRAZING):
         raise _lib.UcsaError(f"reject must be a set of EDGE (4) | GRAZING (8), got {reject!r}")
+    return dev, pts, n, nrm, tp, tn, tm, H, W, (fx, fy, cx, cy), t12, max_dist, min_cos
+
+
+def projective_sums(points, normals, target_points, target_normals, target_mask, intrinsics,
+                    transform, max_dist: float, min_cos: float = 0.0,
+                    reject: int = _EDGE | _GRAZING, return_matches: bool = False):
+    """The normal equations of one projective point-to-plane ICP step of
+    ``points`` [N,3] (float32 on the GPU) against a pair of maps -> ``sums``
+    float64 [29] on the device, or (``sums``, ``pixel`` int32 [N], ``residual``
+    float32 [N]) with ``return_matches``.  The maps are ``target_points`` and
+    ``target_normals`` [H,W,3] float32 in the target camera's frame and
+    ``target_mask`` [H,W] uint8 (``ops.depth.depth_normals``' outputs for one
+    frame, or a model ray-cast dressed the same way); ``intrinsics`` (fx, fy,
+    cx, cy) is the target camera.  One call moves every point by ``transform``
+    (a 3x4 or 4x4 array-like on the host, converted to float32: source frame ->
+    target camera frame, q = R p + t), projects q into the target image with
+    ``ops.integrate_tsdf``'s expression and gathers the pixel it falls in: no
+    search.  The pair matches when the pixel has a normal (mask bit 2), carries
+    no bit of ``reject`` (a set of EDGE (4) | GRAZING (8)), its six floats are
+    finite, the target point c lies within ``max_dist`` of q and -- with source
+    ``normals`` [N,3]; None: no such gate -- the rotated source normal and the
+    target normal nt have a cosine >= ``min_cos``.  Over the matched points
+    r = nt . (c - q) and J = (q x nt, nt) are summed as ``icp_sums`` does in mode
+    "plane": the same 29 float64 numbers in the same tree, so
+    ``utils.registration.solve_step`` and ``compose`` take them unchanged.
+    ``pixel`` is the matched pixel's row-major index or -1, ``residual`` r or
+    NaN.  Contract of ucsa_projective_icp_sums (include/ucsa_hip.h)."""
+    dev, pts, n, nrm, tp, tn, tm, H, W, (fx, fy, cx, cy), t12, max_dist, min_cos = \
+        _projective_step_args(points, normals, target_points, target_normals, target_mask,
+                              intrinsics, transform, max_dist, min_cos, reject)
     ws_doubles = ICP_SUMS * workspace_rows(n)
     ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
     sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
@@ -338,3 +354,91 @@ def projective_sums(points, normals, target_points, target_normals, target_mask,
         reject, fx, fy, cx, cy, t12, max_dist, min_cos, _ptr(ws), ws_doubles, _ptr(sums),
         _ptr(pixel), _ptr(residual), _stream()), "ucsa_projective_icp_sums")
     return (sums, pixel, residual) if return_matches else sums
+
+
+ROBUST = {"none": 0, "huber": 1, "tukey": 2}  # UCSA_ROBUST_NONE / HUBER / TUKEY
+
+
+def _robust_args(point_weight, robust, robust_scale, n, dev):
+    """the checked weight arguments of the two weighted steps -> (weights or None,
+    kind, scale)"""
+    if robust not in ROBUST:
+        raise _lib.UcsaError(f"robust must be 'none', 'huber' or 'tukey', got {robust!r}")
+    scale = 1.0
+    if ROBUST[robust]:
+        if robust_scale is None:
+            raise _lib.UcsaError(f"robust={robust!r} needs a robust_scale")
+        scale = _positive(robust_scale, "robust_scale")
+    pw = None if point_weight is None else \
+        _gpu(point_weight, "point_weight", torch.float32, (n,), device=dev)
+    return pw, ROBUST[robust], scale
+
+
+def projective_sums_weighted(points, normals, target_points, target_normals, target_mask,
+                             intrinsics, transform, max_dist: float, min_cos: float = 0.0,
+                             reject: int = _EDGE | _GRAZING, point_weight=None,
+                             robust: str = "none", robust_scale=None,
+                             return_matches: bool = False):
+    """``projective_sums`` with a weight per row: one step of iteratively
+    reweighted least squares -> ``sums`` float64 [29] on the device, or
+    (``sums``, ``pixel``, ``residual``, ``weight`` float32 [N]) with
+    ``return_matches``.  Association, gates and the row (J, r) are
+    ``projective_sums``'.  Then, in float32, w = p * rho(|r|): p is
+    ``point_weight`` [N] (float32 on the GPU; None: 1; a p that is not finite
+    and > 0 takes the point out, ``ops.integrate_tsdf_weighted``'s rule for a
+    pixel) and rho the kernel ``robust``: "none" 1; "huber" 1 for |r| <= k, else
+    k / |r|; "tukey" (1 - (|r| / c)^2)^2 for |r| < c, else 0, with k or c =
+    ``robust_scale`` in the residual's units.  A row counts when it matched and
+    w > 0; it enters scaled by sqrt(w), so the sums are sum w J^T J, sum w J^T r,
+    sum w r^2 and the number of rows that count, in ``projective_sums``' layout
+    and tree: ``utils.registration.solve_step`` and ``compose`` take them
+    unchanged.  ``weight`` is w for a row that counts and 0 otherwise;
+    ``pixel`` and ``residual`` (the unscaled r) report the geometric match.
+    With "none" and no ``point_weight`` the sums equal ``projective_sums``' as
+    int64 words.  Contract of ucsa_projective_icp_sums_weighted
+    (include/ucsa_hip.h)."""
+    dev, pts, n, nrm, tp, tn, tm, H, W, (fx, fy, cx, cy), t12, max_dist, min_cos = \
+        _projective_step_args(points, normals, target_points, target_normals, target_mask,
+                              intrinsics, transform, max_dist, min_cos, reject)
+    pw, kind, scale = _robust_args(point_weight, robust, robust_scale, n, dev)
+    ws_doubles = ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    pixel = torch.empty(n, dtype=torch.int32, device=dev) if return_matches else None
+    residual = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    weight = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    check(lib().ucsa_projective_icp_sums_weighted(
+        _ptr(pts) if n else None, _ptr(nrm) if n else None, n, _ptr(tp), _ptr(tn), _ptr(tm), H, W,
+        reject, fx, fy, cx, cy, t12, max_dist, min_cos, _ptr(pw) if n else None, kind, scale,
+        _ptr(ws), ws_doubles, _ptr(sums), _ptr(pixel), _ptr(residual), _ptr(weight), _stream()),
+        "ucsa_projective_icp_sums_weighted")
+    return (sums, pixel, residual, weight) if return_matches else sums
+
+
+def tsdf_sums_weighted(volume, points, transform, trunc: float, min_weight: float = 1.0,
+                       max_tsdf: float = 1.0, point_weight=None, robust: str = "none",
+                       robust_scale=None, return_matches: bool = False):
+    """``tsdf_sums`` with a weight per row, as ``projective_sums_weighted`` is to
+    ``projective_sums`` -> ``sums`` float64 [29] on the device, or (``sums``,
+    ``value``, ``matched``, ``weight`` float32 [N]) with ``return_matches``.  The
+    sample, the gates and the row (J, r = -(F * trunc)) are ``tsdf_sums``'; the
+    weight w = p * rho(|r|), the rows that count, the scaling by sqrt(w) and the
+    meaning of the 29 sums are ``projective_sums_weighted``'s, ``robust_scale``
+    in scene units like r.  ``value`` and ``matched`` report the geometric
+    match.  With "none" and no ``point_weight`` the sums equal ``tsdf_sums``' as
+    int64 words.  Contract of ucsa_tsdf_icp_sums_weighted (include/ucsa_hip.h)."""
+    (nx, ny, nz), dev, origin, spacing, pts, n, t12, trunc, min_weight, max_tsdf = \
+        _tsdf_step_args(volume, points, transform, trunc, min_weight, max_tsdf)
+    pw, kind, scale = _robust_args(point_weight, robust, robust_scale, n, dev)
+    ws_doubles = ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    value = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    matched = torch.empty(n, dtype=torch.uint8, device=dev) if return_matches else None
+    weight = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
+    check(lib().ucsa_tsdf_icp_sums_weighted(
+        _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
+        _ptr(pts) if n else None, n, t12, trunc, min_weight, max_tsdf, _ptr(pw) if n else None,
+        kind, scale, _ptr(ws), ws_doubles, _ptr(sums), _ptr(value), _ptr(matched), _ptr(weight),
+        _stream()), "ucsa_tsdf_icp_sums_weighted")
+    return (sums, value, matched, weight) if return_matches else sums

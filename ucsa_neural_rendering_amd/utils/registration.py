@@ -36,10 +36,17 @@ a TSDF volume in one call (``ops.register.tsdf_scores``), the best refined --
 one after another, or with ``lockstep`` all together
 (``register_points_tsdf_batch`` over ``ops.register.tsdf_sums_batch``).
 
+The two frame trackers (``register_frames`` and ``register_points_tsdf`` with what
+sits on them) take ``robust`` / ``robust_scale`` / ``point_weight`` and, for the
+frames, ``view_weights``: iteratively reweighted least squares over
+``ops.register.projective_sums_weighted`` / ``tsdf_sums_weighted``, for frames
+that show something their target does not.  Off by default; for the tracking
+regime only (a redescending kernel narrows the basin).
+
 Not here: scale, rejection of matches on open boundaries, normal compatibility
-gates in the mesh and TSDF routes, robust kernels beyond the ``max_dist``
-schedule: the local loops must start within ``max_dist`` (or ``trunc``) and a few
-degrees of the answer."""
+gates in the mesh and TSDF routes, robust kernels in the mesh route and the
+lock-step batch, scales estimated from the data: the local loops must start
+within ``max_dist`` (or ``trunc``) and a few degrees of the answer."""
 from __future__ import annotations
 
 import math
@@ -137,6 +144,47 @@ def rotation_angle(R):
     s = 0.5 * math.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2
                         + (R[1, 0] - R[0, 1]) ** 2)
     return math.atan2(s, 0.5 * (float(np.trace(R)) - 1.0))
+
+
+# ---------------------------------------------------------------------------
+# robust kernels: the scale and its schedule (host)
+# ---------------------------------------------------------------------------
+ROBUST_KINDS = ("none", "huber", "tukey")
+_ROBUST_TUNING = {"huber": 1.345, "tukey": 4.685}
+
+
+def robust_scale_for(kind: str, sigma: float) -> float:
+    """The ``robust_scale`` that keeps 95 % of least squares' efficiency on
+    Gaussian residuals of standard deviation ``sigma``: 1.345 sigma for "huber",
+    4.685 sigma for "tukey"."""
+    if kind not in _ROBUST_TUNING:
+        raise ValueError(f"robust_scale_for: kind must be 'huber' or 'tukey', got {kind!r}")
+    sigma = float(sigma)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"robust_scale_for: sigma must be > 0 and finite, got {sigma!r}")
+    return _ROBUST_TUNING[kind] * sigma
+
+
+def robust_schedule(robust: str, robust_scale, length=None):
+    """``robust_scale`` (a number or a sequence) as a list of floats.  ``length``
+    None: the sequence as it stands (indexed min(k, len - 1) by the TSDF loop);
+    a number: exactly that many entries, a single number repeated (the levels of
+    ``register_frames``).  "none" gives [None] (times ``length``)."""
+    if robust not in ROBUST_KINDS:
+        raise ValueError(f"robust must be one of {ROBUST_KINDS}, got {robust!r}")
+    if robust == "none":
+        return [None] * (1 if length is None else int(length))
+    if robust_scale is None:
+        raise ValueError(f"robust={robust!r} needs a robust_scale")
+    scales = [float(v) for v in np.atleast_1d(np.asarray(robust_scale, np.float64)).reshape(-1)]
+    if length is not None:
+        if len(scales) == 1:
+            scales = scales * int(length)
+        if len(scales) != int(length):
+            raise ValueError(f"robust_scale names {len(scales)} levels, iterations {length}")
+    if not scales or not all(v > 0.0 and math.isfinite(v) for v in scales):
+        raise ValueError(f"robust_scale must be > 0 and finite, got {robust_scale!r}")
+    return scales
 
 
 # ---------------------------------------------------------------------------
@@ -312,7 +360,8 @@ def refine_poses(depths, poses, intrinsics, grid_or_mesh, **kw):
 def register_points_tsdf(points, volume, trunc: float, init=None, iterations: int = 30,
                          min_weight: float = 1.0, max_tsdf: float = 1.0, max_tsdf_schedule=None,
                          tol_rot: float = 1e-6, tol_trans: float = 1e-6, rcond: float = 1e-8,
-                         device="cuda"):
+                         device="cuda", robust: str = "none", robust_scale=None,
+                         point_weight=None):
     """Align ``points`` [N,3] to the surface a TSDF ``volume`` holds
     (``ops.tsdf_volume``'s dict on the device, integrated with the truncation
     distance ``trunc``) -> ``register_points``' dict with the same keys
@@ -333,7 +382,20 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
     so the pose error, measured at the surface (translation plus angle times
     the distance to the surface), must stay below ``trunc``.  Anything coarser
     is the mesh route's job (``register_points`` with a ``max_dist_schedule``)
-    or global alignment (``global_register_points_tsdf``)."""
+    or global alignment (``global_register_points_tsdf``).
+
+    ``robust`` ("none", "huber", "tukey"), ``robust_scale`` and ``point_weight``
+    turn the loop into iteratively reweighted least squares: each iteration is
+    then ``ops.register.tsdf_sums_weighted`` with the kernel, the scale of
+    iteration k -- ``robust_scale`` is a number, or a sequence indexed
+    min(k, len - 1) like ``max_tsdf_schedule``, in scene units like r --
+    and ``point_weight`` [N] (a weight per point, float32; a point whose weight
+    is not finite and > 0 takes no part).  ``matched`` then counts the rows with
+    a positive weight, ``rmse`` is sqrt(sum w r^2 / that count), and every
+    ``history`` entry carries ``robust`` and ``robust_scale``.  With the defaults
+    the loop calls ``tsdf_sums`` and nothing else, and its entries have no such
+    keys.  For tracking, from a pose already near the answer: "tukey" ignores
+    what lies beyond its scale, true matches of a far start included."""
     import torch
 
     from .. import ops
@@ -341,10 +403,21 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
     T = compose(np.eye(4) if init is None else np.asarray(init, np.float64), np.zeros(6))
     schedule = [float(max_tsdf)] if max_tsdf_schedule is None else \
         [float(m) for m in max_tsdf_schedule]
+    scales = robust_schedule(robust, robust_scale)
+    weighted = robust != "none" or point_weight is not None
+    pw = None if point_weight is None else \
+        _on_device(point_weight, torch.float32, 1, pts.device).reshape(-1)
     history, rank, converged, done = [], 0, False, 0
     for k in range(int(iterations)):
         mt = schedule[min(k, len(schedule) - 1)]
-        sums = ops.register.tsdf_sums(volume, pts, T, trunc, min_weight, mt).cpu().numpy()
+        extra = {}
+        if weighted:
+            sc = scales[min(k, len(scales) - 1)]
+            sums = ops.register.tsdf_sums_weighted(volume, pts, T, trunc, min_weight, mt, pw,
+                                                   robust, sc).cpu().numpy()
+            extra = {"robust": robust, "robust_scale": sc}
+        else:
+            sums = ops.register.tsdf_sums(volume, pts, T, trunc, min_weight, mt).cpu().numpy()
         _, _, sse, count = normal_equations(sums)
         xi, rank = solve_step(sums, rcond)
         T = compose(T, xi)
@@ -352,7 +425,7 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
         om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
         history.append({"matched": int(round(count)),
                         "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
-                        "omega": om, "upsilon": up, "max_tsdf": mt, "sums": sums})
+                        "omega": om, "upsilon": up, "max_tsdf": mt, "sums": sums, **extra})
         if count > 0 and om <= tol_rot and up <= tol_trans:
             converged = True
             break
@@ -467,7 +540,9 @@ def refine_pose_tsdf(depth, pose, intrinsics, volume, trunc: float, stride: int 
     valid pixels are back-projected into the camera frame (``backproject``) and
     registered with ``init=pose``: frame-to-model tracking, for a pose whose
     error at the surface is below ``trunc`` (see ``register_points_tsdf``).
-    ``depth_filter`` as for ``refine_pose``."""
+    ``depth_filter`` as for ``refine_pose``.  ``robust``, ``robust_scale`` and
+    ``point_weight`` (one weight per point kept, in ``backproject``'s row-major
+    order) go to ``register_points_tsdf`` with the rest of ``kw``."""
     import torch
     device = kw.pop("device", "cuda")
     d = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth, np.float32))
@@ -546,9 +621,37 @@ def _source_rows(maps, reject):
     return maps["points"][keep].contiguous(), maps["normals"][keep].contiguous()
 
 
+def _source_weights(maps, reject, level_weight, view_weights, depth_filter):
+    """the weights of ``_source_rows``' rows -> float32 [N] or None: the map
+    ``level_weight`` [h,w], or ``ops.depth.depth_confidence`` of the level's maps
+    with the settings ``view_weights``, at the kept pixels"""
+    import torch
+
+    from .. import ops
+    if level_weight is None and view_weights is None:
+        return None
+    m = maps["mask"]
+    keep = ((m & _NORMAL) != 0) & ((m & reject) == 0)
+    if view_weights is not None:
+        from .depth_frontend import DepthFilter
+        sd, s2 = view_weights.resolved(DepthFilter() if depth_filter is None else depth_filter)
+        w = ops.depth.depth_confidence(maps["points"][None], maps["normals"][None], m[None], sd,
+                                       s2, view_weights.cos_floor, reject)[0]
+    else:
+        w = level_weight if torch.is_tensor(level_weight) else \
+            torch.as_tensor(np.asarray(level_weight, np.float32))
+        w = w.to(device=m.device, dtype=torch.float32)
+        if tuple(w.shape) != tuple(m.shape):
+            raise ValueError(f"point_weight of a level must be {tuple(m.shape)}, got "
+                             f"{tuple(w.shape)}")
+    return w[keep].contiguous()
+
+
 def register_frames(src_maps, dst_maps, intrinsics, init=None, iterations=(10, 5, 4),
                     max_dist: float = 0.3, min_cos: float = 0.8, reject: int = _EDGE | _GRAZING,
-                    rcond: float = 1e-8, tol_rot: float = 1e-6, tol_trans: float = 1e-6):
+                    rcond: float = 1e-8, tol_rot: float = 1e-6, tol_trans: float = 1e-6,
+                    robust: str = "none", robust_scale=None, point_weight=None,
+                    view_weights=None, depth_filter=None):
     """Align one frame to a second pair of maps by projective point-to-plane ICP,
     coarse to fine -> ``register_points``' dict; ``transform`` (4x4 float64) moves
     the source camera's frame into the target camera's, and every ``history``
@@ -563,12 +666,41 @@ def register_frames(src_maps, dst_maps, intrinsics, init=None, iterations=(10, 5
     ``max_dist`` and with a cosine of the normals >= ``min_cos``.  Each iteration
     is ``ops.register.projective_sums``, one read of 29 doubles, ``solve_step``
     and ``compose``.  The basin is set by ``max_dist`` and the scene, not by a
-    truncation band; rank < 6 says the views do not constrain the motion."""
+    truncation band; rank < 6 says the views do not constrain the motion.
+
+    ``robust`` ("none", "huber", "tukey") with ``robust_scale`` -- a number, or
+    one per level, finest first, like ``iterations``; in scene units like r --
+    and a weight per source pixel turn the loop into iteratively reweighted
+    least squares: each iteration is then
+    ``ops.register.projective_sums_weighted``.  The pixel weights are
+    ``point_weight``, a sequence over the levels, finest first, of [h,w] float32
+    maps (None for a level without; a single map where there is one level), or
+    with ``view_weights`` (a ``utils.depth_frontend.ViewWeights``; its None
+    sigmas are ``depth_filter``'s, None: the defaults')
+    ``ops.depth.depth_confidence`` of the source level's own maps; a source row
+    takes the value at its pixel, and one that is not finite and > 0 takes no
+    part.  ``matched`` then counts the rows with a positive weight, ``rmse`` is
+    sqrt(sum w r^2 / that count), and every ``history`` entry carries ``robust``
+    and ``robust_scale``.  With the defaults the loop calls ``projective_sums``
+    and nothing else, and its entries have no such keys.  This is for tracking,
+    from a few degrees and centimetres: "tukey" ignores what lies beyond its
+    scale, true matches of a far start included, and a scale widened on the
+    coarse levels can lock onto the outliers instead (docs/DESIGN_NOTEBOOK.md,
+    section RB)."""
     from .. import ops
     iterations = tuple(int(k) for k in iterations)
     if not iterations or len(src_maps) < len(iterations) or len(dst_maps) < len(iterations):
         raise ValueError(f"iterations names {len(iterations)} levels, the maps have "
                          f"{len(src_maps)} and {len(dst_maps)}")
+    scales = robust_schedule(robust, robust_scale, len(iterations))
+    if point_weight is not None and view_weights is not None:
+        raise ValueError("give point_weight or view_weights, not both")
+    if point_weight is not None and not isinstance(point_weight, (list, tuple)):
+        point_weight = [point_weight]
+    if point_weight is not None and len(point_weight) != len(iterations):
+        raise ValueError(f"point_weight names {len(point_weight)} levels, iterations "
+                         f"{len(iterations)}")
+    weighted = robust != "none" or point_weight is not None or view_weights is not None
     T = compose(np.eye(4) if init is None else np.asarray(init, np.float64), np.zeros(6))
     history, rank, done, converged, n_points = [], 0, 0, False, 0
     for level in reversed(range(len(iterations))):
@@ -576,10 +708,21 @@ def register_frames(src_maps, dst_maps, intrinsics, init=None, iterations=(10, 5
         dst = dst_maps[level]
         K = level_intrinsics(intrinsics, level)
         n_points, converged = int(pts.shape[0]), False
+        extra = {}
+        if weighted:
+            pw = _source_weights(src_maps[level], reject,
+                                 None if point_weight is None else point_weight[level],
+                                 view_weights, depth_filter)
+            extra = {"robust": robust, "robust_scale": scales[level]}
         for _ in range(iterations[level]):
-            sums = ops.register.projective_sums(pts, nrm, dst["points"], dst["normals"],
-                                                dst["mask"], K, T, max_dist, min_cos,
-                                                reject).cpu().numpy()
+            if weighted:
+                sums = ops.register.projective_sums_weighted(
+                    pts, nrm, dst["points"], dst["normals"], dst["mask"], K, T, max_dist, min_cos,
+                    reject, pw, robust, scales[level]).cpu().numpy()
+            else:
+                sums = ops.register.projective_sums(pts, nrm, dst["points"], dst["normals"],
+                                                    dst["mask"], K, T, max_dist, min_cos,
+                                                    reject).cpu().numpy()
             _, _, sse, count = normal_equations(sums)
             xi, rank = solve_step(sums, rcond)
             T = compose(T, xi)
@@ -588,7 +731,7 @@ def register_frames(src_maps, dst_maps, intrinsics, init=None, iterations=(10, 5
             history.append({"level": level, "matched": int(round(count)),
                             "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
                             "omega": om, "upsilon": up, "max_dist": float(max_dist),
-                            "sums": sums})
+                            "sums": sums, **extra})
             if count > 0 and om <= tol_rot and up <= tol_trans:
                 converged = True
                 break
@@ -609,8 +752,12 @@ def odometry(depths, intrinsics, depth_filter=None, iterations=(10, 5, 4),
     ``min_matched`` falls back: its motion is kept at the identity and counted.
     Frame to frame: the drift adds up; fuse and track against the model
     (``refine_pose_projective``) where a volume is at hand.  ``depth_filter`` and
-    ``filtered`` are ``frame_maps``'; ``kw`` goes to ``register_frames``."""
+    ``filtered`` are ``frame_maps``'; ``kw`` goes to ``register_frames``:
+    ``robust``, ``robust_scale``, ``point_weight`` and ``view_weights`` among it
+    (the latter resolved against ``depth_filter``)."""
     levels = len(tuple(iterations))
+    if kw.get("view_weights") is not None:
+        kw.setdefault("depth_filter", depth_filter)
     poses, records, fallbacks, prev = [np.eye(4)], [None], 0, None
     for d in depths:
         maps = frame_maps(d, intrinsics, depth_filter, levels, filtered, device=device)
@@ -668,8 +815,12 @@ def refine_pose_projective(depth, pose, intrinsics, volume, trunc: float, iterat
     motion from the frame's true camera to the camera at ``pose``.  Unlike
     ``refine_pose_tsdf`` the pose error at the surface may exceed ``trunc``: the
     gate is ``register_frames``' ``max_dist``.  ``depth_filter`` and ``filtered``
-    are ``frame_maps``'; ``kw`` goes to ``register_frames``."""
+    are ``frame_maps``'; ``kw`` goes to ``register_frames``: ``robust``,
+    ``robust_scale``, ``point_weight`` and ``view_weights`` among it (the latter
+    resolved against ``depth_filter``)."""
     iterations = tuple(int(k) for k in iterations)
+    if kw.get("view_weights") is not None:
+        kw.setdefault("depth_filter", depth_filter)
     dev = volume["tsdf"].device
     src = frame_maps(depth, intrinsics, depth_filter, len(iterations), filtered,
                      depth_min=depth_min, depth_max=depth_max, device=dev)
