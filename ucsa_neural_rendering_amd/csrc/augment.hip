@@ -28,8 +28,15 @@ struct AugBatch {
   AugOne p[AUG_MAX_BATCH];
 };
 
+// torch.clamp / torch.max / torch.min hand a NaN on; fminf / fmaxf drop it, and
+// a diverged render would come out as a finite, mostly black image.  Finite
+// and infinite values go through the same fminf / fmaxf as before.
 __device__ __forceinline__ float clamp01(float x) {
-  return fminf(fmaxf(x, 0.0f), 1.0f);
+  return x != x ? x : fminf(fmaxf(x, 0.0f), 1.0f);
+}
+
+__device__ __forceinline__ bool any_nan(float r, float g, float b) {
+  return r != r || g != g || b != b;
 }
 
 __device__ __forceinline__ float blend(float a, float b, float ratio) {
@@ -42,7 +49,9 @@ __device__ __forceinline__ float grey(float r, float g, float b) {
 
 __device__ __forceinline__ void hue_shift(float& r, float& g, float& b,
                                           float hue) {
-  const float maxc = fmaxf(r, fmaxf(g, b)), minc = fminf(r, fminf(g, b));
+  const bool bad = any_nan(r, g, b);
+  const float maxc = bad ? __builtin_nanf("") : fmaxf(r, fmaxf(g, b));
+  const float minc = bad ? __builtin_nanf("") : fminf(r, fminf(g, b));
   const bool eqc = maxc == minc;
   const float cr = maxc - minc;
   const float s = cr / (eqc ? 1.0f : maxc);
@@ -62,7 +71,8 @@ __device__ __forceinline__ void hue_shift(float& r, float& g, float& b,
   const float p = clamp01(v * (1.0f - s));
   const float q = clamp01(v * (1.0f - s * f));
   const float t = clamp01(v * (1.0f - (s * (1.0f - f))));
-  const int i = ((int)fi % 6 + 6) % 6;
+  // a NaN hue (NaN or inf pixel) has no sector: p, q, t are NaN whichever it is
+  const int i = fi == fi ? ((int)fi % 6 + 6) % 6 : 0;
   switch (i) {
     case 0: r = v; g = t; b = p; break;
     case 1: r = q; g = v; b = p; break;

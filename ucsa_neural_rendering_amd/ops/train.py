@@ -254,6 +254,11 @@ def augment(img, label, params, out_size=None):
         if not (label.is_cuda and label.dtype == torch.int64):
             raise _lib.UcsaError("label must be an int64 tensor on the GPU")
         label = label.contiguous()
+    if len(params) != B:
+        raise _lib.UcsaError(f"params must have one entry per image: {len(params)} for B = {B}")
+    if B == 0:      # an empty tensor has no data pointer to hand over
+        return (img.new_empty(0, 3, oh, ow),
+                None if label is None else label.new_empty(0, oh, ow))
     arr = (_lib.AugParams * B)()
     for k, q in enumerate(params):
         arr[k].order[:] = [int(v) for v in q["order"]]
