@@ -2579,8 +2579,8 @@ int32_t ucsa_tsdf_icp_sums(const float* tsdf, const float* weight, uint32_t nx, 
  * value and no matched output (step 9): they would be K x n.
  * One lane per point in work-groups of 256, UCSA_TSDF_ICP_BATCH_TILE transforms
  * per work-group along the grid's x axis (k_tsdf_icp_sums_batch); each
- * (work-group, transform) writes its own 29 doubles, then k_icp_reduce_batch
- * while more than one row per transform is left.  Every lane reaches the one
+ * (work-group, transform) writes its own 29 doubles, then k_icp_reduce (the
+ * transform on the grid's y axis) while more than one row per transform is left.  Every lane reaches the one
  * barrier; no atomics; the same bytes every run.  The inputs are never modified.
  * workspace: the stages' rows, K times those of ucsa_tsdf_icp_sums:
  * workspace_doubles >= K * rows(n) * 29 with rows(n) the sum of the counts
@@ -2720,9 +2720,10 @@ int32_t ucsa_projective_icp_sums(const float* points, const float* normals, uint
  * ucsa_tsdf_icp_sums: a robust kernel (Huber, Tukey) on the residual and an
  * optional weight per source point (ucsa_depth_confidence's, for one), so that a
  * pair that passes the gates but belongs to something the target does not show
- * stops pulling on the pose.  The siblings are untouched; these are new entry
- * points over new kernels.  tests/robust_numpy.py restates the contract; sums
- * (as int64 words), the weights and the per-point outputs equal it bit for bit.
+ * stops pulling on the pose.  The entry points stand beside their siblings and
+ * run the same kernels with the weight switched on.  tests/robust_numpy.py
+ * restates the contract; sums (as int64 words), the weights and the per-point
+ * outputs equal it bit for bit.
  *
  * Each takes its sibling's arguments, with the same meaning, and in addition
  * point_weight [n] float32 on the device or NULL (every p = 1), robust_kind
@@ -2752,8 +2753,9 @@ int32_t ucsa_projective_icp_sums(const float* points, const float* normals, uint
  * weight_out[i] = w for a row that counts, +0.0 otherwise.  The siblings'
  * per-point outputs report the geometric match whatever the weight: pixel /
  * residual (the unscaled r) and value / matched.
- * One lane per point in work-groups of 256 (k_projective_icp_sums_weighted,
- * k_tsdf_icp_sums_weighted), the weight loaded with the point, then k_icp_reduce
+ * One lane per point in work-groups of 256 (k_projective_icp_sums<true>,
+ * k_tsdf_icp_sums<true>: the siblings' kernel templates with WEIGHTED set), the
+ * weight loaded with the point, then k_icp_reduce
  * while more than one row is left.  Every lane reaches the one barrier; no
  * atomics; the same bytes every run.  The inputs are never modified.
  * Limits: the siblings', at the siblings' indices up to min_cos (15) and

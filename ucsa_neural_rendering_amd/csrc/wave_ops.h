@@ -88,6 +88,57 @@ __device__ __forceinline__ float wave_last(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// ---------------------------------------------------------------------------
+// The balanced tree of adjacent pairs over the wave's 64 values, the result in
+// every lane; all lanes are active.  Six exchange steps pair lane l with l^1,
+// l^2, a lane of the neighbouring quad (row_half_mirror), a lane of the
+// neighbouring half row (row_mirror), l^16 and l^32: after step k every lane of
+// an aligned group of 2^k lanes holds the sum of that group's tree, and any
+// lane of the partner group will do as the source (a + b is commutative in
+// IEEE, so both partners compute the same bits).  The first four steps are DPP
+// moves (no LDS), the last two __shfl_xor; a value travels in its 32-bit words.
+// For double the pairing and its order are a contract (the 29 sums of the ICP
+// steps, mesh_register.hip); for integers any order gives the same sum.
+// ---------------------------------------------------------------------------
+template <typename T, typename MOVE>
+__device__ __forceinline__ T wave_move_words(T v, MOVE move) {
+  static_assert(sizeof(T) % 4 == 0, "whole 32-bit words");
+  int w[sizeof(T) / 4];
+  __builtin_memcpy(w, &v, sizeof(T));
+#pragma unroll
+  for (unsigned k = 0; k < sizeof(T) / 4; ++k) w[k] = move(w[k]);
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+
+template <int CTRL, typename T>
+__device__ __forceinline__ T wave_dpp(T v) {
+  return wave_move_words(
+      v, [](int w) { return __builtin_amdgcn_update_dpp(0, w, CTRL, 0xf, 0xf, false); });
+}
+
+template <int MASK, typename T>
+__device__ __forceinline__ T wave_xor(T v) {
+  return wave_move_words(v, [](int w) { return __shfl_xor(w, MASK, 64); });
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_tree_sum(T v) {
+  v = v + wave_dpp<0xB1>(v);   // quad_perm:[1,0,3,2]: l ^ 1
+  v = v + wave_dpp<0x4E>(v);   // quad_perm:[2,3,0,1]: l ^ 2
+  v = v + wave_dpp<0x141>(v);  // row_half_mirror: l -> 7 - l, the other quad of the eight
+  v = v + wave_dpp<0x140>(v);  // row_mirror: l -> 15 - l, the other eight of the row
+  v = v + wave_xor<16>(v);
+  v = v + wave_xor<32>(v);
+  return v;
+}
+
+// the four waves of a work-group of 256 meet as (w0 + w1) + (w2 + w3): p is [4]
+template <typename T>
+__device__ __forceinline__ T waves4_sum(const T* p) {
+  return (p[0] + p[1]) + (p[2] + p[3]);
+}
+
 // Reduction over the four 16-lane rows (lanes l, l^16, l^32, l^48), result in
 // all of them: v_permlane32_swap / v_permlane16_swap (gfx950) exchange half
 // waves / neighbouring rows between two copies of the value -- mov + swap + op

@@ -46,6 +46,55 @@ def _transform12(transform):
     return fvec(t[:3].to(torch.float32).reshape(-1).tolist())
 
 
+def _volume_points(volume, points, max_rows: int, limit: str):
+    """the checked lattice of a TSDF ``volume`` and ``points`` [N,3] on its device, at most
+    ``max_rows`` (named ``limit``) -> ((nx, ny, nz), device, origin, spacing, points, N)"""
+    (nx, ny, nz), dev = volume_lattice(volume)
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
+        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
+                             f"{(nx, ny, nz)}")
+    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
+    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
+    n = int(pts.shape[0])
+    if n > max_rows:
+        raise _lib.UcsaError(f"points must have at most {limit} rows")
+    return (nx, ny, nz), dev, origin, spacing, pts, n
+
+
+def _device_transforms(transforms, dev, too_many):
+    """float32 [K,3,4] or [K,4,4] on ``dev`` -> (the contiguous rows [K,3,4], K);
+    ``too_many(K)`` is the error's message for a K beyond the caller's limit, else None"""
+    T = _gpu(transforms, "transforms", torch.float32, (None, None, 4), device=dev)
+    if T.shape[1] not in (3, 4):
+        raise _lib.UcsaError(f"transforms must be [K,3,4] or [K,4,4], got {tuple(T.shape)}")
+    T = T[:, :3].contiguous()
+    K = int(T.shape[0])
+    if too_many(K):
+        raise _lib.UcsaError(too_many(K))
+    return T, K
+
+
+def _sample_gates(min_weight, max_tsdf, closed: bool):
+    """``min_weight`` > 0 and ``max_tsdf`` in (0, 1] -- in (0, 1) when not ``closed`` -- as floats"""
+    min_weight = float(min_weight)
+    if not min_weight > 0:
+        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
+    max_tsdf = float(max_tsdf)
+    if not (0 < max_tsdf <= 1 if closed else 0 < max_tsdf < 1):
+        raise _lib.UcsaError(f"max_tsdf must be in (0, 1{']' if closed else ')'}, got "
+                             f"{max_tsdf!r}")
+    return min_weight, max_tsdf
+
+
+def _sums_buffers(n: int, dev, K=None):
+    """-> (the workspace or None when one stage suffices, its size in doubles, ``sums``
+    uninitialised: [29], or [K,29] for K transforms)"""
+    ws_doubles = (1 if K is None else K) * ICP_SUMS * workspace_rows(n)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
+    shape = ICP_SUMS if K is None else (K, ICP_SUMS)
+    return ws, ws_doubles, torch.empty(shape, dtype=torch.float64, device=dev)
+
+
 def face_unit_normals(verts, faces):
     """The unit normals of a mesh's faces -> float32 [F,3] on its device: the
     ``unit_normal`` of ``ops.mesh_pseudonormals`` without the vertex and edge
@@ -123,9 +172,7 @@ def icp_sums(grid, verts, faces, unit_normal, points, transform, max_dist: float
     if mode not in MODES:
         raise _lib.UcsaError(f"mode must be 'plane' or 'point', got {mode!r}")
     t12 = _transform12(transform)
-    ws_doubles = ICP_SUMS * workspace_rows(n)
-    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
-    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    ws, ws_doubles, sums = _sums_buffers(n, dev)
     face = torch.empty(n, dtype=torch.int32, device=dev) if return_matches else None
     dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
     check(lib().ucsa_icp_sums(
@@ -139,23 +186,11 @@ def icp_sums(grid, verts, faces, unit_normal, points, transform, max_dist: float
 
 def _tsdf_step_args(volume, points, transform, trunc, min_weight, max_tsdf):
     """the checked arguments ``tsdf_sums`` and ``tsdf_sums_weighted`` share"""
-    (nx, ny, nz), dev = volume_lattice(volume)
-    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
-        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
-                             f"{(nx, ny, nz)}")
-    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
-    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
-    n = int(pts.shape[0])
-    if n > 0x7FFFFFFF:
-        raise _lib.UcsaError("points must have at most 2^31-1 rows")
+    (nx, ny, nz), dev, origin, spacing, pts, n = \
+        _volume_points(volume, points, 0x7FFFFFFF, "2^31-1")
     t12 = _transform12(transform)
     trunc = _positive(trunc, "trunc")
-    min_weight = float(min_weight)
-    if not min_weight > 0:
-        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
-    max_tsdf = float(max_tsdf)
-    if not 0 < max_tsdf <= 1:
-        raise _lib.UcsaError(f"max_tsdf must be in (0, 1], got {max_tsdf!r}")
+    min_weight, max_tsdf = _sample_gates(min_weight, max_tsdf, True)
     return (nx, ny, nz), dev, origin, spacing, pts, n, t12, trunc, min_weight, max_tsdf
 
 
@@ -181,9 +216,7 @@ def tsdf_sums(volume, points, transform, trunc: float, min_weight: float = 1.0,
     (include/ucsa_hip.h)."""
     (nx, ny, nz), dev, origin, spacing, pts, n, t12, trunc, min_weight, max_tsdf = \
         _tsdf_step_args(volume, points, transform, trunc, min_weight, max_tsdf)
-    ws_doubles = ICP_SUMS * workspace_rows(n)
-    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
-    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    ws, ws_doubles, sums = _sums_buffers(n, dev)
     value = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
     matched = torch.empty(n, dtype=torch.uint8, device=dev) if return_matches else None
     check(lib().ucsa_tsdf_icp_sums(
@@ -206,32 +239,13 @@ def tsdf_sums_batch(volume, points, transforms, trunc: float, min_weight: float 
     ``TSDF_SUMS_BATCH_MAX`` transforms; K = 0 gives an empty result.
     ``utils.registration.register_points_tsdf_batch`` iterates K loops in lock
     step on it.  Contract of ucsa_tsdf_icp_sums_batch (include/ucsa_hip.h)."""
-    (nx, ny, nz), dev = volume_lattice(volume)
-    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
-        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
-                             f"{(nx, ny, nz)}")
-    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
-    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
-    n = int(pts.shape[0])
-    if n > TSDF_SCORE_MAX_POINTS:
-        raise _lib.UcsaError("points must have at most 2^23 rows")
-    T = _gpu(transforms, "transforms", torch.float32, (None, None, 4), device=dev)
-    if T.shape[1] not in (3, 4):
-        raise _lib.UcsaError(f"transforms must be [K,3,4] or [K,4,4], got {tuple(T.shape)}")
-    T = T[:, :3].contiguous()
-    K = int(T.shape[0])
-    if K > TSDF_SUMS_BATCH_MAX:
-        raise _lib.UcsaError(f"transforms must have at most {TSDF_SUMS_BATCH_MAX} rows, got {K}")
+    (nx, ny, nz), dev, origin, spacing, pts, n = \
+        _volume_points(volume, points, TSDF_SCORE_MAX_POINTS, "2^23")
+    T, K = _device_transforms(transforms, dev, lambda K: K > TSDF_SUMS_BATCH_MAX and (
+        f"transforms must have at most {TSDF_SUMS_BATCH_MAX} rows, got {K}"))
     trunc = _positive(trunc, "trunc")
-    min_weight = float(min_weight)
-    if not min_weight > 0:
-        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
-    max_tsdf = float(max_tsdf)
-    if not 0 < max_tsdf <= 1:
-        raise _lib.UcsaError(f"max_tsdf must be in (0, 1], got {max_tsdf!r}")
-    ws_doubles = K * ICP_SUMS * workspace_rows(n)
-    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
-    sums = torch.empty((K, ICP_SUMS), dtype=torch.float64, device=dev)
+    min_weight, max_tsdf = _sample_gates(min_weight, max_tsdf, True)
+    ws, ws_doubles, sums = _sums_buffers(n, dev, K)
     check(lib().ucsa_tsdf_icp_sums_batch(
         _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
         _ptr(pts) if n else None, n, _ptr(T) if K else None, K, trunc, min_weight, max_tsdf,
@@ -256,28 +270,11 @@ def tsdf_scores(volume, points, transforms, min_weight: float = 1.0, max_tsdf: f
     ``utils.registration.global_register_points_tsdf`` ranks hypotheses by
     inliers - free, then sum e^2.  Contract of ucsa_tsdf_score_transforms
     (include/ucsa_hip.h)."""
-    (nx, ny, nz), dev = volume_lattice(volume)
-    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7FFFFFFF:
-        raise _lib.UcsaError(f"volume: dims must be >= 2 each with at most 2^31-1 points, got "
-                             f"{(nx, ny, nz)}")
-    origin, spacing = _origin_spacing("volume", volume["origin"], volume["spacing"])
-    pts = _gpu(points, "points", torch.float32, (None, 3), device=dev)
-    n = int(pts.shape[0])
-    if n > TSDF_SCORE_MAX_POINTS:
-        raise _lib.UcsaError("points must have at most 2^23 rows")
-    T = _gpu(transforms, "transforms", torch.float32, (None, None, 4), device=dev)
-    if T.shape[1] not in (3, 4):
-        raise _lib.UcsaError(f"transforms must be [K,3,4] or [K,4,4], got {tuple(T.shape)}")
-    T = T[:, :3].contiguous()
-    K = int(T.shape[0])
-    if K > 0x7FFFFFFF:
-        raise _lib.UcsaError("transforms must have at most 2^31-1 rows")
-    min_weight = float(min_weight)
-    if not min_weight > 0:
-        raise _lib.UcsaError(f"min_weight must be > 0, got {min_weight!r}")
-    max_tsdf = float(max_tsdf)
-    if not 0 < max_tsdf < 1:
-        raise _lib.UcsaError(f"max_tsdf must be in (0, 1), got {max_tsdf!r}")
+    (nx, ny, nz), dev, origin, spacing, pts, n = \
+        _volume_points(volume, points, TSDF_SCORE_MAX_POINTS, "2^23")
+    T, K = _device_transforms(transforms, dev, lambda K: K > 0x7FFFFFFF and (
+        "transforms must have at most 2^31-1 rows"))
+    min_weight, max_tsdf = _sample_gates(min_weight, max_tsdf, False)
     scores = torch.empty((K, 4), dtype=torch.int64, device=dev)
     check(lib().ucsa_tsdf_score_transforms(
         _ptr(volume["tsdf"]), _ptr(volume["weight"]), nx, ny, nz, fvec(origin), fvec(spacing),
@@ -344,9 +341,7 @@ def projective_sums(points, normals, target_points, target_normals, target_mask,
     dev, pts, n, nrm, tp, tn, tm, H, W, (fx, fy, cx, cy), t12, max_dist, min_cos = \
         _projective_step_args(points, normals, target_points, target_normals, target_mask,
                               intrinsics, transform, max_dist, min_cos, reject)
-    ws_doubles = ICP_SUMS * workspace_rows(n)
-    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
-    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    ws, ws_doubles, sums = _sums_buffers(n, dev)
     pixel = torch.empty(n, dtype=torch.int32, device=dev) if return_matches else None
     residual = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
     check(lib().ucsa_projective_icp_sums(
@@ -401,9 +396,7 @@ def projective_sums_weighted(points, normals, target_points, target_normals, tar
         _projective_step_args(points, normals, target_points, target_normals, target_mask,
                               intrinsics, transform, max_dist, min_cos, reject)
     pw, kind, scale = _robust_args(point_weight, robust, robust_scale, n, dev)
-    ws_doubles = ICP_SUMS * workspace_rows(n)
-    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
-    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    ws, ws_doubles, sums = _sums_buffers(n, dev)
     pixel = torch.empty(n, dtype=torch.int32, device=dev) if return_matches else None
     residual = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
     weight = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
@@ -430,9 +423,7 @@ def tsdf_sums_weighted(volume, points, transform, trunc: float, min_weight: floa
     (nx, ny, nz), dev, origin, spacing, pts, n, t12, trunc, min_weight, max_tsdf = \
         _tsdf_step_args(volume, points, transform, trunc, min_weight, max_tsdf)
     pw, kind, scale = _robust_args(point_weight, robust, robust_scale, n, dev)
-    ws_doubles = ICP_SUMS * workspace_rows(n)
-    ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev) if ws_doubles else None
-    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    ws, ws_doubles, sums = _sums_buffers(n, dev)
     value = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None
     matched = torch.empty(n, dtype=torch.uint8, device=dev) if return_matches else None
     weight = torch.empty(n, dtype=torch.float32, device=dev) if return_matches else None

@@ -196,6 +196,29 @@ def _on_device(x, dtype, cols, device):
     return t.to(device=device, dtype=dtype).reshape(-1, cols).contiguous()
 
 
+def _host_step(sums, T, rcond, rows, tol_rot, tol_trans):
+    """The host half of one iteration, the same in every loop: ``normal_equations``,
+    ``solve_step`` and ``compose`` on the 29 doubles ``sums`` -> (the new ``T``, ``rank``,
+    the keys every ``history`` entry starts from -- ``matched``, ``rmse``, ``omega``,
+    ``upsilon`` --, whether the exit test held).  ``rows`` is the rows per point: 3.0 in
+    mode "point", else 1.0 (a division and a product by 1.0 are exact)."""
+    _, _, sse, count = normal_equations(sums)
+    xi, rank = solve_step(sums, rcond)
+    om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
+    entry = {"matched": int(round(count / rows)),
+             "rmse": math.sqrt(sse * rows / count) if count > 0 else float("nan"),
+             "omega": om, "upsilon": up}
+    return compose(T, xi), rank, entry, bool(count > 0 and om <= tol_rot and up <= tol_trans)
+
+
+def _result(T, history, rank, done, converged, n_points):
+    """the dict every loop returns"""
+    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
+    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
+            "iterations": done, "converged": converged, "history": history,
+            "n_points": int(n_points)}
+
+
 def register_points(points, verts, faces, init=None, max_dist: float = 0.5, iterations: int = 30,
                     mode: str = "plane", max_dist_schedule=None, tol_rot: float = 1e-6,
                     tol_trans: float = 1e-6, grid=None, sort_points: bool = True,
@@ -242,21 +265,12 @@ def register_points(points, verts, faces, init=None, max_dist: float = 0.5, iter
     for k in range(int(iterations)):
         md = schedule[min(k, len(schedule) - 1)]
         sums = ops.register.icp_sums(grid, v, f, unit, pts, T, md, mode).cpu().numpy()
-        _, _, sse, count = normal_equations(sums)
-        xi, rank = solve_step(sums, rcond)
-        T = compose(T, xi)
+        T, rank, entry, converged = _host_step(sums, T, rcond, rows, tol_rot, tol_trans)
         done = k + 1
-        om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
-        history.append({"matched": int(round(count / rows)),
-                        "rmse": math.sqrt(sse * rows / count) if count > 0 else float("nan"),
-                        "omega": om, "upsilon": up, "max_dist": md, "sums": sums})
-        if count > 0 and om <= tol_rot and up <= tol_trans:
-            converged = True
+        history.append({**entry, "max_dist": md, "sums": sums})
+        if converged:
             break
-    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
-    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
-            "iterations": done, "converged": converged, "history": history,
-            "n_points": int(pts.shape[0])}
+    return _result(T, history, rank, done, converged, pts.shape[0])
 
 
 def _mesh_arrays(mesh):
@@ -418,21 +432,12 @@ def register_points_tsdf(points, volume, trunc: float, init=None, iterations: in
             extra = {"robust": robust, "robust_scale": sc}
         else:
             sums = ops.register.tsdf_sums(volume, pts, T, trunc, min_weight, mt).cpu().numpy()
-        _, _, sse, count = normal_equations(sums)
-        xi, rank = solve_step(sums, rcond)
-        T = compose(T, xi)
+        T, rank, entry, converged = _host_step(sums, T, rcond, 1.0, tol_rot, tol_trans)
         done = k + 1
-        om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
-        history.append({"matched": int(round(count)),
-                        "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
-                        "omega": om, "upsilon": up, "max_tsdf": mt, "sums": sums, **extra})
-        if count > 0 and om <= tol_rot and up <= tol_trans:
-            converged = True
+        history.append({**entry, "max_tsdf": mt, "sums": sums, **extra})
+        if converged:
             break
-    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
-    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
-            "iterations": done, "converged": converged, "history": history,
-            "n_points": int(pts.shape[0])}
+    return _result(T, history, rank, done, converged, pts.shape[0])
 
 
 def _float_rows(T):
@@ -473,26 +478,14 @@ def lockstep_loop(sums_fn, inits, iterations: int = 30, max_tsdf: float = 1.0,
         still = []
         for a, j in enumerate(active):
             sums = rows[a].copy()
-            _, _, sse, count = normal_equations(sums)
-            xi, rank[j] = solve_step(sums, rcond)
-            T[j] = compose(T[j], xi)
+            T[j], rank[j], entry, converged[j] = _host_step(sums, T[j], rcond, 1.0, tol_rot,
+                                                            tol_trans)
             done[j] = k + 1
-            om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
-            history[j].append({"matched": int(round(count)),
-                               "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
-                               "omega": om, "upsilon": up, "max_tsdf": mt, "sums": sums})
-            if count > 0 and om <= tol_rot and up <= tol_trans:
-                converged[j] = True
-            else:
+            history[j].append({**entry, "max_tsdf": mt, "sums": sums})
+            if not converged[j]:
                 still.append(j)
         active = still
-    out = []
-    for j in range(K):
-        last = history[j][-1] if history[j] else {"matched": 0, "rmse": float("nan")}
-        out.append({"transform": T[j], "rmse": last["rmse"], "matched": last["matched"],
-                    "rank": rank[j], "iterations": done[j], "converged": converged[j],
-                    "history": history[j], "n_points": int(n_points)})
-    return out
+    return [_result(T[j], history[j], rank[j], done[j], converged[j], n_points) for j in range(K)]
 
 
 def register_points_tsdf_batch(points, volume, trunc: float, inits, iterations: int = 30,
@@ -723,22 +716,13 @@ def register_frames(src_maps, dst_maps, intrinsics, init=None, iterations=(10, 5
                 sums = ops.register.projective_sums(pts, nrm, dst["points"], dst["normals"],
                                                     dst["mask"], K, T, max_dist, min_cos,
                                                     reject).cpu().numpy()
-            _, _, sse, count = normal_equations(sums)
-            xi, rank = solve_step(sums, rcond)
-            T = compose(T, xi)
+            T, rank, entry, converged = _host_step(sums, T, rcond, 1.0, tol_rot, tol_trans)
             done += 1
-            om, up = float(np.linalg.norm(xi[:3])), float(np.linalg.norm(xi[3:]))
-            history.append({"level": level, "matched": int(round(count)),
-                            "rmse": math.sqrt(sse / count) if count > 0 else float("nan"),
-                            "omega": om, "upsilon": up, "max_dist": float(max_dist),
-                            "sums": sums, **extra})
-            if count > 0 and om <= tol_rot and up <= tol_trans:
-                converged = True
+            history.append({"level": level, **entry, "max_dist": float(max_dist), "sums": sums,
+                            **extra})
+            if converged:
                 break
-    last = history[-1] if history else {"matched": 0, "rmse": float("nan")}
-    return {"transform": T, "rmse": last["rmse"], "matched": last["matched"], "rank": rank,
-            "iterations": done, "converged": converged, "history": history,
-            "n_points": n_points}
+    return _result(T, history, rank, done, converged, n_points)
 
 
 def odometry(depths, intrinsics, depth_filter=None, iterations=(10, 5, 4),
